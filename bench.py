@@ -131,7 +131,11 @@ def parse():
     ap.add_argument("--child", action="store_true", help="internal: a companion run started by the main process (timed region only)")
     ap.add_argument("--caption-tokens", type=int, default=32, help="N=1 only: also time cached greedy decoding of this many tokens per image (0 = skip)")
     ap.add_argument("--gemm-table", default="", help="write the per-shape GEMM timing table (measured inside the timed steps) to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.stock_tuning == "auto":
         args.stock_tuning = args.backbone_tweaks
     if args.child:
@@ -478,6 +482,44 @@ def cpu_baseline(args):
     return out
 
 
+DUMP_VALUES_PER_ARRAY = 6 * 2 ** 20      # float32 values in each of grads.npy / params.npy: 2 x 24 MiB, under the 64 MB bound of --dump-outputs
+
+
+def dump_outputs(out_dir, params, loss, rows_used=None):
+    """--dump-outputs DIR: what the last timed step computed, written right after the timed region (before any untimed step changes the
+    weights again), so that two builds of the project run with the same arguments - same seeded weights, batch and dropout stream - can be
+    compared output for output:
+        loss.npy     the step's loss, float64, shape (1,)
+        grads.npy    the trainable parameters' gradients of that step, float32 (parameters without a .grad are left out)
+        params.npy   the trainable parameters after that step's optimizer update, float32
+    grads / params concatenate, in `parameters_trainable()` order, each whole tensor when it has at most `per` elements, else `per` of its
+    elements drawn with a generator seeded by the tensor's position (the same elements in every run); per = DUMP_VALUES_PER_ARRAY /
+    number of trainable tensors.  rows_used = {id(parameter): n}: only the first n rows of that parameter and of its gradient are written -
+    the time embeddings of frames the batch does not have take no part in the step, and what is left in those rows of the gradient after
+    the step is not defined by it (it differs from run to run)."""
+    import numpy as np
+    per = max(1, DUMP_VALUES_PER_ARRAY // max(len(params), 1))
+    grads, weights = [], []
+    with torch.no_grad():
+        for i, p in enumerate(params):
+            n_rows = (rows_used or {}).get(id(p))
+            numel = p.numel() if n_rows is None else p[:n_rows].numel()
+            idx = None
+            if numel > per:
+                idx = torch.randint(numel, (per,), generator=torch.Generator().manual_seed(i)).to(p.device)
+
+            def pick(t):
+                flat = (t if n_rows is None else t[:n_rows]).detach().reshape(-1)
+                return (flat if idx is None else flat[idx]).float().cpu()
+            weights.append(pick(p))
+            if p.grad is not None:
+                grads.append(pick(p.grad))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss.float().item())], np.float64))
+    np.save(os.path.join(out_dir, "grads.npy"), (torch.cat(grads) if grads else torch.zeros(0)).numpy())
+    np.save(os.path.join(out_dir, "params.npy"), torch.cat(weights).numpy())
+
+
 def _dump_allocator_map(path):
     """Every allocator segment and block (address, size, state, the innermost repository / torch frames that allocated it), gzip JSON:
     a GPU memory-access fault prints an address, this says whose buffer it is next to."""
@@ -690,6 +732,9 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        tpe = model.flamingo.resampler.time_pos_emb
+        dump_outputs(args.dump_outputs, params, loss_last, rows_used={id(tpe): min(max(args.frames, 1), tpe.shape[0])})
     # the error word of the fused cross-attention kernels' in-launch hand-offs (a timed-out arrival wait = a launch computed on garbage): read
     # after the timed region and again after the instrumented steps; a non-zero word is printed in `config` and fails the run
     from flamingo_mini_amd import functional as _Fs

@@ -458,7 +458,7 @@ def test_in_launch_exchange_beside_a_persistent_kernel(b):
     usual distance of the separate launches.  A third leg hands the SAME buffers to a run on another stream: it must get its own counters
     (functional.ensure_sync_buffer is per device AND stream), not share the first stream's."""
     from flamingo_mini_amd import functional as F
-    from util import cu_hog
+    from util import cu_hog, hog_stream
     dtype = torch.bfloat16
     L, nv, dim, dv, heads, dh, ffm = 32, 64, 1280, 256, 8, 64, 2
     p = xattn_params(dim, dv, heads, dh, ffm, tag="hog")
@@ -487,7 +487,7 @@ def test_in_launch_exchange_beside_a_persistent_kernel(b):
         torch.cuda.synchronize()
     finally:
         F.use_sync_exchange = True
-    hog, side = cu_hog(), torch.cuda.Stream()
+    hog, side = cu_hog(), hog_stream()
     sink = torch.zeros(4, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     rc = hog.cu_hog_launch(32, 128 * 1024, 1500.0, sink.data_ptr(), side.cuda_stream)     # 32 CUs held for 1.5 s
@@ -531,7 +531,7 @@ def test_denied_co_residency_is_detected_not_silent():
     BEFORE the fused one already wait for the other kernel to end - slow, but correct: status 0.)"""
     import time
     from flamingo_mini_amd import functional as F
-    from util import cu_hog
+    from util import cu_hog, hog_stream
     dtype = torch.bfloat16
     b, L, nv, dim, dv = 32, 32, 64, 1280, 256
     p = xattn_params(dim, dv, 8, 64, 2, tag="denied")
@@ -555,7 +555,7 @@ def test_denied_co_residency_is_detected_not_silent():
     props = torch.cuda.get_device_properties(0)
     if props.multi_processor_count != 256:
         pytest.skip("the scenario is laid out for 8 XCDs of 32 CUs")
-    hog, side = cu_hog(), torch.cuda.Stream()
+    hog, side = cu_hog(), hog_stream()
     sink = torch.zeros(4, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     assert hog.cu_hog_launch(208, 128 * 1024, 3000.0, sink.data_ptr(), side.cuda_stream) == 0      # 26 CUs of every XCD, for 3 s

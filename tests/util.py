@@ -78,3 +78,12 @@ def cu_hog():
     lib.cu_hog_launch.restype = ctypes.c_int
     lib.cu_hog_launch.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
     return lib
+
+
+def hog_stream():
+    """The stream to launch cu_hog on: it must run BESIDE the current stream's launches, not ahead of them.  HIP maps streams onto a small,
+    fixed pool of hardware queues and, once the pool is full, hands a new stream the least-used queue - late in
+    a test session, after many streams were created, that can be the current stream's own queue, and then every launch the test makes
+    waits behind the hog in that queue.  High-priority streams draw from a pool of their own, apart from the normal-priority queues the
+    test's launches go to."""
+    return torch.cuda.Stream(priority=-1)
