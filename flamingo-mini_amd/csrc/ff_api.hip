@@ -327,10 +327,10 @@ static int resampler_bwd(const ff_resampler_desc* d, const void* x_f, const void
     void* dx_in = W.dx0;
     // d latents = sum over the batch of d x_0 (:179);  d time_pos_emb[t] = sum_{b, n} d x_f[b, t, n] (:166)
     FF_TRY(rows_reduce(s.dt, Mq, s.D, pD, s.q, 1, dx_in, G[0], W.ws, gws, st));
-    if (s.nte > s.T) {
-        hipError_t e = hipMemsetAsync((char*)G[1] + (size_t)s.T * s.D * s.es, 0, (size_t)(s.nte - s.T) * s.D * s.es, st);
-        FF_CHECK(e == hipSuccess, FF_ERR_LAUNCH, "resampler_bwd: memset: %s", hipGetErrorString(e));
-    }
+    // d time_pos_emb rows of frames the batch does not have: exact zeros.  A kernel, not hipMemsetAsync: with the memset, replays of a
+    // captured training step left int32-looking bytes of some other buffer in those rows (tests/test_hip_bounds.py::
+    // test_unused_time_embedding_gradient_rows_are_zero, graphed and piecewise); a launch on the stream keeps its order and the zeros.
+    if (s.nte > s.T) FF_TRY(zero_bytes((char*)G[1] + (size_t)s.T * s.D * s.es, (size_t)(s.nte - s.T) * s.D * s.es, st));
     return rows_reduce(s.dt, Mf, s.D, pD, s.F, s.v, dxf, G[1], W.ws, gws, st);
 }
 
@@ -499,10 +499,7 @@ static int rs_prologue_bwd(const ff_resampler_desc* d, const void* dx0, const vo
     const RowMap pD = plain_rows(s.D);
     // d latents = sum over the batch of d x_0 (:179);  d time_pos_emb[t] = sum_{b, n} d x_f[b, t, n] (:166)
     FF_TRY(rows_reduce(s.dt, s.Bn * s.q, s.D, pD, s.q, 1, dx0, d_latents, W.ws, W.ws_bytes, st));
-    if (s.nte > s.T) {
-        hipError_t e = hipMemsetAsync((char*)d_tpe + (size_t)s.T * s.D * s.es, 0, (size_t)(s.nte - s.T) * s.D * s.es, st);
-        FF_CHECK(e == hipSuccess, FF_ERR_LAUNCH, "resampler_prologue_bwd: memset: %s", hipGetErrorString(e));
-    }
+    if (s.nte > s.T) FF_TRY(zero_bytes((char*)d_tpe + (size_t)s.T * s.D * s.es, (size_t)(s.nte - s.T) * s.D * s.es, st));   // see resampler_bwd
     return rows_reduce(s.dt, s.Bn * s.F, s.D, pD, s.F, s.v, dx_f, d_tpe, W.ws, W.ws_bytes, st);
 }
 

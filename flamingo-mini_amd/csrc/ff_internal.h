@@ -116,6 +116,8 @@ int layernorm_bwd(const LnArgs& a, const void* dy, const void* x, const void* ad
                   size_t ws_bytes, hipStream_t st, const LnDots* dots = nullptr, LnPending* pending = nullptr);
 int layernorm_bwd_finish(int dtype, const LnPending* sets, int n, hipStream_t st);
 size_t rows_reduce_workspace(int rows, int cols, int rows_per_batch, int rows_per_group);
+// zero `bytes` bytes at `p` with a kernel on `st` (ordered like every other launch of the stream, also inside a captured graph)
+int zero_bytes(void* p, size_t bytes, hipStream_t st);
 int rows_reduce(int dtype, int rows, int cols, RowMap x_map, int rows_per_batch, int rows_per_group, const void* x,
                 void* out, void* ws, size_t ws_bytes, hipStream_t st);
 size_t gate_grad_workspace(int rows, int cols);

@@ -817,6 +817,18 @@ int rows_reduce(int dtype, int rows, int cols, RowMap x_map, int rows_per_batch,
     return check_launch("rows_reduce_final");
 }
 
+__global__ __launch_bounds__(256) void zero_bytes_kernel(unsigned char* __restrict__ p, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0;
+}
+
+int zero_bytes(void* p, size_t bytes, hipStream_t st) {
+    if (bytes == 0) return 0;
+    FF_CHECK(p, FF_ERR_SHAPE, "zero_bytes: null pointer");
+    const int grid = (int)std::min<size_t>(1024, (bytes + 255) / 256);
+    hipLaunchKernelGGL(zero_bytes_kernel, dim3(grid), dim3(256), 0, st, (unsigned char*)p, bytes);
+    return check_launch("zero_bytes");
+}
+
 static int gate_blocks(long long n) { return (int)std::max<long long>(1, std::min<long long>(512, n / 4096)); }
 size_t gate_grad_workspace(int rows, int cols) { return (size_t)gate_blocks((long long)rows * cols) * sizeof(float); }
 

@@ -18,6 +18,28 @@ from . import ffi
 _grad_ready_callbacks: list = []
 
 
+# ---- the allocation seam ----------------------------------------------------------------------------
+# Every buffer a kernel of this module writes (outputs, workspaces, saved state, flat gradients) is allocated through these four helpers,
+# which call exactly what a plain allocation would.  tests/guarded.py swaps them for versions that place each buffer between guard bands
+# and poison its body, to catch elements a kernel never writes and writes past a buffer's end.  Not covered, on purpose: the gradient
+# arena's slices (GradArena.take: carved from one buffer the arena's owner allocates, so no guard sits between two slices), the sync
+# buffers (ensure_sync_buffer: zeroed once and kept for the life of the process) and the autograd ordering tokens (never written).
+def _new(shape, dtype, device) -> torch.Tensor:
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _new_zeros(shape, dtype, device) -> torch.Tensor:
+    return torch.zeros(shape, dtype=dtype, device=device)
+
+
+def _new_like(t: torch.Tensor, dtype=None) -> torch.Tensor:
+    return torch.empty_like(t, dtype=dtype)
+
+
+def _new_zeros_like(t: torch.Tensor, dtype=None) -> torch.Tensor:
+    return torch.zeros_like(t, dtype=dtype)
+
+
 def _owners(params, flat=None):
     offs, _ = _flat_offsets(params)
     return [(p, o, p.numel()) for p, o in zip(params, offs)]
@@ -189,7 +211,7 @@ class GradArena:
             return None
         if self.buf.dtype != dtype or self.buf.device != device or self.used + total > self.buf.numel():
             return None
-        out = self.buf[self.used:self.used + total]
+        out = self.buf[self.used:self.used + total]        # not through the allocation seam: test guards do not cover arena slices
         self.used += total
         return out
 
@@ -211,12 +233,12 @@ def _flat_grads(params: Sequence[torch.Tensor]):
     offs, total = _flat_offsets(params)
     flat = _grad_arena.take(total, params[0].dtype, params[0].device) if _grad_arena is not None else None
     if flat is None:
-        flat = torch.empty(total, dtype=params[0].dtype, device=params[0].device)   # alignment pads are never read
+        flat = _new(total, params[0].dtype, params[0].device)   # alignment pads are never read (arena slices: not guarded, see _new)
     return flat, [flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)]
 
 
 def _empty_bytes(n: int, device) -> torch.Tensor:
-    return torch.empty(max(int(n), 16), dtype=torch.uint8, device=device)
+    return _new(max(int(n), 16), torch.uint8, device)
 
 
 def autocast_compute_dtype(ref: torch.Tensor) -> Optional[torch.dtype]:
@@ -259,7 +281,7 @@ def text_time(media_locations: torch.Tensor) -> torch.Tensor:
         ml = ml.to(torch.int64)
     ml = ml.contiguous()
     b, n = ml.shape
-    out = torch.empty((b, n), dtype=torch.int32, device=ml.device)
+    out = _new((b, n), torch.int32, ml.device)
     ffi.check(ffi.lib().ff_text_time(b, n, ml.data_ptr(), ml.element_size(), out.data_ptr(), ffi.stream_handle(ml.device)), "ff_text_time")
     return out
 
@@ -284,7 +306,7 @@ class _ResamplerFn(torch.autograd.Function):
         dev = x_f.device
         saved = _empty_bytes(lib.ff_resampler_saved_bytes(desc), dev)
         scratch = _empty_bytes(lib.ff_resampler_scratch_bytes(desc), dev)
-        out = torch.empty((x_f.shape[0], cfg[3], x_f.shape[3]), dtype=x_f.dtype, device=dev)
+        out = _new((x_f.shape[0], cfg[3], x_f.shape[3]), x_f.dtype, dev)
         ffi.check(lib.ff_resampler_fwd(desc, x_f.data_ptr(), ffi.ptr_array(params), out.data_ptr(), saved.data_ptr(), saved.numel(),
                                        scratch.data_ptr(), scratch.numel(), ffi.stream_handle(dev)), "ff_resampler_fwd")
         ctx.cfg = cfg
@@ -299,7 +321,7 @@ class _ResamplerFn(torch.autograd.Function):
         dev = x_f.device
         dout = dout.contiguous()
         flat, grads = _flat_grads(params)
-        dx_f = torch.empty_like(x_f) if ctx.needs_input_grad[0] else None
+        dx_f = _new_like(x_f) if ctx.needs_input_grad[0] else None
         scratch = _empty_bytes(lib.ff_resampler_scratch_bytes(desc), dev)
         ffi.check(lib.ff_resampler_bwd(desc, x_f.data_ptr(), ffi.ptr_array(params), dout.data_ptr(), saved.data_ptr(), saved.numel(),
                                        ffi.ptr_array(grads), ffi.ptr(dx_f), scratch.data_ptr(), scratch.numel(), ffi.stream_handle(dev)),
@@ -374,7 +396,7 @@ class _RsLayerFn(torch.autograd.Function):
         params = tuple(p.contiguous() for p in params)
         saved = _empty_bytes(lib.ff_resampler_layer_saved_bytes(desc), dev)
         scratch = _empty_bytes(lib.ff_resampler_layer_scratch_bytes(desc), dev)
-        out = torch.empty((x_f.shape[0], cfg[3], x_f.shape[3]), dtype=x_f.dtype, device=dev)
+        out = _new((x_f.shape[0], cfg[3], x_f.shape[3]), x_f.dtype, dev)
         ffi.check(lib.ff_resampler_layer_fwd(desc, x_f.data_ptr(), tpe.data_ptr(), pro.data_ptr(), pro.numel(), x.data_ptr(), 1 if first else 0,
                                              ffi.ptr_array(params), out.data_ptr(), saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(),
                                              ffi.stream_handle(dev)), "ff_resampler_layer_fwd")
@@ -393,8 +415,8 @@ class _RsLayerFn(torch.autograd.Function):
         flat, grads = _flat_grads(params)
         accumulate = rp.dxf is not None                      # the first layer_bwd call of a pass (the LAST layer) overwrites
         if rp.dxf is None:
-            rp.dxf = torch.empty_like(x_f)
-        dx_in = torch.empty_like(dout)
+            rp.dxf = _new_like(x_f)
+        dx_in = _new_like(dout)
         scratch = _empty_bytes(lib.ff_resampler_layer_scratch_bytes(desc), dev)
         ffi.check(lib.ff_resampler_layer_bwd(desc, x_f.data_ptr(), tpe.data_ptr(), pro.data_ptr(), pro.numel(), x.data_ptr(), 1 if ctx.first else 0,
                                              ffi.ptr_array(params), dout.data_ptr(), saved.data_ptr(), saved.numel(), ffi.ptr_array(grads), dx_in.data_ptr(),
@@ -414,7 +436,7 @@ class _RsEpilogueFn(torch.autograd.Function):
         desc = _resampler_desc(x_f, cfg)
         x = x.contiguous()
         epi = _empty_bytes(lib.ff_resampler_epilogue_saved_bytes(desc), x.device)
-        out = torch.empty_like(x)
+        out = _new_like(x)
         ffi.check(lib.ff_resampler_epilogue_fwd(desc, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), epi.data_ptr(), epi.numel(),
                                                 ffi.stream_handle(x.device)), "ff_resampler_epilogue_fwd")
         ctx.cfg, ctx.xf_shape = cfg, tuple(x_f.shape)
@@ -430,7 +452,7 @@ class _RsEpilogueFn(torch.autograd.Function):
         desc = ffi.ResamplerDesc(ffi.dtype_code(x.dtype), b, T, v, d, depth, heads, dim_head, num_latents, nte, ff_mult, ffi.ACTS[act])
         dout = dout.contiguous()
         flat, grads = _flat_grads([gamma, beta])
-        dx = torch.empty_like(x)
+        dx = _new_like(x)
         scratch = _empty_bytes(lib.ff_resampler_layer_scratch_bytes(desc), x.device)
         ffi.check(lib.ff_resampler_epilogue_bwd(desc, dout.data_ptr(), x.data_ptr(), gamma.data_ptr(), epi.data_ptr(), epi.numel(), dx.data_ptr(),
                                                 grads[0].data_ptr(), grads[1].data_ptr(), scratch.data_ptr(), scratch.numel(), ffi.stream_handle(x.device)),
@@ -596,7 +618,7 @@ class _XattnBlockFn(torch.autograd.Function):
         dev = y.device
         saved = _empty_bytes(lib.ff_xattn_saved_bytes(desc), dev)
         scratch = _empty_bytes(lib.ff_xattn_scratch_bytes(desc), dev)
-        out = torch.empty_like(y)
+        out = _new_like(y)
         ffi.check(lib.ff_xattn_block_fwd(desc, y.data_ptr(), vf.data_ptr(), tt.data_ptr(), ffi.ptr_array(params), None, None,
                                          out.data_ptr(), saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(),
                                          ffi.stream_handle(dev)), "ff_xattn_block_fwd")
@@ -612,10 +634,10 @@ class _XattnBlockFn(torch.autograd.Function):
         y, vf, tt, saved, *params = ctx.saved_tensors
         desc = _xattn_desc(y, vf.shape[1], ctx.n_visual, vf.shape[3], ctx.cfg, tt, sync=ctx.sync)
         dev = y.device
-        dout = torch.zeros_like(y) if dout is None else dout.contiguous()
+        dout = _new_zeros_like(y) if dout is None else dout.contiguous()
         flat, grads = _flat_grads(params)
-        dy = torch.empty_like(y)
-        dvf = torch.empty_like(vf) if ctx.needs_input_grad[1] else None
+        dy = _new_like(y)
+        dvf = _new_like(vf) if ctx.needs_input_grad[1] else None
         scratch = _empty_bytes(lib.ff_xattn_scratch_bytes(desc), dev)
         ffi.check(lib.ff_xattn_block_bwd(desc, y.data_ptr(), vf.data_ptr(), tt.data_ptr(), ffi.ptr_array(params), dout.data_ptr(),
                                          saved.data_ptr(), saved.numel(), ffi.ptr_array(grads), dy.data_ptr(), ffi.ptr(dvf),
@@ -636,7 +658,7 @@ class _KvProjectFn(torch.autograd.Function):
         b, N, q, dv = vf.shape
         kv_dim = weights[0].shape[0]
         desc = ffi.KvProjDesc(ffi.dtype_code(vf.dtype), len(weights), b * N * q, dv, kv_dim)
-        kvs = tuple(torch.empty((b, N * q, kv_dim), dtype=vf.dtype, device=vf.device) for _ in weights)
+        kvs = tuple(_new((b, N * q, kv_dim), vf.dtype, vf.device) for _ in weights)
         ws = _empty_bytes(lib.ff_kv_project_workspace_bytes(desc, 0), vf.device)
         ffi.check(lib.ff_kv_project_fwd(desc, vf.data_ptr(), ffi.ptr_array(weights), ffi.ptr_array(kvs), ws.data_ptr(), ws.numel(),
                                         ffi.stream_handle(vf.device)), "ff_kv_project_fwd")
@@ -651,9 +673,9 @@ class _KvProjectFn(torch.autograd.Function):
         vf, *weights = ctx.saved_tensors
         desc = ctx.desc
         b, N, q, _ = vf.shape
-        dkvs = [torch.zeros((b, N * q, desc.kv_dim), dtype=vf.dtype, device=vf.device) if g is None else g.contiguous() for g in dkvs]
+        dkvs = [_new_zeros((b, N * q, desc.kv_dim), vf.dtype, vf.device) if g is None else g.contiguous() for g in dkvs]
         flat, grads = _flat_grads(weights)
-        dvf = torch.empty_like(vf) if ctx.needs_input_grad[0] else None
+        dvf = _new_like(vf) if ctx.needs_input_grad[0] else None
         ws = _empty_bytes(lib.ff_kv_project_workspace_bytes(desc, 1 if dvf is not None else 0), vf.device)
         ffi.check(lib.ff_kv_project_bwd(desc, vf.data_ptr(), ffi.ptr_array(weights), ffi.ptr_array(dkvs), ffi.ptr_array(grads), ffi.ptr(dvf),
                                         ws.data_ptr(), ws.numel(), ffi.stream_handle(vf.device)), "ff_kv_project_bwd")
@@ -692,7 +714,7 @@ class _XattnBlockKvFn(torch.autograd.Function):
         dev = y.device
         saved = _empty_bytes(lib.ff_xattn_saved_bytes(desc), dev)
         scratch = _empty_bytes(lib.ff_xattn_scratch_bytes(desc), dev)
-        out = torch.empty_like(y)
+        out = _new_like(y)
         ffi.check(lib.ff_xattn_block_fwd(desc, y.data_ptr(), None, tt.data_ptr(), ffi.ptr_array(params), kv.data_ptr(),
                                          kv.data_ptr() + inner * kv.element_size(), out.data_ptr(), saved.data_ptr(), saved.numel(),
                                          scratch.data_ptr(), scratch.numel(), ffi.stream_handle(dev)), "ff_xattn_block_fwd(hoisted kv)")
@@ -713,7 +735,7 @@ class _XattnBlockKvFn(torch.autograd.Function):
         own = [p for i, p in enumerate(params) if i != _KV_PARAM]            # d to_kv.weight comes from _KvProjectFn
         flat, own_grads = _flat_grads(own)
         grads = own_grads[:_KV_PARAM] + [None] + own_grads[_KV_PARAM:]
-        dy, dkv = torch.empty_like(y), torch.empty_like(kv)
+        dy, dkv = _new_like(y), _new_like(kv)
         scratch = _empty_bytes(lib.ff_xattn_scratch_bytes(desc), dev)
         aligned = all(t.data_ptr() % 16 == 0 for t in (y, dout, params[2], params[7]))     # the deferred entry point requires it
         if _wgrad_queue.enabled and ctx.defer and aligned and all(p.grad is None for p in own) and not _wgrad_queue.seen_in_this_pass(own):
@@ -788,7 +810,7 @@ def xattn_block(y: torch.Tensor, visual_features: Optional[torch.Tensor], tt: to
     dev = y.device
     saved = _empty_bytes(lib.ff_xattn_saved_bytes(desc), dev)
     scratch = _empty_bytes(lib.ff_xattn_scratch_bytes(desc), dev)
-    out = torch.empty_like(y)
+    out = _new_like(y)
     with torch.no_grad():
         ffi.check(lib.ff_xattn_block_fwd(desc, y.data_ptr(), None, tt.data_ptr(), ffi.ptr_array([p.contiguous() for p in params]),
                                          k.data_ptr(), v.data_ptr(), out.data_ptr(), saved.data_ptr(), saved.numel(),
@@ -803,7 +825,7 @@ class _QuickGeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         x = x.contiguous()
-        y = torch.empty_like(x)
+        y = _new_like(x)
         ffi.check(ffi.lib().ff_quick_gelu_fwd(ffi.dtype_code(x.dtype), x.numel(), x.data_ptr(), y.data_ptr(), ffi.stream_handle(x.device)),
                   "ff_quick_gelu_fwd")
         ctx.save_for_backward(x)
@@ -813,7 +835,7 @@ class _QuickGeluFn(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         dy = dy.contiguous()
-        dx = torch.empty_like(x)
+        dx = _new_like(x)
         ffi.check(ffi.lib().ff_quick_gelu_bwd(ffi.dtype_code(x.dtype), x.numel(), x.data_ptr(), dy.data_ptr(), dx.data_ptr(),
                                               ffi.stream_handle(x.device)), "ff_quick_gelu_bwd")
         return dx
@@ -835,8 +857,8 @@ class _ShiftedCEFn(torch.autograd.Function):
         logits = logits.contiguous()
         labels = labels.contiguous().to(torch.int64)
         b, L, V = logits.shape
-        rows = torch.empty(b * (L - 1), dtype=torch.float32, device=logits.device)
-        lse = torch.empty_like(rows)
+        rows = _new(b * (L - 1), torch.float32, logits.device)
+        lse = _new_like(rows)
         ffi.check(lib.ff_shifted_ce_fwd(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ignore_index,
                                         rows.data_ptr(), lse.data_ptr(), ffi.stream_handle(logits.device)), "ff_shifted_ce_fwd")
         ctx.ignore_index = ignore_index
@@ -848,7 +870,7 @@ class _ShiftedCEFn(torch.autograd.Function):
         lib = ffi.lib()
         logits, labels, lse = ctx.saved_tensors
         b, L, V = logits.shape
-        dlogits = torch.empty_like(logits)
+        dlogits = _new_like(logits)
         g = grad_rows.contiguous().float()
         ffi.check(lib.ff_shifted_ce_bwd(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ctx.ignore_index,
                                         lse.data_ptr(), g.data_ptr(), dlogits.data_ptr(), ffi.stream_handle(logits.device)), "ff_shifted_ce_bwd")
@@ -879,8 +901,8 @@ def gemm(A, B, *, a_layout=0, b_layout=0, scale=1.0, act=None, act_bwd=None, aux
     ffi.require_cuda(A, B)
     M, K = (A.shape if a_layout == 0 else A.shape[::-1])
     N = B.shape[0] if b_layout == 0 else B.shape[1]
-    C_ = torch.empty((M, N), dtype=A.dtype, device=A.device)
-    aux_out = torch.empty_like(C_) if want_aux_out else None
+    C_ = _new((M, N), A.dtype, A.device)
+    aux_out = _new_like(C_) if want_aux_out else None
     d = ffi.GemmDesc(ffi.dtype_code(A.dtype), M, N, K, a_layout, b_layout, ffi.rowmap(A.stride(0)), ffi.rowmap(B.stride(0)),
                      ffi.rowmap(N), float(scale), ffi.ACTS.get(act, ffi.ACT_NONE), ffi.ACTS.get(act_bwd, ffi.ACT_NONE), split_k, tile, stages)
     ws = _empty_bytes(lib.ff_gemm_workspace_bytes(d), A.device)
@@ -892,9 +914,9 @@ def gemm(A, B, *, a_layout=0, b_layout=0, scale=1.0, act=None, act_bwd=None, aux
 def layernorm_fwd(x, gamma, beta, add=None, add_rows_per_seg=0, add_div=0, eps=1e-5):
     lib = ffi.lib()
     rows, cols = x.shape
-    y = torch.empty_like(x)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty_like(mean)
+    y = _new_like(x)
+    mean = _new(rows, torch.float32, x.device)
+    rstd = _new_like(mean)
     d = ffi.LnDesc(ffi.dtype_code(x.dtype), rows, cols, ffi.rowmap(cols), ffi.rowmap(cols), ffi.rowmap(cols), add_rows_per_seg, add_div, eps, 0)
     ffi.check(lib.ff_layernorm_fwd(d, x.data_ptr(), ffi.ptr(add), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
                                    rstd.data_ptr(), ffi.stream_handle(x.device)), "ff_layernorm_fwd")
@@ -904,8 +926,8 @@ def layernorm_fwd(x, gamma, beta, add=None, add_rows_per_seg=0, add_div=0, eps=1
 def layernorm_bwd(dy, x, gamma, mean, rstd, add=None, add_rows_per_seg=0, add_div=0, dx_residual=None, eps=1e-5):
     lib = ffi.lib()
     rows, cols = x.shape
-    dx = torch.empty_like(x)
-    dg, db = torch.empty_like(gamma), torch.empty_like(gamma)
+    dx = _new_like(x)
+    dg, db = _new_like(gamma), _new_like(gamma)
     d = ffi.LnDesc(ffi.dtype_code(x.dtype), rows, cols, ffi.rowmap(cols), ffi.rowmap(cols), ffi.rowmap(cols), add_rows_per_seg, add_div, eps, 1)
     ws = _empty_bytes(lib.ff_layernorm_bwd_workspace_bytes(d), x.device)
     ffi.check(lib.ff_layernorm_bwd(d, dy.data_ptr(), x.data_ptr(), ffi.ptr(add), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
@@ -917,7 +939,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, add=None, add_rows_per_seg=0, add_di
 def rows_reduce(x, rows_per_batch, rows_per_group):
     lib = ffi.lib()
     rows, cols = x.shape
-    out = torch.empty((rows_per_batch // rows_per_group, cols), dtype=x.dtype, device=x.device)
+    out = _new((rows_per_batch // rows_per_group, cols), x.dtype, x.device)
     d = ffi.ReduceDesc(ffi.dtype_code(x.dtype), rows, cols, ffi.rowmap(cols), rows_per_batch, rows_per_group)
     ws = _empty_bytes(lib.ff_rows_reduce_workspace_bytes(d), x.device)
     ffi.check(lib.ff_rows_reduce(d, x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), ffi.stream_handle(x.device)), "ff_rows_reduce")
@@ -927,7 +949,7 @@ def rows_reduce(x, rows_per_batch, rows_per_group):
 def gate_grad(a, b, alpha):
     lib = ffi.lib()
     rows, cols = a.shape
-    out = torch.empty_like(alpha)
+    out = _new_like(alpha)
     ws = _empty_bytes(lib.ff_gate_grad_workspace_bytes(rows, cols), a.device)
     ffi.check(lib.ff_gate_grad(ffi.dtype_code(a.dtype), rows, cols, a.data_ptr(), b.data_ptr(), alpha.data_ptr(), out.data_ptr(),
                                ws.data_ptr(), ws.numel(), ffi.stream_handle(a.device)), "ff_gate_grad")
@@ -949,8 +971,8 @@ def attention_fwd(q, k, v, tt=None, n_visual=0):
     lib = ffi.lib()
     mode = ffi.ATTN_DENSE if tt is None else ffi.ATTN_MEDIA
     d = _attn_desc(q, k, mode, n_visual, tt)
-    o = torch.empty_like(q)
-    lse = torch.empty((q.shape[0], q.shape[2], q.shape[1]), dtype=torch.float32, device=q.device)
+    o = _new_like(q)
+    lse = _new((q.shape[0], q.shape[2], q.shape[1]), torch.float32, q.device)
     d.q, d.k, d.v, d.o = _bnhd_strides(q), _bnhd_strides(k), _bnhd_strides(v), _bnhd_strides(o)
     ffi.check(lib.ff_attention_fwd(d, q.data_ptr(), k.data_ptr(), v.data_ptr(), ffi.ptr(tt), o.data_ptr(), lse.data_ptr(),
                                    ffi.stream_handle(q.device)), "ff_attention_fwd")
@@ -961,7 +983,7 @@ def attention_bwd(q, k, v, o, do, lse, tt=None, n_visual=0):
     lib = ffi.lib()
     mode = ffi.ATTN_DENSE if tt is None else ffi.ATTN_MEDIA
     d = _attn_desc(q, k, mode, n_visual, tt)
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    dq, dk, dv = _new_like(q), _new_like(k), _new_like(v)
     d.q, d.k, d.v, d.o = _bnhd_strides(q), _bnhd_strides(k), _bnhd_strides(v), _bnhd_strides(o)
     d.dq, d.dk, d.dv, d.dout = _bnhd_strides(dq), _bnhd_strides(dk), _bnhd_strides(dv), _bnhd_strides(do)
     ws = _empty_bytes(lib.ff_attention_bwd_workspace_bytes(d), q.device)

@@ -97,6 +97,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if hit is not None and hit[0] == key and all(b["param_ptrs"][0] == b["params"][0].data_ptr() for b in hit[1]):
             return hit[1]
         self._sync_host_steps()
+        from . import functional as _F
         table = {}
         for p in active:
             ffi.require_cuda(p, p.grad)
@@ -107,8 +108,8 @@ class FusedAdamW(torch.optim.Optimizer):
             sdt = self.state_dtype if (mixed and self.state_dtype is not None) else p.dtype
             if not st:
                 st["step"] = torch.zeros((), dtype=torch.float32)
-                st["exp_avg"] = torch.zeros_like(p, dtype=sdt, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, dtype=sdt, memory_format=torch.preserve_format)
+                st["exp_avg"] = _F._new_zeros_like(p, dtype=sdt)          # (p is contiguous: the same layout preserve_format gives)
+                st["exp_avg_sq"] = _F._new_zeros_like(p, dtype=sdt)
             if mixed and self.master_dtype is not None and "master" not in st:
                 st["master"] = p.detach().to(torch.float32)
             has_master = "master" in st

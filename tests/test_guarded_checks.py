@@ -1,0 +1,202 @@
+"""The checkers of tests/test_hip_bounds.py, checked themselves on the CPU: the guards (tests/guarded.py) catch writes past a buffer's end,
+into the padding between rows and unwritten elements; the row / element checks (tests/util.py) catch defects of a GEMM that the whole-tensor
+relative error `rel(...) < 8e-3` (the bf16 tolerance of the parity tests) lets through."""
+import numpy as np
+import pytest
+import torch
+
+from guarded import GuardViolation, Guards, guarded_allocations
+from util import gemm_bound_ok, gemm_ref, rel, rel_rows, rnd
+
+
+def _bf16(x):
+    return torch.as_tensor(np.asarray(x, np.float64)).to(torch.bfloat16)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.uint8, torch.int32])
+def test_untouched_guards_pass_and_bodies_are_poisoned(dtype):
+    g = Guards()
+    t = g.new((37, 5), dtype, "cpu")
+    z = g.new_zeros((3, 7), dtype, "cpu")
+    assert t.shape == (37, 5) and t.dtype == dtype and t.is_contiguous()
+    if dtype.is_floating_point:
+        assert torch.isnan(t).all()
+    else:
+        assert (t.view(torch.uint8) == 0xA5).all()
+    assert (z == 0).all()
+    raw, head = g.raw(t)
+    assert head % 4096 == 0 and t.data_ptr() - raw.data_ptr() == head   # the body keeps the allocator's alignment (the kernels' vector paths)
+    assert raw.numel() - head - t.numel() * t.element_size() >= 64 * 1024
+    t.fill_(1)
+    g.check()                                                      # writing the whole body is fine
+
+
+def test_guard_sentinel_is_finite_and_huge():
+    for dtype in (torch.float32, torch.bfloat16):
+        g = Guards()
+        t = g.new((4, 4), dtype, "cpu")
+        raw, head = g.raw(t)
+        s = raw[:head].view(dtype)
+        assert torch.isfinite(s).all() and (s.float().abs() > 1e37).all()
+        assert float((s[:8].float() * 0).abs().max()) == 0.0        # a zero weight discards it
+
+
+def test_write_one_element_past_the_end_is_caught():
+    g = Guards()
+    t = g.new((16, 24), torch.float32, "cpu")
+    t.fill_(0)
+    raw, head = g.raw(t)
+    raw[head + t.numel() * 4: head + t.numel() * 4 + 4].view(torch.float32).fill_(0.0)
+    with pytest.raises(GuardViolation, match=r"tail guard of \(16, 24\) float32 hit at body byte 1536"):
+        g.check()
+    (site, side, off, *_), = g.violations()
+    assert side == "tail" and off == 16 * 24 * 4 and "test_guarded_checks.py" in site
+
+
+def test_write_before_the_start_is_caught():
+    g = Guards()
+    t = g.new(100, torch.bfloat16, "cpu")
+    raw, head = g.raw(t)
+    raw[head - 2:head].fill_(0)
+    (site, side, off, *_), = g.violations()
+    assert side == "head" and off == -2
+
+
+def test_write_into_the_padding_between_rows_is_caught():
+    """An output with a row pitch larger than its width (RowMap.ld > cols): the padding columns belong to the caller and must survive bit
+    for bit - compared here against a snapshot, as tests/test_hip_bounds.py does for the GEMM's padded outputs."""
+    g = Guards()
+    rows, cols, ld = 8, 20, 32
+    buf = g.new((rows, ld), torch.bfloat16, "cpu")
+    buf.fill_(3.0)
+    before = buf.clone()
+    view = buf[:, :cols]
+    view.fill_(1.0)                                               # a correct kernel: only the cols of each row
+    assert torch.equal(buf[:, cols:].view(torch.int16), before[:, cols:].view(torch.int16))
+    buf[5, cols + 1] = 7.0                                        # a kernel that stored with pitch = cols and width = ld
+    assert not torch.equal(buf[:, cols:].view(torch.int16), before[:, cols:].view(torch.int16))
+    g.check()                                                     # (inside the allocation: only the padding snapshot sees it)
+
+
+def test_unwritten_tail_block_is_caught():
+    """A kernel that skips the last row tile leaves the poison: NaN reaches every comparison and rel_rows names the first untouched row."""
+    M, N = 300, 64
+    ref = rnd((M, N), 1).astype(np.float64)
+    g = Guards()
+    out = g.new((M, N), torch.float32, "cpu")
+    out[:256] = torch.from_numpy(ref[:256]).float()               # the last (ragged) 44-row tile never written
+    assert not (rel(out, ref) < 8e-3)                             # NaN fails every bound
+    worst, row = rel_rows(out, ref, (0,))
+    assert worst == np.inf and row == (256,)
+    g.check()                                                     # nothing outside the body was touched
+
+
+def test_guarded_allocations_swaps_and_restores_the_seam():
+    from flamingo_mini_amd import functional as F
+    before = {n: getattr(F, n) for n in ("_new", "_new_zeros", "_new_like", "_new_zeros_like")}
+    with guarded_allocations(device_types=("cpu",)) as g:
+        a = F._new((4, 8), torch.float32, "cpu")
+        b = F._empty_bytes(10, "cpu")
+        c = F._new_like(a.t())                                    # empty_like's layout: a transposed tensor stays transposed
+        d = F._new_zeros_like(a, dtype=torch.bfloat16)
+        assert torch.isnan(a).all() and (b == 0xA5).all() and c.stride() == (1, 8) and (d == 0).all() and d.dtype == torch.bfloat16
+        assert len(g.records) == 4
+        a.fill_(0)
+    assert {n: getattr(F, n) for n in before} == before
+    assert not g.records                                          # the registry does not survive the context
+    with pytest.raises(GuardViolation):
+        with guarded_allocations(device_types=("cpu",)):
+            t = F._new(64, torch.float32, "cpu")
+            t.untyped_storage()[t.numel() * 4] = 0                # one byte past the end (the storage is the guarded buffer)
+    assert {n: getattr(F, n) for n in before} == before
+    with guarded_allocations():                                   # CUDA only by default: CPU allocations pass through unguarded
+        assert not torch.isnan(F._new_zeros((2,), torch.float32, "cpu")).any()
+
+
+def test_the_seam_without_guards_allocates_as_before():
+    from flamingo_mini_amd import functional as F
+    t = torch.empty(3, 5).t()
+    for new, plain in ((F._new_like(t), torch.empty_like(t)), (F._new_zeros_like(t, dtype=torch.bfloat16), torch.zeros_like(t, dtype=torch.bfloat16))):
+        assert new.shape == plain.shape and new.stride() == plain.stride() and new.dtype == plain.dtype
+    assert F._new_zeros((2, 3), torch.int32, "cpu").equal(torch.zeros(2, 3, dtype=torch.int32))
+    assert F._empty_bytes(3, "cpu").numel() == 16
+
+
+# ---- the row / element checks against defects injected into a float64 GEMM reference ----------------------------------------------------
+M, N, K = 408, 424, 328          # tests/test_hip_primitives.py::test_gemm_every_instantiated_tile: partial tiles in M and N, a K tail of 8
+
+
+@pytest.fixture(scope="module")
+def gemm_case():
+    A, B = _bf16(rnd((M, K), 11)), _bf16(rnd((N, K), 12))
+    acc, _ = gemm_ref(A, B)
+    good = _bf16(acc)                                             # a correct bf16 kernel: the exact product, rounded once
+    return A, B, acc, good
+
+
+def test_a_correct_product_passes_every_check(gemm_case):
+    A, B, acc, good = gemm_case
+    assert rel(good, acc) < 8e-3
+    assert rel_rows(good, acc, (0,))[0] < 4e-3
+    ok, worst, _ = gemm_bound_ok(good, A, B)
+    assert ok, worst
+
+
+def test_one_tile_missing_its_k_tail(gemm_case):
+    """The corner 128 x 128 tile (24 x 40 elements of it are inside the problem) drops the last 8 of 328 k-steps."""
+    A, B, acc, _ = gemm_case
+    a, b = A.double().numpy(), B.double().numpy()
+    bad = acc.copy()
+    bad[384:, 384:] = a[384:, :320] @ b[384:, :320].T
+    bad = _bf16(bad)
+    r = rel(bad, acc)
+    assert 5e-3 < r < 2e-2                                        # about the bound of the test above (1e-2): whether it is caught is luck
+    assert rel_rows(bad, acc, (0,))[0] > 0.03                     # each of those 24 rows: 40 of 424 elements off by ~16 %
+    ok, worst, idx = gemm_bound_ok(bad, A, B)
+    assert not ok and worst > 20 and idx[0] >= 384 and idx[1] >= 384
+
+
+def test_last_eight_columns_of_one_row_wrong(gemm_case):
+    A, B, acc, good = gemm_case
+    bad = good.clone()
+    bad[200, -8:] = _bf16(1.2 * acc[200, -8:])                    # a 20 % error in one row's last column group
+    assert rel(bad, acc) < 8e-3                                   # rel() does NOT see it
+    worst, row = rel_rows(bad, acc, (0,))
+    assert row == (200,) and worst > 2e-2                         # several times a bf16 row's rounding error
+    ok, worst, idx = gemm_bound_ok(bad, A, B)
+    assert not ok and idx[0] == 200 and idx[1] >= N - 8
+
+
+def test_one_row_tile_left_stale(gemm_case):
+    """A plan that skips the last row tile.  In a plain `torch.empty` output the caching allocator hands back the previous call's block,
+    which (same shape, the loop of test_gemm_every_instantiated_tile) already holds the right product: no value check can tell.  Under the
+    guards' poison the stale rows are NaN, and both checks name them."""
+    A, B, acc, good = gemm_case
+    reused = good.clone()                                         # the previous call's C, handed back by the allocator
+    reused[384:] = good[384:]                                     # "left stale" = unchanged
+    assert rel(reused, acc) < 8e-3                                # nothing to see without the poison
+    g = Guards()
+    out = g.new((M, N), torch.bfloat16, "cpu")
+    out[:384] = good[:384]
+    assert not (rel(out, acc) < 8e-3)
+    worst, row = rel_rows(out, acc, (0,))
+    assert worst == np.inf and row == (384,)
+    ok, _, idx = gemm_bound_ok(out, A, B)
+    assert not ok and idx[0] >= 384
+
+
+def test_rel_rows_exact_zero_rows_and_small_rows():
+    ref = rnd((6, 5, 16), 3).astype(np.float64)
+    ref[2, 3] = 0.0                                               # e.g. a masked-query attention row
+    ref[4, 1] *= 1e-9                                             # a tiny row: compared absolutely, not relatively
+    got = ref.copy()
+    got[4, 1] += 1e-9
+    worst, _ = rel_rows(got, ref, (0, 1))
+    assert worst < 1e-6
+    got[2, 3, 7] = 1e-30                                          # any value in an exactly-zero row
+    assert rel_rows(got, ref, (0, 1)) == (np.inf, (2, 3))
+    att = np.moveaxis(ref.reshape(6, 5, 4, 4), 0, 0)              # (b, nq, h, d) with rows (b, h, q)
+    got = att.copy()
+    got[1, 2, 3, 0] *= 1.5
+    worst, row = rel_rows(got, att, (0, 2, 1))
+    assert row == (1, 3, 2) and worst > 0.01

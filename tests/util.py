@@ -87,3 +87,77 @@ def hog_stream():
     waits behind the hog in that queue.  High-priority streams draw from a pool of their own, apart from the normal-priority queues the
     test's launches go to."""
     return torch.cuda.Stream(priority=-1)
+
+
+# ---- row-level and element-level checks (tests/test_hip_bounds.py; the checkers' own tests: tests/test_guarded_checks.py) ----
+# rel() above is ONE number over a whole tensor: an error confined to a few rows or one tile is diluted by everything else.  These two
+# look at the worst row / the worst element instead.
+def _np64(a):
+    return np.asarray(a.detach().double().cpu().numpy() if torch.is_tensor(a) else a, np.float64)
+
+
+def _report(tag, v):
+    if os.environ.get("FF_TOL_REPORT"):      # the same report as rel(), the test id tagged [rows] / [elem]
+        with open(os.environ["FF_TOL_REPORT"], "a") as f:
+            f.write(f"{os.environ.get('PYTEST_CURRENT_TEST', '?').split(' ')[0]}[{tag}]\t{v:.3e}\n")
+
+
+def rel_rows(got, ref, row_axes, floor=1e-2):
+    """(worst row's relative L2 error, that row's index) - a row is the set of elements that share the indices on `row_axes`, e.g. (0, 1)
+    = (sample, token) of a (b, n, d) block output, (0, 2, 1) = (b, h, q) of a (b, nq, h, d) attention output.
+    Rows whose reference norm is below `floor` x the median row norm are compared absolutely (their error is divided by that floor
+    instead of by their own norm).  Rows the reference holds as exactly zero must be exactly zero: any other value gives inf.  A NaN in
+    `got` (an element a kernel never wrote, under tests/guarded.py's poison) gives inf for its row."""
+    g, r = _np64(got), _np64(ref)
+    assert g.shape == r.shape, (g.shape, r.shape)
+    row_axes = tuple(a % r.ndim for a in (row_axes if isinstance(row_axes, (tuple, list)) else (row_axes,)))
+    rest = tuple(a for a in range(r.ndim) if a not in row_axes)
+    rows_shape = tuple(r.shape[a] for a in row_axes)
+    g2 = np.transpose(g, row_axes + rest).reshape(int(np.prod(rows_shape)), -1)
+    r2 = np.transpose(r, row_axes + rest).reshape(int(np.prod(rows_shape)), -1)
+    rn = np.linalg.norm(r2, axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        en = np.linalg.norm(g2 - r2, axis=1)
+    nz = rn[rn > 0]
+    den = np.maximum(rn, floor * (float(np.median(nz)) if nz.size else 1.0))
+    err = en / den
+    zero_rows = ~np.any(r2 != 0, axis=1)
+    err[zero_rows] = np.where(np.any(g2[zero_rows] != 0, axis=1), np.inf, 0.0)
+    err[~np.isfinite(err)] = np.inf
+    i = int(np.argmax(err))
+    worst = float(err[i])
+    _report("rows", worst)
+    return worst, tuple(int(x) for x in np.unravel_index(i, rows_shape))
+
+
+def gemm_ref(A, B, a_layout=0, b_layout=0, scale=1.0):
+    """(scale . op(A) op(B), |scale| . |op(A)| |op(B)|) in float64 from what the kernel saw - the product and the size of its terms."""
+    a, b = _np64(A), _np64(B)
+    a = a if a_layout == 0 else a.T
+    b = b.T if b_layout == 0 else b
+    return scale * (a @ b), abs(scale) * (np.abs(a) @ np.abs(b))
+
+
+def gemm_bound_ok(C, A, B, a_layout=0, b_layout=0, scale=1.0, epilogue=None, u_out=None, u_mid=0.0, c=2.0):
+    """Element-wise bound for a bf16 / fp32 GEMM with fp32 accumulation:
+            |C - f(C*)| <= u_out |f(C*)| + |f'(C*)| (c K 2^-24 (|A| |B|) + u_mid |C*|)
+    C* = scale op(A) op(B) in float64, f the epilogue: `epilogue(acc) -> (f(acc), |f'(acc)|)` (None: identity).  u_out is the output's
+    rounding (default 2^-7 for bf16: one ulp at the bottom of a binade, twice the round-to-nearest worst case - measured on an MI355X,
+    tests/test_hip_bounds.py: <= 0.96 of the bound at 2^-8, so <= 0.48 at 2^-7; 2^-22 for fp32); c K 2^-24 |A||B| the worst-case error of a K-term fp32 sum (c = 2:
+    a split-K combine on top); u_mid the rounding of an intermediate the epilogue starts from (0: the epilogue sees the fp32 accumulator).
+    A single dropped k-step, or one wrong element in any one tile, exceeds it by orders of magnitude.
+    Returns (ok, worst error / bound, index of that element)."""
+    got = _np64(C)
+    acc, absprod = gemm_ref(A, B, a_layout, b_layout, scale)
+    K = (A.shape[1] if a_layout == 0 else A.shape[0])
+    ref, deriv = (acc, np.ones_like(acc)) if epilogue is None else epilogue(acc)
+    if u_out is None:
+        u_out = 2.0 ** -7 if C.dtype == torch.bfloat16 else 2.0 ** -22
+    bound = u_out * np.abs(ref) + np.abs(deriv) * (c * K * 2.0 ** -24 * absprod + u_mid * np.abs(acc)) + 1e-30
+    with np.errstate(invalid="ignore", over="ignore"):
+        ratio = np.abs(got - ref) / bound
+    ratio[~np.isfinite(ratio)] = np.inf
+    i = int(np.argmax(ratio))
+    worst = float(ratio.reshape(-1)[i])
+    _report("elem", worst)
+    return worst <= 1.0, worst, tuple(int(x) for x in np.unravel_index(i, ratio.shape))
