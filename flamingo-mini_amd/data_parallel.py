@@ -269,7 +269,8 @@ class GradientAllReducer:
             self._mean_in_place(p.grad)
         if self.active and self._sync and self._collect is None:
             # fused parameters whose gradient did not arrive as a bucket of this model (torch.autocast over fp32 parameters: the fused modules ran
-            # on CASTS of them, whose buckets are not ours; the gradients reached the parameters through the casts' backward): exchanged here
+            # on CASTS of them, whose buckets are not ours; the gradients reached the parameters through the casts' backward): exchanged here.
+            # (graphs.PiecewiseGraphedTrainStep hands them over as buckets of their own, earlier in the step: they are in _early then.)
             for p in self._fused_params:
                 if p.grad is not None and id(p) not in self._early and id(p) not in seen:
                     self._mean_in_place(p.grad)
@@ -323,6 +324,7 @@ class ShardedAdamW(torch.optim.Optimizer):
         self._work: List = []
         self._late: List = []        # buckets whose gradients are being accumulated: their pipeline runs in step()
         self._updated = set()        # buckets already updated in the running step
+        self._arrived = set()        # ids of the parameters whose bucket arrived in the running step (updated now or in step())
         self._sync = True
         self._loaded = None          # a state_dict loaded before the buckets exist: applied as they are created
         self._dev_scalars = {}       # capturable: device -> (step counter, learning rate)
@@ -459,6 +461,7 @@ class ShardedAdamW(torch.optim.Optimizer):
                                "wrap all but the last micro-batch in ShardedAdamW.no_sync()")
         if not self._sync:
             return                               # autograd accumulates into .grad; nothing is exchanged or updated
+        self._arrived.update(key)
         if accumulating:                         # the gradient of this step is .grad AFTER autograd has added `flat` to it: see step()
             if st not in self._late:
                 self._late.append(st)
@@ -494,10 +497,13 @@ class ShardedAdamW(torch.optim.Optimizer):
         for ev in self._work:
             torch.cuda.current_stream().wait_event(ev)
         self._work.clear()
-        covered = {id(p) for st in self.buckets.values() for p in st["params"]}
+        # Checked against the buckets of THIS step, not against every bucket ever seen: a step without autocast before this one has created
+        # the buckets of all fused parameters, and an autocast step after it still delivers none of them.
+        covered = self._arrived | {id(p) for st in self._late for p in st["params"]}
+        self._arrived = set()
         stray = [self._names.get(id(p), "?") for p in self._model.parameters()
                  if p.requires_grad and p.grad is not None and id(p) in self._fused_ids and id(p) not in covered]
-        if stray:       # (torch.autocast over fp32 parameters: the fused modules ran on casts, no bucket of THIS model ever arrived)
+        if stray:       # (torch.autocast over fp32 parameters: the fused modules ran on casts, no bucket of THIS model arrived in this step)
             raise RuntimeError(f"ShardedAdamW: {len(stray)} fused parameter(s) (e.g. {stray[0]}) have a gradient that did not arrive as a gradient bucket "
                                "of their module - under torch.autocast the fused modules run on casts of fp32 parameters. Use bf16 parameters with "
                                "master_dtype=torch.float32 here, or GradientAllReducer + FusedAdamW under autocast.")

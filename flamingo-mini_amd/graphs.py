@@ -319,6 +319,7 @@ class PiecewiseGraphedTrainStep:
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
         self.graphs = []
         self.segment_buckets = []
+        self.cast_buckets = []         # (segment, parameter): gradients of fused parameters that arrived as no bucket (autocast; see _capture)
         self.host_timing: Optional[dict] = None
         if not self.capture:
             self.loss = None
@@ -414,6 +415,16 @@ class PiecewiseGraphedTrainStep:
                     if seen.get(id(p)) != mark:
                         seen[id(p)] = mark
                         last_touched[id(p)] = k
+        if reducer is not None:
+            # torch.autocast over fp32 parameters: the fused modules ran on casts, whose buckets are not the reducer's, and the gradients reached
+            # the fp32 parameters through the casts' backward.  Each such gradient becomes a bucket of its own in the segment after which it is
+            # final: exchanged before that segment's optimizer piece (overlap_optimizer), and marked early, so finish() leaves it alone instead
+            # of all-reducing it again after the update.  Without autocast every fused parameter is owned by a recorded bucket: nothing is added.
+            owned = {id(p) for buckets in self.segment_buckets for _, owners in buckets for p, _, _ in owners}
+            for p in getattr(reducer, "_fused_params", ()):
+                if p.grad is not None and id(p) not in owned and id(p) in last_touched:
+                    self.segment_buckets[last_touched[id(p)]].append((p.grad, [(p, 0, p.numel())]))
+                    self.cast_buckets.append((last_touched[id(p)], p))
         if reducer is not None:        # an un-fused parameter (the tied token embedding) takes part in two segments: exchange it after the last one
             seen = set()
             for buckets in reversed(self.segment_buckets):

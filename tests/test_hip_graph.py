@@ -216,27 +216,71 @@ def test_sharded_adamw_on_one_rccl_rank_equals_fused_adamw(one_rank_rccl, master
         assert rel(pb, pa) < 1e-2, n
 
 
+class _ToyLoose(_Toy):
+    """_Toy plus one un-fused trainable parameter (the token embedding's role)."""
+
+    def __init__(self):
+        super().__init__()
+        self.loose = torch.nn.Parameter(torch.ones(64))
+
+    def forward(self, x_f, y, media_locations):
+        return super().forward(x_f, y * self.loose, media_locations)
+
+
 def test_sharded_adamw_refuses_autocast_over_fp32_parameters(one_rank_rccl):
     """Under torch.autocast the fused modules run on casts of their fp32 parameters, so no gradient bucket of THIS model ever reaches
     ShardedAdamW - whose update is per bucket.  It must say so instead of silently not updating those parameters."""
     from flamingo_mini_amd.data_parallel import ShardedAdamW
     torch.manual_seed(0)
-
-    class ToyLoose(_Toy):                   # ... plus one un-fused trainable parameter (the token embedding's role)
-        def __init__(self):
-            super().__init__()
-            self.loose = torch.nn.Parameter(torch.ones(64))
-
-        def forward(self, x_f, y, media_locations):
-            return super().forward(x_f, y * self.loose, media_locations)
-
-    model = ToyLoose().cuda()
+    model = _ToyLoose().cuda()
     ml = torch.zeros(2, 16, dtype=torch.int64, device="cuda"); ml[:, 0] = 1
     batch = dict(x_f=dev(rnd((2, 1, 24, 64), 70)), y=dev(rnd((2, 16, 64), 71)), media_locations=ml)
     opt = ShardedAdamW(model, lr=1e-2, force_collectives=True)
     try:
         with torch.autocast("cuda", dtype=torch.bfloat16):
             loss = model(**batch)
+        loss.backward()
+        with pytest.raises(RuntimeError, match="did not arrive as a gradient bucket"):
+            opt.finish_step()
+        torch.cuda.synchronize()
+    finally:
+        opt.close()
+
+
+def test_sharded_adamw_refuses_autocast_after_ordinary_steps(one_rank_rccl):
+    """The refusal above looks at the buckets of the RUNNING step.  Ordinary steps (fp32 parameters, no autocast) create a bucket for every fused
+    parameter and must train exactly like FusedAdamW - plain steps and a step accumulated over two micro-batches under no_sync() - without a
+    false alarm; an autocast step after them still delivers no bucket of this model, and finish_step() must refuse it instead of quietly
+    skipping the update of the fused parameters."""
+    from flamingo_mini_amd import FusedAdamW
+    from flamingo_mini_amd.data_parallel import ShardedAdamW
+    torch.manual_seed(0)
+    model = _ToyLoose().cuda()
+    plain = copy.deepcopy(model)
+    ml = torch.zeros(2, 16, dtype=torch.int64, device="cuda"); ml[:, 0] = 1
+    batches = [dict(x_f=dev(rnd((2, 1, 24, 64), 80 + i)), y=dev(rnd((2, 16, 64), 90 + i)), media_locations=ml) for i in range(5)]
+    hp = dict(lr=1e-2, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.05)
+    opt_p = FusedAdamW(plain.parameters(), **hp)
+    opt = ShardedAdamW(model, force_collectives=True, **hp)
+    try:
+        for micro in ([batches[0]], [batches[1]], [batches[2], batches[3]]):         # two plain steps, then one accumulated step
+            plain.zero_grad(set_to_none=True)
+            for b in micro:
+                (plain(**b) / len(micro)).backward()
+            opt_p.step()
+            opt.zero_grad()
+            for b in micro[:-1]:
+                with opt.no_sync():
+                    (model(**b) / len(micro)).backward()
+            (model(**micro[-1]) / len(micro)).backward()
+            opt.finish_step()
+        torch.cuda.synchronize()
+        assert len(opt.buckets) >= 2 and opt.step_count == 3
+        for (n, pa), (_, pb) in zip(plain.named_parameters(), model.named_parameters()):
+            assert rel(pb, pa) < 1e-4, n                              # every parameter updated as FusedAdamW updates it
+        opt.zero_grad()
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            loss = model(**batches[4])
         loss.backward()
         with pytest.raises(RuntimeError, match="did not arrive as a gradient bucket"):
             opt.finish_step()
@@ -302,6 +346,9 @@ def test_piecewise_graphs_with_eager_collectives_equal_eager_and_full_capture(on
                 assert sum(g is not None for g in step._opt_pieces) >= 3 and step._opt_graph is None
             if name.startswith("piecewise"):
                 assert len(step.graphs) == 1 + 3 and sum(len(b) for b in step.segment_buckets) >= 4      # forward + 3 backward segments; blocks, to_kv, resampler, embedding
+                # without autocast every fused parameter's gradient is a slice of a recorded bucket: no bucket of its own is added (the
+                # benchmark's path is the one it was before those buckets existed)
+                assert step.cast_buckets == [], [(k, n) for k, q in step.cast_buckets for n, x in model.named_parameters() if x is q]
             out = [None] + [float(step()) for _ in range(n_steps - 1)]
         torch.cuda.synchronize()
         reducer.close()
