@@ -387,13 +387,19 @@ int decode_ffw(int M, int d, int ffi, int act, float eps, const void* y1, const 
     up.A = (const bf16*)y1; up.B = (const bf16*)W1; up.gamma = (const bf16*)gamma; up.beta = (const bf16*)beta;
     up.C = (bf16*)Aact; up.aux_out = (bf16*)Hpre; up.xn_out = (bf16*)xn; up.mean = mean; up.rstd = rstd;
     if (ks > 1) { up.zero_tickets = tickets; up.n_zero = cdiv(d, nb_down); }
-    FF_TRY(launch_decode(up, st));
+    int pid = profile_begin(FF_DTYPE_BF16, -10, 0, 0, M, ffi, d, 1, 1, st);
+    int rc = launch_decode(up, st);
+    profile_end(pid, st);
+    FF_TRY(rc);
     DecodeArgs dn = {};
     dn.M = M; dn.N = d; dn.kslice = ffi / ks; dn.kslices = ks; dn.nb = nb_down; dn.ln = 0; dn.act = FF_ACT_NONE; dn.eps = 0.f; dn.scale = 1.f;
     dn.lda = ffi; dn.ldb = ffi; dn.ldc = d; dn.ldr = d;
     dn.A = (const bf16*)Aact; dn.B = (const bf16*)W3; dn.C = (bf16*)y_out; dn.aux_out = (bf16*)ffw_out; dn.residual = (const bf16*)y1;
     dn.gate = (const bf16*)alpha; dn.partial = partial; dn.tickets = tickets;
-    return launch_decode(dn, st);
+    pid = profile_begin(FF_DTYPE_BF16, -11, 0, 0, M, d, ffi, 1, ks, st);
+    rc = launch_decode(dn, st);
+    profile_end(pid, st);
+    return rc;
 }
 
 }  // namespace ff

@@ -1604,9 +1604,10 @@ int xa_qattn_fwd(const XaFusedArgs& a, int dtype, int dim_head, const void* y, c
              "xa_qattn_fwd: phase 2 (to_out inside the launch) asked for a problem that does not take it, or with a null argument");
     FF_CHECK(!out || !out->ln_out || (out->ln_g && out->ln_b && out->ln_mean && out->ln_rstd && out->ln_part), FF_ERR_SHAPE,
              "xa_qattn_fwd: phase 3 (LayerNorm of the feed-forward inside the launch) with a null argument");
-    const int pid = profile_begin(dtype, out ? (out->ln_out ? -8 : -6) : -4, a.heads, 0, a.n_q, a.n_kv, a.dim, a.batch * a.heads, dim_head, st);
-    int rc;
     const int nsb = res_ring_depth(a, dtype, dim_head, false);
+    // (b_layout of the record: the resident kernel's ring depth, 0 = the general kernel)
+    const int pid = profile_begin(dtype, out ? (out->ln_out ? -8 : -6) : -4, a.heads, nsb, a.n_q, a.n_kv, a.dim, a.batch * a.heads, dim_head, st);
+    int rc;
     const XaOutArgs none = {};
     if (nsb == 6 && out) rc = launch_fwd_res<6, true>(a, y, gamma, beta, Wq, K, V, tt, yn, Qs, O, mean, rstd, lse, *out, st);
     else if (nsb == 4 && out) rc = launch_fwd_res<4, true>(a, y, gamma, beta, Wq, K, V, tt, yn, Qs, O, mean, rstd, lse, *out, st);

@@ -23,6 +23,7 @@ from . import functional as F
 from .backbones import load_language_model, load_vision_encoder
 from .configuration_flamingo import FlamingoConfig
 from .gated_cross_attention import ModifiedLMBlock
+from .graphs import _prepared_capture_stream
 from .perceiver_resampler import PerceiverResampler
 from .utils import get_common_prefix_length
 
@@ -406,9 +407,12 @@ class _DecodeSession:
             self._step()                                                      # eager once: lazy initialisation, allocator pools
             remaining -= 1
             try:
+                # captured on a stream whose sync buffer exists before the capture: an unprepared capture would keep the separate to_out
+                # launches where the eager steps exchange inside the fused launch (> 32 rows) - replay and eager steps must be the same work
+                self.capture_stream = _prepared_capture_stream(self.model)
                 g = torch.cuda.CUDAGraph()
                 torch.cuda.synchronize()
-                with torch.cuda.graph(g):
+                with torch.cuda.graph(g, stream=self.capture_stream):
                     self._step()
                 self.graph, self.replay = g, g.replay
             except Exception:                                                 # the steps run eagerly from here on (and in later calls)

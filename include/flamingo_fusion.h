@@ -100,7 +100,10 @@ int ff_gemm(const ff_gemm_desc* d, const void* A, const void* B, void* C, void* 
 /* Optional measurement aid (bench.py's roofline leg): while enabled, every GEMM main-kernel launch is bracketed by two
  * HIP events on its own stream.  ff_gemm_profile_read() waits for the recorded launches, fills `out` (returns the count)
  * and clears the log.  ff_gemm_profile_enable(0) switches it off.  Recording is thread-safe (launches of any thread on any stream claim
- * their slot atomically); enable / read / disable belong to ONE controlling thread, called while no launch is in flight. */
+ * their slot atomically); enable / read / disable belong to ONE controlling thread, called while no launch is in flight.
+ * `tile` < 0 marks the non-GEMM launches: -1 / -2 / -3 attention core (forward, dQ, dK / dV); -4 / -6 / -8 the fused cross-attention
+ * forward (b_layout = the resident kernel's ring depth, 0 = the general kernel) and -5 / -7 / -9 its backward; -10 / -11 the decode
+ * feed-forward for <= 32 rows (LayerNorm + up-projection; down-projection + gate + residual, split_k = K slices combined in the launch). */
 typedef struct ff_gemm_profile_record {
     int dtype, tile, a_layout, b_layout;
     int M, N, K, nz, split_k;
