@@ -17,14 +17,17 @@ The step (forward + backward + gradient exchange + optimizer) is captured once i
 between the replays - the path that does not depend on collectives being capturable).
 The headline `value` is the north star's configuration: the frozen CLIP / GPT-2 stay UNTOUCHED Hugging Face modules on stock
 PyTorch-ROCm with hipBLASLt's default heuristic.  `--backbone-tweaks on` enables three result-identical op substitutions inside them
-plus the pre-tuned hipBLASLt solution file for their GEMMs (flamingo-mini_amd/tuning/); the default run reports that configuration too,
-as the companion `with_backbone_op_substitutions`.
+plus the pre-tuned hipBLASLt solution file for their GEMMs (flamingo-mini_amd/tuning/); a `--full` run of config B reports that
+configuration too, as the companion `with_backbone_op_substitutions` (and `fp32_master_optimizer`).
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live: right after the timed region `--profile-steps` eager steps of
-the same workload run with every GEMM / attention launch of the fusion library bracketed by HIP events on its stream
-(ff_gemm_profile_*; events cannot be recorded inside a replayed graph); the dominant GEMM variant is reported against
-the dense bf16 MFMA peak.  `cpu_baseline` times the all-core torch CPU restatement (oracle/torch_port.py) of the same hot path on
-this box's host cores (and config A end to end).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the line (`roofline`
+null).  `--full` adds, after the timed region, everything else the benchmark measures:
+    python bench.py --full
+`roofline` is measured live: right after the timed region `--profile-steps` eager steps of the same workload run with every GEMM /
+attention launch of the fusion library bracketed by HIP events on its stream (ff_gemm_profile_*; events cannot be recorded inside a
+replayed graph); the dominant GEMM variant is reported against the dense bf16 MFMA peak.  `caption` times cached greedy decoding,
+`cpu_baseline` the all-core torch CPU restatement (oracle/torch_port.py) of the same hot path on this box's host cores (and config A
+end to end); config B adds the two companion runs, N > 1 the `bucket_timeline`, a piecewise replay its host time per step.
 """
 from __future__ import annotations
 
@@ -81,9 +84,13 @@ def parse():
                          "update of this rank's 1/N slice -> all-gather per gradient bucket, replaces the gradient all-reduce); torch = torch.optim.AdamW(fused=True)")
     ap.add_argument("--reduce-dtype", default="native", choices=["native", "f32"],
                     help="N > 1 with the all-reduce path: exchange gradient buckets in their own dtype (bf16, ReduceOp.AVG) or widened to fp32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run what else the benchmark measures: the instrumented eager steps (roofline), caption "
+                         "decoding, the CPU baseline, the companion runs (config B), the bucket timeline (N > 1) and the piecewise host timing.  Without it "
+                         "the run sets up, warms up, times the steps, writes --dump-outputs and prints the line; the flags below still ask for one of them")
     ap.add_argument("--companions", default="auto", choices=["auto", "on", "off"],
                     help="N=1 only: after the main measurement, re-run the same workload in child processes (a) with the op substitutions inside the "
-                         "backbones + the tuning file, (b) with the fp32-master / fp32-moment optimizer, and add both to the JSON line (auto = on for the default config B run)")
+                         "backbones + the tuning file, (b) with the fp32-master / fp32-moment optimizer, and add both to the JSON line (auto = on for the default config B run with --full)")
     ap.add_argument("--segment-arena", default="on", choices=["on", "off"],
                     help="piecewise replay with a reducer: the gradient buckets of a backward segment live in one buffer and travel as ONE collective (11 per step instead of 47)")
     ap.add_argument("--overlap-optimizer", default="auto", choices=["auto", "on", "off"],
@@ -99,7 +106,8 @@ def parse():
                          "eager launches at N > 1 (every rank takes the first mode that ALL ranks can capture)")
     ap.add_argument("--force-collectives", action="store_true", help="N=1: run the gradient exchange through a 1-rank RCCL group (what a single GPU can exercise of the N > 1 path)")
     ap.add_argument("--bucket-timeline", action="store_true", help="after the timed region, one eager step with HIP events around every gradient "
-                                                                   "bucket's exchange: when it became ready, when its collective finished (rank 0, `bucket_timeline` in the JSON line)")
+                                                                   "bucket's exchange: when it became ready, when its collective finished (rank 0, `bucket_timeline` in the JSON line; "
+                                                                   "on by default at N > 1 with --full)")
     ap.add_argument("--segment-layers", type=int, default=4,
                     help="piecewise replay: gated layers per backward segment (= per exchange point; with --wgrad-group / --kv-group set to the same number the "
                          "launch structure follows it)")
@@ -112,7 +120,8 @@ def parse():
                     help="off: the gated blocks keep to_out (+ gate + residual) and d LN(y) as launches of their own instead of running them inside the fused "
                          "attention launches through the in-launch exchange (ff_xattn_desc.sync; A/B timing)")
     ap.add_argument("--lm-dropout", type=float, default=None, help="debugging aid: dropout probability inside the stock LM (default: the architecture's)")
-    ap.add_argument("--profile-steps", type=int, default=3, help="instrumented eager steps after the timed region (roofline objects)")
+    ap.add_argument("--profile-steps", type=int, default=None, help="instrumented eager steps after the timed region (roofline objects; default 3 with "
+                                                                    "--full or --gemm-table, else 0)")
     ap.add_argument("--stock-tuning", default="auto", choices=["auto", "on", "off"],
                     help="load the pre-tuned hipBLASLt solution file for the stock CLIP / GPT-2 GEMMs (PyTorch TunableOp, tuning off); auto = with --backbone-tweaks on")
     ap.add_argument("--backbone-tweaks", default="off", choices=["on", "off"],
@@ -121,7 +130,7 @@ def parse():
     ap.add_argument("--debug-phases", action="store_true", help="print host-side issue time of each phase of 5 eager steps and exit")
     ap.add_argument("--hoist-kv", default="on", choices=["on", "off"],
                     help="project K / V of all cross-attention layers up front in grouped launches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (a plain run has none)")
     ap.add_argument("--rccl-channels", type=int, default=0,
                     help="N > 1: cap RCCL's channels (NCCL_MAX_NCHANNELS; one workgroup per channel on the side stream).  0 = RCCL's choice.  The step's exchange "
                          "(1.37 GB per rank) needs ~8 ms of a ~25 ms backward at full xGMI speed, while every CU a collective occupies turns a 256-tile "
@@ -129,7 +138,8 @@ def parse():
     ap.add_argument("--shared-gpu-rehearsal", action="store_true",
                     help="N > 1 ranks on a box with one GPU: all ranks on device 0, gloo instead of RCCL - a rehearsal of the multi-rank launch contract, not a measurement")
     ap.add_argument("--child", action="store_true", help="internal: a companion run started by the main process (timed region only)")
-    ap.add_argument("--caption-tokens", type=int, default=32, help="N=1 only: also time cached greedy decoding of this many tokens per image (0 = skip)")
+    ap.add_argument("--caption-tokens", type=int, default=None, help="N=1 only: also time cached greedy decoding of this many tokens per image (0 = skip; "
+                                                                     "default 32 with --full, else 0)")
     ap.add_argument("--gemm-table", default="", help="write the per-shape GEMM timing table (measured inside the timed steps) to this file")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
@@ -138,6 +148,10 @@ def parse():
         ap.error("--steps must be >= 1")
     if args.stock_tuning == "auto":
         args.stock_tuning = args.backbone_tweaks
+    if args.profile_steps is None:
+        args.profile_steps = 3 if (args.full or args.gemm_table) else 0
+    if args.caption_tokens is None:
+        args.caption_tokens = 32 if args.full else 0
     if args.child:
         args.no_cpu_baseline, args.caption_tokens, args.profile_steps, args.companions = True, 0, 0, "off"
     for k, v in CONFIGS[args.config].items():
@@ -740,7 +754,7 @@ def main():
     from flamingo_mini_amd import functional as _Fs
     sync_timeouts = int(_Fs.sync_exchange_status()) if getattr(_Fs, "_sync_buffers", None) else 0
     piecewise_host = None
-    if graph_mode == "piecewise" and hasattr(step, "host_timing"):      # host seconds by kind of call over 5 more steps (launch-bound or not, and by what)
+    if args.full and graph_mode == "piecewise" and hasattr(step, "host_timing"):      # host seconds by kind of call over 5 more steps (launch-bound or not, and by what)
         step.host_timing = {}
         for _ in range(5):
             step()
@@ -763,7 +777,7 @@ def main():
     if graph_mode == "piecewise" and hasattr(step, "close"):
         step.close()                        # the eager steps below run one backward pass over the whole graph
     bucket_timeline = None
-    if collectives and reducer is not None and (args.bucket_timeline or world > 1):
+    if collectives and reducer is not None and (args.bucket_timeline or (args.full and world > 1)):
         # One eager step with HIP events around every bucket's exchange (rank 0 reports): when each bucket became final, when its collective
         # finished, both relative to the start of backward - the table DESIGN.md section 6 predicts, line by line.
         eager_step()
@@ -915,9 +929,9 @@ def main():
             result["bucket_timeline"] = bucket_timeline
         if world == 1 and args.caption_tokens > 0:
             result["caption"] = caption_leg(args, model, batch, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args)
-        want_companions = args.companions == "on" or (args.companions == "auto" and args.config == "B" and args.backbone_tweaks == "off"
+        want_companions = args.companions == "on" or (args.companions == "auto" and args.full and args.config == "B" and args.backbone_tweaks == "off"
                                                       and args.optimizer == "fused" and not args.no_optimizer and not collectives)
         if world == 1 and want_companions:
             # free this process's model and graph pools first: the children build their own copies on the same GPU

@@ -8,7 +8,7 @@ tag=$1; rnd=${2:-r04}; R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/$tag; mkdir -p $out
 cd $R
 timeout 1200 python -m pytest tests -m gpu -q -p no:cacheprovider > $out/pytest.txt 2>&1; echo "pytest rc=$?"; tail -n 3 $out/pytest.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1; echo "smoke rc=$?"; tail -n 2 $out/smoke.txt
-timeout 900 python bench.py --gemm-table $out/gemm_table.txt > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"; cut -c1-400 $out/bench_default.json
+timeout 900 python bench.py --full --gemm-table $out/gemm_table.txt > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"; cut -c1-400 $out/bench_default.json
 cd /tmp
 B="python $R/bench.py --no-cpu-baseline --caption-tokens 0 --profile-steps 0 --companions off"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- $B --steps 5 --warmup 2 > $out/prof_bench.json 2> $out/prof.err
@@ -26,8 +26,8 @@ cat $out/decode_chain.txt
 bash tools/sessions/r5/gpu_r5_s15.sh $tag > $out/launch_modes.log 2>&1      # the launch-mode table (stderr of every run kept, a run without a JSON line is named)
 head -4 $out/launch_modes_one_rank_rccl.txt
 # round 5: the other configurations of BASELINE.json (stock backbones, 6 timed steps), config E with its per-shape GEMM table and hipBLASLt beside every one of its shapes
-for c in A C D; do timeout 400 python bench.py --config $c --no-cpu-baseline --caption-tokens 0 --companions off --steps 6 --warmup 2 2> $out/bench_config_$c.err | tail -1 > $out/bench_config_$c.json; done
-timeout 600 python bench.py --config E --no-cpu-baseline --caption-tokens 0 --companions off --steps 6 --warmup 2 --gemm-table $out/gemm_table_E.txt 2> $out/bench_config_E.err | tail -1 > $out/bench_config_E.json
+for c in A C D; do timeout 400 python bench.py --full --config $c --no-cpu-baseline --caption-tokens 0 --companions off --steps 6 --warmup 2 2> $out/bench_config_$c.err | tail -1 > $out/bench_config_$c.json; done
+timeout 600 python bench.py --full --config E --no-cpu-baseline --caption-tokens 0 --companions off --steps 6 --warmup 2 --gemm-table $out/gemm_table_E.txt 2> $out/bench_config_E.err | tail -1 > $out/bench_config_E.json
 timeout 500 python tools/gemm_yardstick.py $out/gemm_table_E.txt > $out/gemm_yardstick_E.txt 2> $out/gemm_yardstick_E.err; head -4 $out/gemm_yardstick_E.txt | cut -c1-200
 for c in A C D E; do python -c "
 import json,sys
