@@ -26,6 +26,7 @@ struct AdamTable {
     float lr, beta1, beta2, eps, decay, bc1, bc2_sqrt, grad_scale;
     const float* step_dev;   // capturable mode: the step count lives on the device (HIP-graph replays cannot change kernel arguments)
     const float* lr_dev;     // ... and so does the learning rate, when a scheduler is to stay effective under replay
+    const float* grad_coef;  // CLIP kernels: device scalar multiplying every (grad_scale'd) gradient - the max-norm clip coefficient
 };
 
 // T: storage type of the parameters' compute copy and of the gradients; ST: storage type of the two moments; MASTER: the update
@@ -33,7 +34,9 @@ struct AdamTable {
 // (training/train.sh:24), so that steps far below bf16 resolution of a weight (lr 1e-4) are not lost.
 // MODE 1 (default for the bf16-state kernel; FF_ADAMW_MODE=0 for A/B): gradients and moments, touched once per step, are streamed with
 // nontemporal accesses so that they do not evict what the next kernels read (37.52 -> 37.40 ms/step at config B in a same-box A/B)
-template <typename T, typename ST, bool MASTER, int VEC, int MODE = 0>
+// CLIP: every gradient is also multiplied by *t.grad_coef (gradient clipping by global norm, ff_grad_clip_coef); the kernels without it
+// are the ones the unclipped step always ran.
+template <typename T, typename ST, bool MASTER, int VEC, int MODE = 0, bool CLIP = false>
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     int ti = 0;
 #pragma unroll 1
@@ -52,6 +55,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
         bc2_sqrt = sqrtf(1.f - powf(t.beta2, step));
     }
     const float lr = t.lr_dev ? *t.lr_dev : t.lr;
+    // CLIP folds the coefficient into the one factor every gradient is multiplied by (the unclipped instantiations compile as before).  With
+    // a coefficient of 1 the parameters and the fp32 kernel's moments are the unclipped ones bit for bit; the bf16-parameter kernels contract
+    // the moments' multiply-adds differently, so those may differ in the last bit
+    float clip_scale = 0.f;
+    if constexpr (CLIP) clip_scale = t.grad_scale * *t.grad_coef;
     const float step_size = lr / bc1, keep = 1.f - lr * t.decay;
     bool vec = VEC > 1 && n % VEC == 0 && ((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0;
     if (MASTER) vec = vec && (uintptr_t)w % 16 == 0;
@@ -83,7 +91,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     auto update = [&](float (&pf)[VEC], const float (&gf)[VEC], float (&mf)[VEC], float (&vf)[VEC]) {
 #pragma unroll
         for (int e = 0; e < VEC; e++) {
-            const float gr = gf[e] * t.grad_scale;
+            float gr;
+            if constexpr (CLIP) gr = gf[e] * clip_scale;
+            else gr = gf[e] * t.grad_scale;
             pf[e] *= keep;
             mf[e] = t.beta1 * mf[e] + (1.f - t.beta1) * gr;
             vf[e] = t.beta2 * vf[e] + (1.f - t.beta2) * gr * gr;
@@ -139,8 +149,22 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     }
 }
 
+template <bool CLIP>
+static void adamw_dispatch(int dtype, bool master, int state_dtype, dim3 grid, hipStream_t stream, const AdamTable& t) {
+    const dim3 block(256);
+    if (dtype == FF_DTYPE_F32) adamw_kernel<float, float, false, 4, 0, CLIP><<<grid, block, 0, stream>>>(t);
+    else if (master) adamw_kernel<bf16, float, true, 8, 1, CLIP><<<grid, block, 0, stream>>>(t);  // (master copy, gradients, moments: streamed nontemporally)
+    else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1, CLIP><<<grid, block, 0, stream>>>(t);
+    else {
+        static const int mode = CLIP ? 1 : dbg_switch("FF_ADAMW_MODE", 1);
+        if (mode >= 1) adamw_kernel<bf16, bf16, false, 8, 1, CLIP><<<grid, block, 0, stream>>>(t);
+        else if constexpr (!CLIP) adamw_kernel<bf16, bf16, false, 8><<<grid, block, 0, stream>>>(t);
+    }
+}
+
 static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, void* const* exp_avg,
-                        void* const* exp_avg_sq, float* const* master, const float* lr_dev, const long long* numels, hipStream_t stream) {
+                        void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef, const long long* numels,
+                        hipStream_t stream) {
     FF_CHECK(d && params && grads && exp_avg && exp_avg_sq && numels, FF_ERR_SHAPE, "ff_adamw_step: null argument");
     FF_CHECK(d->dtype == FF_DTYPE_F32 || d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_adamw_step: dtype %d", d->dtype);
     FF_CHECK(state_dtype == d->dtype || state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: moments must be stored in the parameter dtype or in fp32");
@@ -150,6 +174,7 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
     t.lr = d->lr; t.beta1 = d->beta1; t.beta2 = d->beta2; t.eps = d->eps; t.decay = d->weight_decay;
     t.step_dev = d->step_dev;
     t.lr_dev = lr_dev;
+    t.grad_coef = grad_coef;
     t.bc1 = 1.f - powf(d->beta1, (float)std::max(d->step, 1));
     t.bc2_sqrt = sqrtf(1.f - powf(d->beta2, (float)std::max(d->step, 1)));
     t.grad_scale = d->grad_scale == 0.f ? 1.f : d->grad_scale;
@@ -170,18 +195,172 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
         if (!cnt) break;
         t.block_start[cnt] = blocks;
         t.count = cnt;
-        const dim3 grid(blocks), block(256);
-        if (d->dtype == FF_DTYPE_F32) adamw_kernel<float, float, false, 4><<<grid, block, 0, stream>>>(t);
-        else if (master) {
-            FF_CHECK(state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: fp32 master copies go with fp32 moments");
-            adamw_kernel<bf16, float, true, 8, 1><<<grid, block, 0, stream>>>(t);       // (master copy, gradients, moments: streamed nontemporally)
-        } else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1><<<grid, block, 0, stream>>>(t);
-        else {
-            static const int mode = dbg_switch("FF_ADAMW_MODE", 1);
-            if (mode >= 1) adamw_kernel<bf16, bf16, false, 8, 1><<<grid, block, 0, stream>>>(t);
-            else adamw_kernel<bf16, bf16, false, 8><<<grid, block, 0, stream>>>(t);
-        }
+        const dim3 grid(blocks);
+        if (master) FF_CHECK(state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: fp32 master copies go with fp32 moments");
+        if (grad_coef) adamw_dispatch<true>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
+        else adamw_dispatch<false>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
         FF_TRY(check_launch("adamw"));
+    }
+    return FF_OK;
+}
+
+
+// ---- gradient clipping by global L2 norm (torch.nn.utils.clip_grad_norm_, norm_type 2; HF Trainer's max_grad_norm) ----------------------
+// Sum of squares over many gradient tensors in the AdamW table's chunks: workgroup b of a launch writes ONE fp32 partial, partials[b]
+// (no atomics: fixed slots, so the total is reproducible bit for bit); ff_grad_sumsq_reduce adds the partials up in fp64 in a fixed
+// order, ff_grad_clip_coef turns the sum into the norm and the coefficient AdamW (CLIP) or ff_scale_grads applies on the device.
+struct GradTable {
+    void* g[kAdamTensors];
+    long long n[kAdamTensors];
+    int block_start[kAdamTensors + 1];
+    int count;
+    float scale;             // sumsq: each gradient is multiplied by it before squaring (grad_scale)
+    float* partials;         // sumsq: one slot per workgroup of the launch
+    const float* coef;       // scale: device scalar every gradient is multiplied by
+};
+constexpr long long kGradMaxBlocks = 1 << 22;       // workgroups per launch (x 256 threads stays far below 2^32; block_start stays an int)
+
+template <typename T>
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const GradTable t) {
+    __shared__ float red[4];
+    constexpr int VEC = Vec<T>::N, PIECES = 8;      // 8 independent 16-byte loads per thread in flight before the first square
+    int ti = 0;
+#pragma unroll 1
+    while (ti + 1 < t.count && (int)blockIdx.x >= t.block_start[ti + 1]) ti++;
+    const long long n = t.n[ti];
+    const long long base = (long long)((int)blockIdx.x - t.block_start[ti]) * kAdamChunk;
+    const long long end = min(n, base + (long long)kAdamChunk);
+    const T* g = (const T*)t.g[ti];
+    const float scale = t.scale;
+    float acc = 0.f;
+    long long tail = base;                          // elements from here to `end` are summed one by one
+    if ((uintptr_t)g % 16 == 0) {                   // (base is a multiple of the chunk, so every vector below is 16-byte aligned)
+        const long long vend = base + (end - base) / VEC * VEC;
+        tail = vend;
+        long long i = base + (long long)threadIdx.x * VEC;
+        for (; i + (PIECES - 1) * 256 * VEC < vend; i += PIECES * 256 * VEC) {
+            typename Vec<T>::raw r[PIECES];
+#pragma unroll
+            for (int k = 0; k < PIECES; k++) r[k] = __builtin_nontemporal_load((const typename Vec<T>::raw*)(g + i + k * 256 * VEC));
+#pragma unroll
+            for (int k = 0; k < PIECES; k++)
+#pragma unroll
+                for (int e = 0; e < VEC; e++) {
+                    const float x = (float)r[k][e] * scale;
+                    acc = fmaf(x, x, acc);
+                }
+        }
+        for (; i < vend; i += 256 * VEC) {          // (a tensor's last, partial chunk)
+            float x[VEC];
+            Vec<T>::load_nt(g + i, x);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) {
+                const float y = x[e] * scale;
+                acc = fmaf(y, y, acc);
+            }
+        }
+    }
+    for (long long i = tail + threadIdx.x; i < end; i += 256) {      // ragged tail (< VEC elements), or an unaligned tensor's whole chunk
+        const float x = to_f32(g[i]) * scale;
+        acc = fmaf(x, x, acc);
+    }
+    acc = block_sum<4>(acc, red);
+    if (threadIdx.x == 0) t.partials[blockIdx.x] = acc;
+}
+
+// one workgroup: sum = (accumulate ? *sum : 0) + the partials, in fp64 and in a fixed order (thread k adds slots k, k + 1024, ... in
+// index order; the 16 waves combine with a fixed shuffle tree; thread 0 adds the wave sums in wave order)
+__global__ __launch_bounds__(1024) void grad_sumsq_reduce_kernel(const float* partials, long long n, double* sum, int accumulate) {
+    __shared__ double red[16];
+    double s = 0.0;
+    long long i = threadIdx.x;
+    for (; i + 3 * 1024 < n; i += 4 * 1024) {
+        const float a = partials[i], b = partials[i + 1024], c = partials[i + 2048], d = partials[i + 3072];
+        s += (double)a; s += (double)b; s += (double)c; s += (double)d;
+    }
+    for (; i < n; i += 1024) s += (double)partials[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = accumulate ? *sum : 0.0;
+        for (int w = 0; w < 16; w++) total += red[w];
+        *sum = total;
+    }
+}
+
+// torch.nn.utils.clip_grad_norm_: norm = ||g||_2 (fp32), coef = clamp(max_norm / (norm + 1e-6), max=1) - a NaN norm gives a NaN coefficient
+// and an infinite one 0, as there (no step is skipped)
+__global__ void grad_clip_coef_kernel(const double* sum, float max_norm, float* norm, float* coef) {
+    if (threadIdx.x != 0) return;
+    const float nrm = (float)sqrt(*sum);
+    const float c = max_norm / (nrm + 1e-6f);
+    if (norm) *norm = nrm;
+    if (coef) *coef = c > 1.f ? 1.f : c;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void grad_scale_kernel(const GradTable t) {
+    constexpr int VEC = Vec<T>::N;
+    int ti = 0;
+#pragma unroll 1
+    while (ti + 1 < t.count && (int)blockIdx.x >= t.block_start[ti + 1]) ti++;
+    const long long n = t.n[ti];
+    const long long base = (long long)((int)blockIdx.x - t.block_start[ti]) * kAdamChunk;
+    const long long end = min(n, base + (long long)kAdamChunk);
+    T* g = (T*)t.g[ti];
+    const float c = *t.coef;
+    long long tail = base;
+    if ((uintptr_t)g % 16 == 0) {                   // vector body; a ragged tail and an unaligned tensor go element by element
+        const long long vend = base + (end - base) / VEC * VEC;
+        tail = vend;
+        for (long long i = base + (long long)threadIdx.x * VEC; i < vend; i += 256 * VEC) {
+            float x[VEC];
+            Vec<T>::load(g + i, x);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) x[e] *= c;
+            Vec<T>::store(g + i, x);
+        }
+    }
+    for (long long i = tail + threadIdx.x; i < end; i += 256) g[i] = from_f32<T>(to_f32(g[i]) * c);
+}
+
+static long long grad_slots(int n_tensors, const long long* numels) {
+    long long slots = 0;
+    for (int i = 0; i < n_tensors; i++)
+        if (numels[i] > 0) slots += (numels[i] + kAdamChunk - 1) / kAdamChunk;
+    return slots;
+}
+
+// the tensors of one call in launches of <= kAdamTensors tensors and <= kGradMaxBlocks workgroups; launch(table, blocks, first slot)
+template <typename F>
+static int grad_launches(const char* what, int n_tensors, void* const* grads, const long long* numels, GradTable& t, F&& launch) {
+    FF_CHECK(n_tensors >= 0 && (n_tensors == 0 || (grads && numels)), FF_ERR_SHAPE, "%s: null argument", what);
+    long long slot = 0;
+    int i = 0;
+    while (i < n_tensors) {
+        int cnt = 0;
+        long long blocks = 0;
+        while (i < n_tensors && cnt < kAdamTensors) {
+            if (numels[i] > 0) {
+                const long long b = (numels[i] + kAdamChunk - 1) / kAdamChunk;
+                FF_CHECK(b <= kGradMaxBlocks, FF_ERR_SHAPE, "%s: tensor %d has %lld elements", what, i, numels[i]);
+                if (blocks + b > kGradMaxBlocks) break;
+                FF_CHECK(grads[i], FF_ERR_SHAPE, "%s: tensor %d has a null pointer", what, i);
+                t.g[cnt] = grads[i]; t.n[cnt] = numels[i];
+                t.block_start[cnt] = (int)blocks;
+                blocks += b;
+                cnt++;
+            }
+            i++;
+        }
+        if (!cnt) break;
+        t.block_start[cnt] = (int)blocks;
+        t.count = cnt;
+        launch(t, (int)blocks, slot);
+        FF_TRY(check_launch(what));
+        slot += blocks;
     }
     return FF_OK;
 }
@@ -190,10 +369,59 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
 
 extern "C" int ff_adamw_step(const ff_adamw_desc* d, void* const* params, const void* const* grads, void* const* exp_avg,
                              void* const* exp_avg_sq, const long long* numels, ff_stream_t stream) {
-    return ff::adamw_launch(d, d ? d->dtype : 0, params, grads, exp_avg, exp_avg_sq, nullptr, nullptr, numels, (hipStream_t)stream);
+    return ff::adamw_launch(d, d ? d->dtype : 0, params, grads, exp_avg, exp_avg_sq, nullptr, nullptr, nullptr, numels, (hipStream_t)stream);
 }
 extern "C" int ff_adamw_step_mixed(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, void* const* exp_avg,
                                    void* const* exp_avg_sq, float* const* master, const float* lr_dev, const long long* numels,
                                    ff_stream_t stream) {
-    return ff::adamw_launch(d, state_dtype, params, grads, exp_avg, exp_avg_sq, master, lr_dev, numels, (hipStream_t)stream);
+    return ff::adamw_launch(d, state_dtype, params, grads, exp_avg, exp_avg_sq, master, lr_dev, nullptr, numels, (hipStream_t)stream);
+}
+
+extern "C" int ff_adamw_step_clipped(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, void* const* exp_avg,
+                                     void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef,
+                                     const long long* numels, ff_stream_t stream) {
+    FF_CHECK(grad_coef, FF_ERR_SHAPE, "ff_adamw_step_clipped: grad_coef is null");
+    return ff::adamw_launch(d, state_dtype, params, grads, exp_avg, exp_avg_sq, master, lr_dev, grad_coef, numels, (hipStream_t)stream);
+}
+extern "C" long long ff_grad_sumsq_partials(int n_tensors, const long long* numels) {
+    return n_tensors > 0 && numels ? ff::grad_slots(n_tensors, numels) : 0;
+}
+extern "C" int ff_grad_sumsq(int dtype, int n_tensors, const void* const* grads, const long long* numels, float scale, float* partials,
+                             long long n_partials, ff_stream_t stream) {
+    using namespace ff;
+    FF_CHECK(dtype == FF_DTYPE_F32 || dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_grad_sumsq: dtype %d", dtype);
+    FF_CHECK(n_tensors >= 0 && (n_tensors == 0 || numels), FF_ERR_SHAPE, "ff_grad_sumsq: null argument");
+    const long long need = n_tensors > 0 ? grad_slots(n_tensors, numels) : 0;
+    FF_CHECK(need <= n_partials && (need == 0 || partials), FF_ERR_WORKSPACE, "ff_grad_sumsq: %lld partials needed, %lld given", need, n_partials);
+    GradTable t;
+    t.scale = scale;
+    t.coef = nullptr;
+    return grad_launches("ff_grad_sumsq", n_tensors, (void* const*)grads, numels, t, [&](GradTable& tt, int blocks, long long slot) {
+        tt.partials = partials + slot;
+        if (dtype == FF_DTYPE_F32) grad_sumsq_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
+        else grad_sumsq_kernel<bf16><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
+    });
+}
+extern "C" int ff_grad_sumsq_reduce(const float* partials, long long n_partials, double* sum, int accumulate, ff_stream_t stream) {
+    FF_CHECK(sum && n_partials >= 0 && (n_partials == 0 || partials), FF_ERR_SHAPE, "ff_grad_sumsq_reduce: null argument");
+    ff::grad_sumsq_reduce_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(partials, n_partials, sum, accumulate);
+    return ff::check_launch("ff_grad_sumsq_reduce");
+}
+extern "C" int ff_grad_clip_coef(const double* sum, float max_norm, float* norm, float* coef, ff_stream_t stream) {
+    FF_CHECK(sum && (norm || coef), FF_ERR_SHAPE, "ff_grad_clip_coef: null argument");
+    ff::grad_clip_coef_kernel<<<1, 64, 0, (hipStream_t)stream>>>(sum, max_norm, norm, coef);
+    return ff::check_launch("ff_grad_clip_coef");
+}
+extern "C" int ff_scale_grads(int dtype, int n_tensors, void* const* grads, const long long* numels, const float* coef, ff_stream_t stream) {
+    using namespace ff;
+    FF_CHECK(dtype == FF_DTYPE_F32 || dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_scale_grads: dtype %d", dtype);
+    FF_CHECK(coef, FF_ERR_SHAPE, "ff_scale_grads: coef is null");
+    GradTable t;
+    t.scale = 1.f;
+    t.partials = nullptr;
+    t.coef = coef;
+    return grad_launches("ff_scale_grads", n_tensors, grads, numels, t, [&](GradTable& tt, int blocks, long long) {
+        if (dtype == FF_DTYPE_F32) grad_scale_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
+        else grad_scale_kernel<bf16><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
+    });
 }

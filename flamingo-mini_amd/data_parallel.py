@@ -17,6 +17,7 @@ the ones that are not.
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 from typing import List, Optional
 
 import torch
@@ -298,14 +299,25 @@ class ShardedAdamW(torch.optim.Optimizer):
     `step()` on the accumulated values.  A second backward without no_sync() after a bucket was already updated in this step raises.
     `capturable=True` keeps the step count and the learning rate in device scalars (graphs.GraphedTrainStep replays the step).
 
+    `max_grad_norm=c` clips the global L2 norm of the averaged gradients to c before the update (torch.nn.utils.clip_grad_norm_, HF
+    Trainer's max_grad_norm).  Each bucket's pipeline then stops after the reduce-scatter: it writes the sum of squares of this rank's
+    share of the bucket's parameters (not the alignment pads) into the bucket's fixed slots (ff_grad_sumsq) while backward continues.
+    step() adds the slots up (fp64), all-reduces that one scalar, adds the replicated un-fused parameters' share once, after the
+    all-reduce, computes the coefficient on the device, and only then runs every bucket's update and all-gather, and the un-fused
+    parameters' update, with it - every rank gets the same coefficient bit for bit.  The update no longer overlaps backward.  `grad_norm`
+    is the pre-clip norm of the last step.
+
     xGMI arithmetic (8 GPUs, 7 links x ~153 GB/s each): reduce-scatter + all-gather move 2 * (S / 8) per link pair instead of a
     ring's 2 * (7/8) * S over one link, and the update touches 1/8 of the state per rank.
     """
 
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  master_dtype=None, process_group: Optional[dist.ProcessGroup] = None, force_collectives: bool = False, update_fn=None,
-                 capturable: bool = False, overlap: bool = False):
+                 capturable: bool = False, overlap: bool = False, max_grad_norm: Optional[float] = None):
         from .optim import FusedAdamW
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm must be > 0 (None: no clipping), got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
@@ -343,11 +355,30 @@ class ShardedAdamW(torch.optim.Optimizer):
         self._loose_update_fn = update_fn
         self._loose_state = {}
         self._undo = _bucket_launch_structure(model) if self.collectives else []
+        self._pending = []           # max_grad_norm: buckets exchanged in the running step, updated in step() once the coefficient exists
+        self._clip = None            # max_grad_norm: the buckets' partial slots and the device scalars (kernel path)
+        if self.max_grad_norm is not None and update_fn is None and on_gpu:
+            from . import ffi
+            fused_p = [p for p in model.parameters() if id(p) in fused]
+            dev = fused_p[0].device if fused_p else next(p.device for p in model.parameters() if p.is_cuda)
+            # room for every bucket's slots: this rank sums at most one piece of each parameter
+            cap = int(ffi.lib().ff_grad_sumsq_partials(len(fused_p), (C.c_longlong * len(fused_p))(*[p.numel() for p in fused_p])))
+            self._clip = dict(partials=torch.zeros(max(cap, 1), dtype=torch.float32, device=dev), used=0, loose_partials=None,
+                              sum=torch.zeros((), dtype=torch.float64, device=dev), norm=torch.zeros((), dtype=torch.float32, device=dev),
+                              coef=torch.ones((), dtype=torch.float32, device=dev))
+        elif self.max_grad_norm is not None:
+            self._clip = dict(norm=None)         # (CPU test hook: the same sequence in torch)
         F.add_grad_ready_callback(self._on_bucket)
 
     @property
     def hp(self):
         return self.param_groups[0]
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """max_grad_norm: the global L2 norm of the averaged gradients before clipping, from the last step (0-dim fp32; on the device its
+        storage is the same every step).  None without max_grad_norm."""
+        return None if self._clip is None else self._clip["norm"]
 
     def close(self):
         F.remove_grad_ready_callback(self._on_bucket)
@@ -389,9 +420,8 @@ class ShardedAdamW(torch.optim.Optimizer):
         return sc
 
     # ---- the kernel call (tests substitute a torch implementation through update_fn on CPU ranks) ----
-    def _hip_update(self, p, g, m, v, master, step):
+    def _hip_update(self, p, g, m, v, master, step, coef=None):
         from . import ffi
-        import ctypes as C
         lib = ffi.lib()
         step_dev = lr_dev = None
         if self.capturable:
@@ -400,8 +430,70 @@ class ShardedAdamW(torch.optim.Optimizer):
         desc = ffi.AdamWDesc(ffi.dtype_code(p.dtype), 1, step, self.hp["lr"], self.hp["betas"][0], self.hp["betas"][1], self.hp["eps"],
                              self.hp["weight_decay"], 1.0, step_dev)
         one = lambda t: ffi.ptr_array([t])
-        ffi.check(lib.ff_adamw_step_mixed(desc, ffi.dtype_code(m.dtype), one(p), one(g), one(m), one(v), None if master is None else one(master),
-                                          lr_dev, (C.c_longlong * 1)(p.numel()), ffi.stream_handle(p.device)), "ff_adamw_step_mixed")
+        if coef is None:
+            ffi.check(lib.ff_adamw_step_mixed(desc, ffi.dtype_code(m.dtype), one(p), one(g), one(m), one(v), None if master is None else one(master),
+                                              lr_dev, (C.c_longlong * 1)(p.numel()), ffi.stream_handle(p.device)), "ff_adamw_step_mixed")
+        else:
+            ffi.check(lib.ff_adamw_step_clipped(desc, ffi.dtype_code(m.dtype), one(p), one(g), one(m), one(v), None if master is None else one(master),
+                                                lr_dev, coef.data_ptr(), (C.c_longlong * 1)(p.numel()), ffi.stream_handle(p.device)), "ff_adamw_step_clipped")
+
+    # ---- gradient clipping (max_grad_norm) ----
+    def _shard_sumsq(self, st, g):
+        """Sum of squares of this rank's averaged gradient pieces into the bucket's slots (torch on the CPU test ranks)."""
+        if "partials" not in self._clip:
+            st["sumsq"] = sum((g[a:a + n].detach().double().pow(2).sum() for a, n in st["own"]), torch.zeros((), dtype=torch.float64, device=g.device))
+            return
+        from . import ffi
+        own, part, es = st["own"], self._clip["partials"], g.element_size()
+        ptrs = (C.c_void_p * len(own))(*[g.data_ptr() + a * es for a, _ in own])
+        ffi.check(ffi.lib().ff_grad_sumsq(ffi.dtype_code(g.dtype), len(own), ptrs, (C.c_longlong * len(own))(*[n for _, n in own]), 1.0,
+                                          part.data_ptr() + 4 * st["slot"], part.numel() - st["slot"], ffi.stream_handle(g.device)), "ff_grad_sumsq")
+
+    def _clip_coef(self):
+        """The coefficient of this step from the shards' slots, the one all-reduce of their sum and the un-fused parameters' gradients
+        (replicated and already averaged: counted once, after the all-reduce)."""
+        loose = [p.grad for p in self.loose if p.grad is not None]
+        clip = self._clip
+        pending = {id(st) for st in self._pending}
+        if "partials" not in clip:                # CPU test hook: the same sequence in torch
+            total = torch.zeros((), dtype=torch.float64)
+            for st in self.buckets.values():
+                if id(st) in pending:
+                    total = total + st["sumsq"].cpu()
+            if self.collectives:
+                dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
+            for g in loose:
+                total = total + g.detach().double().pow(2).sum().cpu()
+            clip["norm"] = total.sqrt().float()
+            return torch.clamp(self.max_grad_norm / (clip["norm"] + 1e-6), max=1.0)
+        from . import ffi
+        lib = ffi.lib()
+        part, dev = clip["partials"], clip["partials"].device
+        stream = ffi.stream_handle(dev)
+        for st in self.buckets.values():          # a bucket without a gradient in this step adds nothing
+            if id(st) not in pending and st["slots"]:
+                part[st["slot"]:st["slot"] + st["slots"]].zero_()
+        ffi.check(lib.ff_grad_sumsq_reduce(part.data_ptr(), clip["used"], clip["sum"].data_ptr(), 0, stream), "ff_grad_sumsq_reduce")
+        if self.collectives:
+            dist.all_reduce(clip["sum"], op=dist.ReduceOp.SUM, group=self.group)
+        if loose:
+            tables = []
+            for dt in (torch.float32, torch.bfloat16):
+                gs = [g for g in loose if g.dtype == dt]
+                if gs:
+                    n = (C.c_longlong * len(gs))(*[g.numel() for g in gs])
+                    tables.append((ffi.dtype_code(dt), gs, n, int(lib.ff_grad_sumsq_partials(len(gs), n))))
+            need = sum(t[3] for t in tables)
+            if clip["loose_partials"] is None or clip["loose_partials"].numel() < need:
+                clip["loose_partials"] = torch.zeros(max(need, 1), dtype=torch.float32, device=dev)
+            lp, off = clip["loose_partials"], 0
+            for code, gs, n, k in tables:
+                ffi.check(lib.ff_grad_sumsq(code, len(gs), ffi.ptr_array(gs), n, 1.0, lp.data_ptr() + 4 * off, lp.numel() - off, stream), "ff_grad_sumsq")
+                off += k
+            ffi.check(lib.ff_grad_sumsq_reduce(lp.data_ptr(), off, clip["sum"].data_ptr(), 1, stream), "ff_grad_sumsq_reduce")
+        ffi.check(lib.ff_grad_clip_coef(clip["sum"].data_ptr(), self.max_grad_norm, clip["norm"].data_ptr(), clip["coef"].data_ptr(), stream),
+                  "ff_grad_clip_coef")
+        return clip["coef"]
 
     def _bucket_name(self, owners) -> str:
         return self._names.get(id(owners[0][0]), f"bucket{len(self.buckets)}")
@@ -427,13 +519,35 @@ class ShardedAdamW(torch.optim.Optimizer):
             st = dict(name=self._bucket_name(owners), owners=[(p, off, cnt) for p, off, cnt in owners], params=[p for p, _, _ in owners], pflat=pflat,
                       shard=shard, lo=lo, m=torch.zeros(shard, dtype=sdt, device=flat.device), v=torch.zeros(shard, dtype=sdt, device=flat.device),
                       master=pflat[lo:lo + shard].to(torch.float32) if sdt != flat.dtype else None, gshard=torch.empty(shard, dtype=flat.dtype, device=flat.device))
+            if self.max_grad_norm is not None:
+                # the pieces of this rank's shard that hold parameters (shard-relative offset, length): the pads between and after them
+                # are never written by the kernels, so they are not summed
+                own = [(max(off, lo) - lo, min(off + cnt, lo + shard) - max(off, lo)) for _, off, cnt in owners if max(off, lo) < min(off + cnt, lo + shard)]
+                st["own"] = own
+                if "partials" in self._clip:          # this bucket's fixed partial slots (in order of creation)
+                    from . import ffi
+                    k = int(ffi.lib().ff_grad_sumsq_partials(len(own), (C.c_longlong * len(own))(*[n for _, n in own])))
+                    if self._clip["used"] + k > self._clip["partials"].numel():
+                        raise RuntimeError("ShardedAdamW: the gradient-norm partial slots are exhausted")
+                    st.update(slot=self._clip["used"], slots=k)
+                    self._clip["used"] += k
             if self._loaded is not None and st["name"] in self._loaded:
                 self._restore_bucket(st, self._loaded.pop(st["name"]))
             self.buckets[key] = st
         return st
 
     def _pipeline(self, st, flat):
-        """reduce-scatter -> update of this rank's slice -> all-gather, on the current stream."""
+        """reduce-scatter -> update of this rank's slice -> all-gather, on the current stream.  max_grad_norm: reduce-scatter -> sum of
+        squares of this rank's slice; the update and the all-gather wait for step() (_update)."""
+        g = self._exchange(st, flat)
+        if self.max_grad_norm is not None:
+            st["g"] = g
+            self._pending.append(st)
+            self._shard_sumsq(st, g)
+            return
+        self._update(st, g)
+
+    def _exchange(self, st, flat):
         lo, shard = st["lo"], st["shard"]
         if self.collectives:
             if self.cuda:
@@ -444,7 +558,16 @@ class ShardedAdamW(torch.optim.Optimizer):
             g = st["gshard"]
         else:
             g = flat[lo:lo + shard]
-        self._update_fn(st["pflat"][lo:lo + shard], g, st["m"], st["v"], st["master"], self.step_count + 1)
+        return g
+
+    def _update(self, st, g, coef=None):
+        lo, shard = st["lo"], st["shard"]
+        if coef is None:
+            self._update_fn(st["pflat"][lo:lo + shard], g, st["m"], st["v"], st["master"], self.step_count + 1)
+        elif self._update_fn == self._hip_update:
+            self._hip_update(st["pflat"][lo:lo + shard], g, st["m"], st["v"], st["master"], self.step_count + 1, coef)
+        else:                                    # (CPU test hook)
+            self._update_fn(st["pflat"][lo:lo + shard], g * coef, st["m"], st["v"], st["master"], self.step_count + 1)
         if self.collectives:
             dist.all_gather_into_tensor(st["pflat"], st["pflat"][lo:lo + shard].clone() if not self.cuda else st["pflat"][lo:lo + shard], group=self.group)
 
@@ -517,19 +640,26 @@ class ShardedAdamW(torch.optim.Optimizer):
             self._updated.add(tuple(id(p) for p in st["params"]))
             self._pipeline(st, flat)
         self._late.clear()
+        coef = None
+        if self.max_grad_norm is not None:
+            coef = self._clip_coef()
+            for st in self._pending:
+                self._update(st, st.pop("g"), coef)
+            self._pending.clear()
         self._updated.clear()
         self._arrival = 0
         self.step_count += 1
         if self._loose_opt is not None:
             for g in self._loose_opt.param_groups:
                 g["lr"] = self.hp["lr"]
-            self._loose_opt.step()
+            self._loose_opt.step(grad_coef=coef)
         else:
             for p in self.loose:
                 if p.grad is None:
                     continue
                 s = self._loose_state.setdefault(id(p), dict(m=torch.zeros_like(p), v=torch.zeros_like(p)))
-                self._loose_update_fn(p.data.view(-1), p.grad.view(-1), s["m"].view(-1), s["v"].view(-1), None, self.step_count)
+                g = p.grad.view(-1) if coef is None else p.grad.view(-1) * coef
+                self._loose_update_fn(p.data.view(-1), g, s["m"].view(-1), s["v"].view(-1), None, self.step_count)
 
     @torch.no_grad()
     def step(self, closure=None):

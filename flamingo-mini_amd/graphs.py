@@ -303,6 +303,9 @@ class PiecewiseGraphedTrainStep:
             raise ValueError("pace must be 'host' or 'stream'")
         if overlap_optimizer and (pace != "host" or not capture):
             raise ValueError("overlap_optimizer needs pace='host' and capture=True")
+        if overlap_optimizer and getattr(optimizer, "max_grad_norm", None) is not None:
+            raise ValueError("overlap_optimizer=True updates a segment's parameters before the global gradient norm exists, so it cannot be "
+                             "combined with an optimizer with max_grad_norm set: use overlap_optimizer=False to clip")
         self.model, self.optimizer, self.reducer = model, optimizer, reducer
         self.pace = pace
         self.overlap_optimizer = bool(overlap_optimizer) and optimizer is not None

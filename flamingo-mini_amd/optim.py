@@ -10,11 +10,20 @@ changing `group["lr"]`: call `sync_device_hyperparams()` (GraphedTrainStep does)
 Mixed precision (the reference trains with `--fp16` autocast = fp32 master weights and fp32 moments, training/train.sh:24):
 `master_dtype=torch.float32` keeps an fp32 master copy of every bf16 parameter in the optimizer state (`state["master"]`); the kernel
 updates the master copy and writes its bf16 rounding into the parameter in the same pass, so steps far below the bf16 resolution of a
-weight (lr 1e-4) accumulate instead of vanishing.  `state_dtype=torch.float32` alone keeps only the two moments in fp32."""
+weight (lr 1e-4) accumulate instead of vanishing.  `state_dtype=torch.float32` alone keeps only the two moments in fp32.
+
+Gradient clipping (the reference's HF Trainer clips the global L2 norm of the gradients to `max_grad_norm`, default 1.0, before every
+step): `max_grad_norm=c` makes step() equal torch.nn.utils.clip_grad_norm_(params, c) followed by the AdamW update, without a pass that
+rewrites the gradients - one sum-of-squares sweep over every gradient of every group (ff_grad_sumsq, fixed per-workgroup slots), an fp64
+reduction to the norm and the coefficient on the device (ff_grad_sumsq_reduce, ff_grad_clip_coef), and the AdamW kernel multiplies each
+gradient by the coefficient as it reads it (ff_adamw_step_clipped); `.grad` stays unscaled.  `grad_norm` is the pre-clip norm of the last
+step (what HF logs as grad_norm), a device scalar that keeps its storage, so it is valid after a graph replay too.  Nothing synchronises
+with the host: GraphedTrainStep captures the clipped step as it is.  With data parallelism, GradientAllReducer.finish() has averaged the
+gradients before step() reads them, so the norm is the global one; ShardedAdamW takes its own max_grad_norm."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable
+from typing import Iterable, Optional
 
 import torch
 
@@ -23,22 +32,43 @@ from . import ffi
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 grad_scale: float = 1.0, capturable: bool = False, master_dtype=None, state_dtype=None):
+                 grad_scale: float = 1.0, capturable: bool = False, master_dtype=None, state_dtype=None, max_grad_norm: Optional[float] = None):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameters")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm must be > 0 (None: no clipping), got {max_grad_norm}")
+        # an optimizer-wide setting (the norm spans every group), so it is no group hyper-parameter and stays out of state_dict()
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._clip = None                                 # clipping: partials / fp64 sum / norm / coefficient on the device (first step)
         if master_dtype not in (None, torch.float32) or state_dtype not in (None, torch.float32):
             raise ValueError("master_dtype / state_dtype: None (the parameter's dtype) or torch.float32")
         if master_dtype is not None:
             state_dtype = torch.float32                   # fp32 masters go with fp32 moments
         self.master_dtype, self.state_dtype = master_dtype, state_dtype
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, capturable=capturable))
+        if self.max_grad_norm is not None and len({p.device for g in self.param_groups for p in g["params"]}) > 1:
+            raise ValueError("FusedAdamW(max_grad_norm=...) needs every parameter on one device (the global norm is reduced on it)")
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """max_grad_norm: the total L2 norm of the gradients (grad_scale applied) BEFORE clipping, from the last step - a 0-dim fp32 device
+        tensor whose storage is the same every step (None before the first step, and without max_grad_norm)."""
+        return None if self._clip is None else self._clip["norm"]
 
     @torch.no_grad()
-    def step(self, closure=None, *, only=None, advance: bool = True):
+    def step(self, closure=None, *, only=None, advance: bool = True, grad_coef: Optional[torch.Tensor] = None):
         """only / advance (capturable mode): update just the parameters whose id() is in `only` - one of several calls that together cover every
         parameter with a gradient exactly once per training step (graphs.PiecewiseGraphedTrainStep(overlap_optimizer=True) updates the
         parameters of a backward segment while the next segments still run).  The FIRST partial call of a training step passes advance=True
-        (the device step counters count training steps, not calls) and must execute before the others."""
+        (the device step counters count training steps, not calls) and must execute before the others.  Not with max_grad_norm: the norm
+        needs every gradient of the step before the first update.
+        grad_coef: a 0-dim fp32 device tensor every gradient is multiplied by - a clip coefficient computed elsewhere (ShardedAdamW's, over
+        the gradients of every rank); only without max_grad_norm."""
+        if self.max_grad_norm is not None and only is not None:
+            raise ValueError("FusedAdamW.step(only=...) cannot clip gradients: max_grad_norm needs the norm over every gradient before the first "
+                             "update (PiecewiseGraphedTrainStep(overlap_optimizer=True) cannot be used with it)")
+        if self.max_grad_norm is not None and grad_coef is not None:
+            raise ValueError("FusedAdamW.step(grad_coef=...) replaces the optimizer's own clipping: construct it without max_grad_norm")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -53,17 +83,14 @@ class FusedAdamW(torch.optim.Optimizer):
             only = frozenset(only)
             if not all(g.get("capturable", False) for g in self.param_groups):
                 raise ValueError("FusedAdamW.step(only=...) needs capturable=True (step counts live in device scalars shared by the partial calls)")
+        coef = self._clip_coef(lib) if self.max_grad_norm is not None else grad_coef
         for gi, group in enumerate(self.param_groups):
             capturable = group.get("capturable", False)
             if capturable and advance:
                 self._advance_device_steps(group)
             for bucket in self._buckets(gi, group, only):
                 params, grad_ptrs, n = bucket["params"], bucket["grad_ptrs"], len(bucket["params"])
-                for i, p in enumerate(params):           # only the gradient addresses change from step to step
-                    g = p.grad
-                    if g.dtype != p.dtype or not g.is_contiguous():
-                        raise ffi.FusionLibraryError("FusedAdamW needs contiguous gradients of the parameter's dtype")
-                    grad_ptrs[i] = g.data_ptr()
+                self._refresh_grad_ptrs(bucket)
                 lr_dev = None
                 if capturable:
                     step, step_dev = 0, group["_step_dev"][bucket["device"]].data_ptr()
@@ -73,10 +100,53 @@ class FusedAdamW(torch.optim.Optimizer):
                     step, step_dev = bucket["step"], None
                 desc = ffi.AdamWDesc(bucket["dtype_code"], n, step, group["lr"], group["betas"][0], group["betas"][1], group["eps"],
                                      group["weight_decay"], group["grad_scale"], step_dev)
-                ffi.check(lib.ff_adamw_step_mixed(desc, bucket["state_code"], bucket["param_ptrs"], grad_ptrs, bucket["m_ptrs"], bucket["v_ptrs"],
-                                                  bucket["w_ptrs"], lr_dev, bucket["numels"], ffi.stream_handle(bucket["device"])),
-                          "ff_adamw_step_mixed")
+                if coef is None:
+                    ffi.check(lib.ff_adamw_step_mixed(desc, bucket["state_code"], bucket["param_ptrs"], grad_ptrs, bucket["m_ptrs"], bucket["v_ptrs"],
+                                                      bucket["w_ptrs"], lr_dev, bucket["numels"], ffi.stream_handle(bucket["device"])),
+                              "ff_adamw_step_mixed")
+                else:
+                    ffi.check(lib.ff_adamw_step_clipped(desc, bucket["state_code"], bucket["param_ptrs"], grad_ptrs, bucket["m_ptrs"], bucket["v_ptrs"],
+                                                        bucket["w_ptrs"], lr_dev, coef.data_ptr(), bucket["numels"], ffi.stream_handle(bucket["device"])),
+                              "ff_adamw_step_clipped")
         return loss
+
+    @staticmethod
+    def _refresh_grad_ptrs(bucket) -> None:
+        for i, p in enumerate(bucket["params"]):       # only the gradient addresses change from step to step
+            g = p.grad
+            if g.dtype != p.dtype or not g.is_contiguous():
+                raise ffi.FusionLibraryError("FusedAdamW needs contiguous gradients of the parameter's dtype")
+            bucket["grad_ptrs"][i] = g.data_ptr()
+
+    def _clip_coef(self, lib) -> Optional[torch.Tensor]:
+        """max_grad_norm: enqueue the global norm of every gradient of every group (grad_scale applied) and the clip coefficient; returns
+        the device scalar the AdamW launches of this step read.  No host synchronisation (capturable)."""
+        buckets = [(group, b) for gi, group in enumerate(self.param_groups) for b in self._buckets(gi, group)]
+        if not buckets:
+            return None
+        devices = {b["device"] for _, b in buckets}
+        if len(devices) > 1:
+            raise ValueError("FusedAdamW(max_grad_norm=...) needs every parameter on one device (the global norm is reduced on it)")
+        device = devices.pop()
+        slots = [int(lib.ff_grad_sumsq_partials(len(b["params"]), b["numels"])) for _, b in buckets]
+        clip = self._clip
+        if clip is None or clip["device"] != device:
+            clip = self._clip = dict(device=device, norm=torch.zeros((), dtype=torch.float32, device=device),
+                                     coef=torch.ones((), dtype=torch.float32, device=device),
+                                     sum=torch.zeros((), dtype=torch.float64, device=device), partials=None)
+        if clip["partials"] is None or clip["partials"].numel() < sum(slots):
+            clip["partials"] = torch.zeros(max(sum(slots), 1), dtype=torch.float32, device=device)
+        stream = ffi.stream_handle(device)
+        partials, total, off = clip["partials"], clip["partials"].numel(), 0
+        for (group, b), k in zip(buckets, slots):     # slots continue from bucket to bucket (dtypes, groups)
+            self._refresh_grad_ptrs(b)
+            ffi.check(lib.ff_grad_sumsq(b["dtype_code"], len(b["params"]), b["grad_ptrs"], b["numels"], float(group["grad_scale"] or 1.0),
+                                        partials.data_ptr() + 4 * off, total - off, stream), "ff_grad_sumsq")
+            off += k
+        ffi.check(lib.ff_grad_sumsq_reduce(partials.data_ptr(), off, clip["sum"].data_ptr(), 0, stream), "ff_grad_sumsq_reduce")
+        ffi.check(lib.ff_grad_clip_coef(clip["sum"].data_ptr(), self.max_grad_norm, clip["norm"].data_ptr(), clip["coef"].data_ptr(), stream),
+                  "ff_grad_clip_coef")
+        return clip["coef"]
 
     def sync_device_hyperparams(self) -> None:
         """capturable mode: copy `group["lr"]` into the device scalar the captured kernels read (call before replaying a graph)."""
@@ -199,3 +269,50 @@ class FusedAdamW(torch.optim.Optimizer):
             for k in ("_step_dev", "_lr_dev", "_lr_on_dev"):
                 g.pop(k, None)
         return out
+
+
+def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (norm_type 2) on the device: the total L2 norm of the gradients of `parameters` (fp32 0-dim tensor,
+    summed in fp32 per workgroup and in fp64 over workgroups, also for bf16 gradients) is returned, and every gradient is multiplied in
+    place by min(1, max_norm / (norm + 1e-6)).  A non-finite norm propagates as in torch; error_if_nonfinite=True raises instead (one host
+    synchronisation, as in torch).  Gradients: contiguous fp32 / bf16 on one device."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f"clip_grad_norm_ computes the L2 norm only (norm_type=2), got norm_type={norm_type}")
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    devices = {g.device for g in grads}
+    if len(devices) > 1:
+        raise ValueError("clip_grad_norm_ needs every gradient on one device")
+    ffi.require_cuda(*grads)
+    device = devices.pop()
+    lib = ffi.lib()
+    stream = ffi.stream_handle(device)
+    tables = []
+    for dt in (torch.float32, torch.bfloat16):
+        gs = [g for g in grads if g.dtype == dt]
+        if gs:
+            if not all(g.is_contiguous() for g in gs):
+                raise ffi.FusionLibraryError("clip_grad_norm_ needs contiguous gradients")
+            tables.append((ffi.dtype_code(dt), len(gs), ffi.ptr_array(gs), (C.c_longlong * len(gs))(*[g.numel() for g in gs])))
+    if sum(n for _, n, _, _ in tables) != len(grads):
+        raise ffi.FusionLibraryError("clip_grad_norm_ handles float32 and bfloat16 gradients")
+    slots = [int(lib.ff_grad_sumsq_partials(n, numels)) for _, n, _, numels in tables]
+    partials = torch.empty(max(sum(slots), 1), dtype=torch.float32, device=device)
+    total = torch.empty((), dtype=torch.float64, device=device)
+    norm = torch.empty((), dtype=torch.float32, device=device)
+    coef = torch.empty((), dtype=torch.float32, device=device)
+    off = 0
+    for (code, n, ptrs, numels), k in zip(tables, slots):
+        ffi.check(lib.ff_grad_sumsq(code, n, ptrs, numels, 1.0, partials.data_ptr() + 4 * off, partials.numel() - off, stream), "ff_grad_sumsq")
+        off += k
+    ffi.check(lib.ff_grad_sumsq_reduce(partials.data_ptr(), off, total.data_ptr(), 0, stream), "ff_grad_sumsq_reduce")
+    ffi.check(lib.ff_grad_clip_coef(total.data_ptr(), float(max_norm), norm.data_ptr(), coef.data_ptr(), stream), "ff_grad_clip_coef")
+    if error_if_nonfinite and not bool(torch.isfinite(norm)):
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be clipped. "
+                           "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    for code, n, ptrs, numels in tables:
+        ffi.check(lib.ff_scale_grads(code, n, ptrs, numels, coef.data_ptr(), stream), "ff_scale_grads")
+    return norm

@@ -45,7 +45,8 @@ enum { FF_DTYPE_F32 = 0, FF_DTYPE_BF16 = 1 };
 enum { FF_ACT_NONE = -1, FF_ACT_GELU = 0, FF_ACT_SQRELU = 1, FF_ACT_RELU = 2 }; /* utils.py:26-30 */
 
 int ff_version(void);          /* ABI version, bumped on any signature change (3: ff_gemm_desc.tile / .stages replace ff_gemm_set_tuning;
-                                * 4: ff_xattn_desc.sync, ff_xattn_sync_bytes / _status, ff_resampler_layer_* / _prologue_* / _epilogue_*) */
+                                * 4: ff_xattn_desc.sync, ff_xattn_sync_bytes / _status, ff_resampler_layer_* / _prologue_* / _epilogue_*;
+                                * 5: gradient clipping: ff_grad_sumsq*, ff_grad_clip_coef, ff_scale_grads, ff_adamw_step_clipped) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -383,6 +384,31 @@ int ff_adamw_step(const ff_adamw_desc* d, void* const* params, const void* const
  * effective when the launch is replayed from a captured HIP graph. */
 int ff_adamw_step_mixed(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, void* const* exp_avg,
                         void* const* exp_avg_sq, float* const* master, const float* lr_dev, const long long* numels, ff_stream_t stream);
+/* ff_adamw_step_mixed with every gradient multiplied by the device scalar *grad_coef as it is read (one fp32 factor grad_scale * *grad_coef):
+ * gradient clipping by global norm (ABI 5) with the coefficient of ff_grad_clip_coef, without touching the gradients in memory. */
+int ff_adamw_step_clipped(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, void* const* exp_avg,
+                          void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef, const long long* numels,
+                          ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Gradient clipping by global L2 norm (ABI 5): torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2), which the reference's
+ * HF Trainer applies before every optimizer step (TrainingArguments.max_grad_norm, default 1.0).  Everything stays on the device:
+ *   ff_grad_sumsq          sum of squares of (scale * g) over n_tensors contiguous gradients of one dtype; ONE fp32 partial per
+ *                          workgroup in partials[0 .. ff_grad_sumsq_partials(n_tensors, numels) - 1] (fixed slots, no atomics: the total
+ *                          is reproducible bit for bit).  Offset `partials` to continue the slots of an earlier call (another dtype,
+ *                          another bucket); n_partials is the room left there (FF_ERR_WORKSPACE if too small).
+ *   ff_grad_sumsq_reduce   one workgroup: *sum = (accumulate ? *sum : 0) + the n_partials partials, added in fp64 in a fixed order.  A
+ *                          data-parallel caller all-reduces *sum between this and the next call.
+ *   ff_grad_clip_coef      *norm = sqrt(*sum) (fp32), *coef = min(1, max_norm / (*norm + 1e-6)); either output may be null.  A non-finite
+ *                          norm propagates as in torch (NaN coefficient for a NaN norm, 0 for an infinite one).
+ *   ff_scale_grads         g *= *coef in place over n_tensors contiguous gradients of one dtype (fp32 math).
+ * ------------------------------------------------------------------------------------------------------ */
+long long ff_grad_sumsq_partials(int n_tensors, const long long* numels);
+int ff_grad_sumsq(int dtype, int n_tensors, const void* const* grads, const long long* numels, float scale, float* partials,
+                  long long n_partials, ff_stream_t stream);
+int ff_grad_sumsq_reduce(const float* partials, long long n_partials, double* sum, int accumulate, ff_stream_t stream);
+int ff_grad_clip_coef(const double* sum, float max_norm, float* norm, float* coef, ff_stream_t stream);
+int ff_scale_grads(int dtype, int n_tensors, void* const* grads, const long long* numels, const float* coef, ff_stream_t stream);
 
 
 /* ------------------------------------------------------------------------------------------------------

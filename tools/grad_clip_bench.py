@@ -1,0 +1,75 @@
+"""Cost of gradient clipping (max_grad_norm) in the captured training step at a bench.py workload (default: config B, the headline).
+
+    python tools/grad_clip_bench.py [--config B] [--rounds 7] [--steps 10] [--max-grad-norm 1.0] [--only clipped]
+
+Builds the model through bench.build_model, captures two GraphedTrainSteps on it - FusedAdamW(capturable=True) without and with
+max_grad_norm - and replays them alternately (`--rounds` rounds of `--steps` replays each, HIP events around each block), so that
+clock and thermal drift fall on both alike.  Prints one JSON line: median ms per step of each, their difference, and the trainable
+gradient bytes one sum-of-squares sweep reads.  `--only clipped` replays just the clipped step (for a rocprofv3 --kernel-trace --stats
+run that isolates the clipping kernels)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="B")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--max-grad-norm", type=float, default=1.0)
+    ap.add_argument("--only", default="", choices=["", "clipped"])
+    a = ap.parse_args()
+    saved, sys.argv = sys.argv, [sys.argv[0], "--config", a.config]
+    import bench
+    args = bench.parse()
+    sys.argv = saved
+    from flamingo_mini_amd import FusedAdamW, GraphedTrainStep, ffi
+    ffi.lib()
+    device = torch.device("cuda", 0)
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    if args.stock_tuning != "off" and dtype == torch.bfloat16:
+        from flamingo_mini_amd.backbones import load_stock_gemm_tuning
+        load_stock_gemm_tuning()
+    model, cfg = bench.build_model(args, device, dtype)
+    batch = bench.synthetic_batch(args, cfg, device, dtype, 0)
+    model.set_launch_structure(hoist_kv=args.hoist_kv == "on")
+    params = list(model.parameters_trainable())
+    grad_bytes = sum(p.numel() * p.element_size() for p in params)
+    kinds = ["clipped"] if a.only else ["plain", "clipped"]
+    steps, opts = {}, {}
+    for kind in kinds:
+        opts[kind] = FusedAdamW(params, lr=1e-4, capturable=True, max_grad_norm=a.max_grad_norm if kind == "clipped" else None)
+        steps[kind] = GraphedTrainStep(model, opts[kind], batch, warmup=2)
+    times = {k: [] for k in kinds}
+    for _ in range(a.rounds):
+        for kind in kinds:
+            steps[kind]()                                  # (one untimed replay after switching)
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(a.steps):
+                steps[kind]()
+            t1.record()
+            t1.synchronize()
+            times[kind].append(t0.elapsed_time(t1) / a.steps)
+    for s in steps.values():
+        s.close()
+    out = dict(config=a.config, trainable_params=sum(p.numel() for p in params), grad_bytes=grad_bytes, max_grad_norm=a.max_grad_norm,
+               rounds=a.rounds, steps_per_round=a.steps, grad_norm=float(opts["clipped"].grad_norm))
+    for kind in kinds:
+        out[f"{kind}_ms_median"] = round(statistics.median(times[kind]), 4)
+        out[f"{kind}_ms_all"] = [round(t, 4) for t in times[kind]]
+    if not a.only:
+        out["delta_ms_median"] = round(statistics.median([c - p for c, p in zip(times["clipped"], times["plain"])]), 4)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
