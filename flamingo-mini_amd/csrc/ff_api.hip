@@ -46,13 +46,29 @@ static LnArgs ln_args(int dtype, int rows, int cols, RowMap x, RowMap y, RowMap 
 // =====================================================================================================
 struct RsDims {
     int dt, Bn, T, v, D, F, q, H, dh, inner, ffi, R, depth, nte, act;
-    size_t es;
+    int Mq, Mkv, Mf;                    // rows over the batch: latents, cat(media, latents), media
+    size_t es, attn_ws;                 // element size; bytes of the attention backward's workspace
     float scale;
+    RowMap pD, pI, pF;                  // plain rows of width D / inner / ffi
+    RowMap lat_bcast;                   // latents (q, D) repeated over the batch (:179)
+    RowMap kv_media, kv_lat;            // media rows inside kv_in; latent rows inside kv_in (base + F*D)
     explicit RsDims(const ff_resampler_desc& d) {
         dt = d.dtype; Bn = d.batch; T = d.n_frames; v = d.n_tokens; D = d.dim; F = T * v; q = d.num_latents;
         H = d.heads; dh = d.dim_head; inner = H * dh; ffi = d.ff_mult * D; R = F + q; depth = d.depth;
         nte = d.num_time_embeds; act = d.act; es = dtype_size(dt); scale = 1.0f / sqrtf((float)dh);
+        Mq = Bn * q; Mkv = Bn * R; Mf = Bn * F; attn_ws = (size_t)Bn * H * q * 4;
+        pD = plain_rows(D); pI = plain_rows(inner); pF = plain_rows(ffi);
+        lat_bcast = RowMap{D, 0, q};
+        kv_media = RowMap{D, (long long)R * D, F};
+        kv_lat = RowMap{D, (long long)R * D, q};
     }
+    LnArgs ln_latents() const { return ln_args(dt, Mq, D, pD, pD, pD); }      // a LayerNorm over plain latent rows
+    LnArgs ln_media(RowMap y) const {                                         // LayerNorm(x_f + time_pos_emb) (:166, :52)
+        LnArgs a = ln_args(dt, Mf, D, pD, y, pD);
+        a.add_rows_per_seg = F; a.add_div = v;
+        return a;
+    }
+    template <typename P> P* kv_latent_rows(P* kv) const { return (P*)((char*)kv + (size_t)F * D * es); }
 };
 struct RsLayerSaved {
     void *x_in, *kv_in, *Qs, *K, *V, *O, *x_mid, *xn_f, *Hpre, *Aact;
@@ -64,28 +80,32 @@ struct RsSaved {
     void* x_last;
     RsLayerSaved L[kMaxDepth];
 };
+// what one layer keeps for its backward, apart from its input (the stack-level call keeps that itself, the layer-wise caller owns it)
+static void rs_take_layer_saved(const RsDims& s, Arena& a, RsLayerSaved& L) {
+    const size_t rows_q = s.Mq, rows_kv = s.Mkv;
+    L.mean_l = a.take<float>(rows_q * 4);
+    L.rstd_l = a.take<float>(rows_q * 4);
+    L.kv_in = a.take(rows_kv * s.D * s.es);
+    L.Qs = a.take(rows_q * s.inner * s.es);
+    L.K = a.take(rows_kv * s.inner * s.es);
+    L.V = a.take(rows_kv * s.inner * s.es);
+    L.lse = a.take<float>((size_t)s.Bn * s.H * s.q * 4);
+    L.O = a.take(rows_q * s.inner * s.es);
+    L.x_mid = a.take(rows_q * s.D * s.es);
+    L.mean_f = a.take<float>(rows_q * 4);
+    L.rstd_f = a.take<float>(rows_q * 4);
+    L.xn_f = a.take(rows_q * s.D * s.es);
+    L.Hpre = a.take(rows_q * s.ffi * s.es);
+    L.Aact = a.take(rows_q * s.ffi * s.es);
+}
 static size_t rs_saved_layout(const RsDims& s, void* base, size_t cap, RsSaved& o) {
     Arena a(base, cap);
-    const size_t rows_q = (size_t)s.Bn * s.q, rows_kv = (size_t)s.Bn * s.R;
-    o.mean_m = a.take<float>((size_t)s.Bn * s.F * 4);
-    o.rstd_m = a.take<float>((size_t)s.Bn * s.F * 4);
+    const size_t rows_q = s.Mq;
+    o.mean_m = a.take<float>((size_t)s.Mf * 4);
+    o.rstd_m = a.take<float>((size_t)s.Mf * 4);
     for (int l = 0; l < s.depth; l++) {
-        RsLayerSaved& L = o.L[l];
-        L.x_in = l == 0 ? nullptr : a.take(rows_q * s.D * s.es);
-        L.mean_l = a.take<float>(rows_q * 4);
-        L.rstd_l = a.take<float>(rows_q * 4);
-        L.kv_in = a.take(rows_kv * s.D * s.es);
-        L.Qs = a.take(rows_q * s.inner * s.es);
-        L.K = a.take(rows_kv * s.inner * s.es);
-        L.V = a.take(rows_kv * s.inner * s.es);
-        L.lse = a.take<float>((size_t)s.Bn * s.H * s.q * 4);
-        L.O = a.take(rows_q * s.inner * s.es);
-        L.x_mid = a.take(rows_q * s.D * s.es);
-        L.mean_f = a.take<float>(rows_q * 4);
-        L.rstd_f = a.take<float>(rows_q * 4);
-        L.xn_f = a.take(rows_q * s.D * s.es);
-        L.Hpre = a.take(rows_q * s.ffi * s.es);
-        L.Aact = a.take(rows_q * s.ffi * s.es);
+        o.L[l].x_in = l == 0 ? nullptr : a.take(rows_q * s.D * s.es);
+        rs_take_layer_saved(s, a, o.L[l]);
     }
     o.x_last = a.take(rows_q * s.D * s.es);
     o.mean_o = a.take<float>(rows_q * 4);
@@ -93,58 +113,80 @@ static size_t rs_saved_layout(const RsDims& s, void* base, size_t cap, RsSaved& 
     return align_up(a.used);
 }
 
-// Backward keeps what the weight-gradient GEMMs need (d x at each layer's output, d x_mid, d H, d Qs, d K, d V) for EVERY layer:
-// the weight gradients are not on the critical path, so they run after the data-gradient chain as grouped launches over up to
-// kGemmMaxZ layers (same shapes, different operands) - one chip-filling launch instead of four that each fill a third of it.
-struct RsLayerStash {
-    void *dx_out, *dx_mid, *dH, *dQs, *dK, *dV;
-};
-struct RsScratch {
-    void *dx0, *dxn, *dO, *dkv, *dln, *dxf, *ws;
-    RsLayerStash L[kMaxDepth];
-    float* lnp[3 * kMaxDepth + 1];     // partials of the postponed LayerNorm-backward reductions (null: not deferrable at this width)
-    size_t ws_bytes;
-};
 static size_t rs_ws_bytes(const RsDims& s) {
-    const int Mq = s.Bn * s.q, Mkv = s.Bn * s.R;
     size_t w = 0;
     auto g = [&](int M, int N, int K, int nz) { w = std::max(w, gemm_workspace_bytes(s.dt, M, N, K, nz, 0)); };
-    g(Mq, s.inner, s.D, 1); g(Mkv, s.inner, s.D, 2); g(Mq, s.D, s.inner, 1); g(Mq, s.ffi, s.D, 1); g(Mq, s.D, s.ffi, 1);   // fwd
+    g(s.Mq, s.inner, s.D, 1); g(s.Mkv, s.inner, s.D, 2); g(s.Mq, s.D, s.inner, 1); g(s.Mq, s.ffi, s.D, 1); g(s.Mq, s.D, s.ffi, 1);   // fwd
     for (int nz = 1; nz <= 4; nz++) {                                                                                       // grouped wgrad (kRsGroup)
-        g(s.D, s.ffi, Mq, nz); g(s.ffi, s.D, Mq, nz); g(s.D, s.inner, Mq, nz); g(s.inner, s.D, Mq, nz); g(s.inner, s.D, Mkv, nz);
+        g(s.D, s.ffi, s.Mq, nz); g(s.ffi, s.D, s.Mq, nz); g(s.D, s.inner, s.Mq, nz); g(s.inner, s.D, s.Mq, nz); g(s.inner, s.D, s.Mkv, nz);
     }
-    g(Mkv, s.D, s.inner, 1);
-    w = std::max(w, layernorm_bwd_workspace(s.Bn * s.F, s.D));
-    w = std::max(w, layernorm_bwd_workspace(Mq, s.D));
-    w = std::max(w, rows_reduce_workspace(Mq, s.D, s.q, 1));
-    w = std::max(w, rows_reduce_workspace(s.Bn * s.F, s.D, s.F, s.v));
-    return align_up(w) + align_up((size_t)s.Bn * s.H * s.q * 4);
+    g(s.Mkv, s.D, s.inner, 1);
+    w = std::max(w, layernorm_bwd_workspace(s.Mf, s.D));
+    w = std::max(w, layernorm_bwd_workspace(s.Mq, s.D));
+    w = std::max(w, rows_reduce_workspace(s.Mq, s.D, s.q, 1));
+    w = std::max(w, rows_reduce_workspace(s.Mf, s.D, s.F, s.v));
+    return align_up(w) + align_up(s.attn_ws);
 }
+// The scratch of a layer's launches, the same in both call forms.  Per call: the workspace (GEMM / LayerNorm / reduce workspace in front,
+// the attention backward's behind it) and four gradients that only the data-gradient chain itself reads.  Per layer: the gradients that
+// the weight-gradient GEMMs read as well, and the partials of the layer's three postponed LayerNorm-backward reductions.
+struct RsChain {
+    void *ws, *dxn, *dO, *dkv, *dln;
+    size_t ws_bytes, gws;               // all of ws (what the forward launches get); ws without the attention tail (the backward launches)
+    float* attn_ws;
+};
+struct RsLayerGrads {
+    void *dx_mid, *dH, *dQs, *dK, *dV;
+};
+static void rs_take_ws(const RsDims& s, Arena& a, RsChain& c) {
+    c.ws_bytes = rs_ws_bytes(s);
+    c.ws = a.take(c.ws_bytes);
+    c.gws = c.ws_bytes - align_up(s.attn_ws);
+    c.attn_ws = c.ws ? (float*)((char*)c.ws + c.gws) : nullptr;
+}
+static void rs_take_chain(const RsDims& s, Arena& a, RsChain& c) {
+    c.dxn = a.take((size_t)s.Mq * s.D * s.es);
+    c.dO = a.take((size_t)s.Mq * s.inner * s.es);
+    c.dkv = a.take((size_t)s.Mkv * s.D * s.es);
+    c.dln = a.take((size_t)s.Mq * s.D * s.es);
+}
+static void rs_take_layer_grads(const RsDims& s, Arena& a, RsLayerGrads& g) {
+    g.dx_mid = a.take((size_t)s.Mq * s.D * s.es);
+    g.dH = a.take((size_t)s.Mq * s.ffi * s.es);
+    g.dQs = a.take((size_t)s.Mq * s.inner * s.es);
+    g.dK = a.take((size_t)s.Mkv * s.inner * s.es);
+    g.dV = a.take((size_t)s.Mkv * s.inner * s.es);
+}
+// lnp[0] ff norm, [1] norm_latents, [2] norm_media of one layer (null: not deferrable at this width, the chain finishes them on the spot)
+static void rs_take_ln_partials(const RsDims& s, Arena& a, bool deferrable, float** lnp) {
+    for (int i = 0; i < 3; i++) lnp[i] = deferrable ? a.take<float>(layernorm_bwd_partial_bytes(i == 2 ? s.Mf : s.Mq, s.D)) : nullptr;
+}
+
+// The stack-level backward keeps what the weight-gradient GEMMs need (d x at each layer's output, d x_mid, d H, d Qs, d K, d V) for EVERY
+// layer: the weight gradients are not on the critical path, so they run after the data-gradient chain as grouped launches over up to
+// kGemmMaxZ layers (same shapes, different operands) - one chip-filling launch instead of four that each fill a third of it.
+struct RsScratch {
+    RsChain c;
+    void *dx0, *dxf;
+    void* dx_out[kMaxDepth];
+    RsLayerGrads L[kMaxDepth];
+    float* lnp[3 * kMaxDepth + 1];      // [3l .. 3l+2] layer l (rs_take_ln_partials); [3 depth] final norm
+};
 static size_t rs_scratch_layout(const RsDims& s, void* base, size_t cap, bool bwd, RsScratch& o) {
     Arena a(base, cap);
-    const size_t rows_q = (size_t)s.Bn * s.q, rows_kv = (size_t)s.Bn * s.R;
-    o.ws_bytes = rs_ws_bytes(s);
-    o.ws = a.take(o.ws_bytes);
+    rs_take_ws(s, a, o.c);
     if (bwd) {
-        o.dx0 = a.take(rows_q * s.D * s.es);        // d (latents broadcast over the batch)
-        o.dxn = a.take(rows_q * s.D * s.es);
-        o.dO = a.take(rows_q * s.inner * s.es);
-        o.dkv = a.take(rows_kv * s.D * s.es);
-        o.dln = a.take(rows_q * s.D * s.es);
-        o.dxf = a.take((size_t)s.Bn * s.F * s.D * s.es);
+        o.dx0 = a.take((size_t)s.Mq * s.D * s.es);        // d (latents broadcast over the batch)
+        rs_take_chain(s, a, o.c);
+        o.dxf = a.take((size_t)s.Mf * s.D * s.es);
         for (int l = 0; l < s.depth; l++) {
-            RsLayerStash& L = o.L[l];
-            L.dx_out = a.take(rows_q * s.D * s.es);
-            L.dx_mid = a.take(rows_q * s.D * s.es);
-            L.dH = a.take(rows_q * s.ffi * s.es);
-            L.dQs = a.take(rows_q * s.inner * s.es);
-            L.dK = a.take(rows_kv * s.inner * s.es);
-            L.dV = a.take(rows_kv * s.inner * s.es);
+            o.dx_out[l] = a.take((size_t)s.Mq * s.D * s.es);
+            rs_take_layer_grads(s, a, o.L[l]);
         }
         static const int defer_ln = dbg_switch("FF_DEFER_LN", 1);
         const bool lnd = defer_ln != 0 && layernorm_bwd_deferrable(s.dt, s.D);
-        for (int i = 0; i < 3 * s.depth + 1; i++)       // [3l] ff norm, [3l+1] norm_latents, [3l+2] norm_media of layer l; [3 depth] final norm
-            o.lnp[i] = lnd ? a.take<float>(layernorm_bwd_partial_bytes(i % 3 == 2 ? s.Bn * s.F : (int)rows_q, s.D)) : nullptr;
+        for (int l = 0; l < s.depth; l++) rs_take_ln_partials(s, a, lnd, o.lnp + 3 * l);
+        o.lnp[3 * s.depth] = lnd ? a.take<float>(layernorm_bwd_partial_bytes(s.Mq, s.D)) : nullptr;
     }
     return align_up(a.used);
 }
@@ -170,6 +212,90 @@ static ff_attn_desc rs_attn_desc(const RsDims& s) {
     return a;
 }
 
+// ---- the launches, each written once; the call forms below pass their own buffers in ----
+// statistics of x_f + time_pos_emb, shared by the norm_media of every layer (:166, :52)
+static int rs_media_stats(const RsDims& s, const void* x_f, const void* tpe, float* mean_m, float* rstd_m, hipStream_t st) {
+    return layernorm_fwd(s.ln_media(s.pD), x_f, tpe, nullptr, nullptr, nullptr, mean_m, rstd_m, st);
+}
+
+// One layer's forward (:181-183).  p: the layer's twelve parameters; x_in is read through x_map (lat_bcast: the latents parameter itself).
+static int rs_layer_forward(const RsDims& s, const void* const* p, const void* x_f, const void* tpe, float* mean_m, float* rstd_m, const void* x_in,
+                            RowMap x_map, void* x_out, const RsLayerSaved& L, void* ws, size_t ws_bytes, hipStream_t st) {
+    const RowMap pD = s.pD, pI = s.pI, pF = s.pF;
+    void* kv_lat_base = s.kv_latent_rows(L.kv_in);
+    {   // norm_media -> media rows of kv_in (:52,65)
+        LnArgs a = s.ln_media(s.kv_media);
+        a.stats_given = 1;
+        FF_TRY(layernorm_fwd(a, x_f, tpe, p[0], p[1], L.kv_in, mean_m, rstd_m, st));
+    }
+    // norm_latents -> latent rows of kv_in (:53,65)
+    FF_TRY(layernorm_fwd(ln_args(s.dt, s.Mq, s.D, x_map, s.kv_lat, pD), x_in, nullptr, p[2], p[3], kv_lat_base, L.mean_l, L.rstd_l, st));
+    // q = to_q(latents) * scale (:57,79)
+    FF_TRY(Gemm(s.dt, s.Mq, s.inner, s.D).a(0, s.kv_lat).b(0, pD).c(pI).scale(s.scale).problem(kv_lat_base, p[4], L.Qs).run(ws, ws_bytes, st));
+    // k, v = to_k / to_v (cat(media, latents)) (:69-70), one grouped launch
+    FF_TRY(Gemm(s.dt, s.Mkv, s.inner, s.D).a(0, pD).b(0, pD).c(pI).problem(L.kv_in, p[5], L.K).problem(L.kv_in, p[6], L.V).run(ws, ws_bytes, st));
+    FF_TRY(attention_fwd(rs_attn_desc(s), L.Qs, L.K, L.V, nullptr, L.O, L.lse, st));   // :85-92
+    // x = x + to_out(o) (:96, :182)
+    FF_TRY(Gemm(s.dt, s.Mq, s.D, s.inner).a(0, pI).b(0, pI).c(pD).res_map(x_map).problem(L.O, p[7], L.x_mid, nullptr, nullptr, x_in).run(ws, ws_bytes, st));
+    // x = x + ffw(x) (:183; utils.py:45-50)
+    FF_TRY(layernorm_fwd(s.ln_latents(), L.x_mid, nullptr, p[8], p[9], L.xn_f, L.mean_f, L.rstd_f, st));
+    FF_TRY(Gemm(s.dt, s.Mq, s.ffi, s.D).a(0, pD).b(0, pD).c(pF).act(s.act).problem(L.xn_f, p[10], L.Aact, L.Hpre).run(ws, ws_bytes, st));
+    return Gemm(s.dt, s.Mq, s.D, s.ffi).a(0, pF).b(0, pF).c(pD).problem(L.Aact, p[11], x_out, nullptr, nullptr, L.x_mid).run(ws, ws_bytes, st);
+}
+
+static int rs_final_norm(const RsDims& s, const void* x_last, const void* gamma, const void* beta, void* out, float* mean, float* rstd, hipStream_t st) {
+    return layernorm_fwd(s.ln_latents(), x_last, nullptr, gamma, beta, out, mean, rstd, st);   // :187
+}
+
+// A LayerNorm backward on the data-gradient chain.  The final reduction of d gamma / d beta is not on that chain: with a `partial` buffer
+// the partials stay there and `pending` describes them for layernorm_bwd_finish (its .partial stays null if the unfused path had to run
+// after all); without one everything finishes on the spot, in the workspace.
+static int rs_ln_bwd(const RsChain& W, float* partial, LnPending* pending, const LnArgs& a, const void* dy, const void* x, const void* add,
+                     const void* gamma, const float* mean, const float* rstd, void* dx, const void* dx_res, void* dg, void* db, hipStream_t st) {
+    if (partial)
+        return layernorm_bwd(a, dy, x, add, gamma, mean, rstd, dx, dx_res, dg, db, partial, layernorm_bwd_partial_bytes(a.rows, a.cols), st, nullptr, pending);
+    return layernorm_bwd(a, dy, x, add, gamma, mean, rstd, dx, dx_res, dg, db, W.ws, W.gws, st);
+}
+
+// One layer's data-gradient chain (the critical path of backward): d x_out -> d x_in, d x_f (+= dx_f_res if given), and the six LayerNorm
+// parameter gradients g[0..3], g[8..9] (or their partials, lnp / ln_sets as in rs_take_ln_partials).  The operands of the layer's
+// weight-gradient GEMMs are left in T; those GEMMs and layernorm_bwd_finish are the caller's, each call form its own way.
+static int rs_layer_backward(const RsDims& s, const void* const* p, void* const* g, const void* x_f, const void* tpe, const float* mean_m,
+                             const float* rstd_m, const void* x_in, RowMap x_map, const RsLayerSaved& L, const void* dx_out, void* dx_in,
+                             void* dx_f, const void* dx_f_res, const RsChain& W, const RsLayerGrads& T, float* const* lnp, LnPending* ln_sets,
+                             hipStream_t st) {
+    const RowMap pD = s.pD, pI = s.pI, pF = s.pF;
+    // ---- FeedForward backward (x_out = x_mid + W3 act(W1 LN(x_mid))) ----
+    FF_TRY(Gemm(s.dt, s.Mq, s.ffi, s.D).a(0, pD).b(1, pF).c(pF).act_bwd(s.act).problem(dx_out, p[11], T.dH, nullptr, L.Hpre).run(W.ws, W.gws, st));
+    FF_TRY(Gemm(s.dt, s.Mq, s.D, s.ffi).a(0, pF).b(1, pD).c(pD).problem(T.dH, p[10], W.dxn).run(W.ws, W.gws, st));
+    FF_TRY(rs_ln_bwd(W, lnp[0], &ln_sets[0], s.ln_latents(), W.dxn, L.x_mid, nullptr, p[8], L.mean_f, L.rstd_f, T.dx_mid, dx_out, g[8], g[9], st));   // d x_mid
+    // ---- attention backward (x_mid = x_in + Wo O) ----
+    FF_TRY(Gemm(s.dt, s.Mq, s.inner, s.D).a(0, pD).b(1, pI).c(pI).problem(T.dx_mid, p[7], W.dO).run(W.ws, W.gws, st));
+    FF_TRY(attention_bwd(rs_attn_desc(s), L.Qs, L.K, L.V, nullptr, L.O, W.dO, L.lse, T.dQs, T.dK, T.dV, W.attn_ws, s.attn_ws, st));
+    // d kv_in = dK Wk + dV Wv
+    FF_TRY(Gemm(s.dt, s.Mkv, s.D, s.inner).a(0, pI).b(1, pD).c(pD).problem(T.dK, p[5], W.dkv).run(W.ws, W.gws, st));
+    FF_TRY(Gemm(s.dt, s.Mkv, s.D, s.inner).a(0, pI).b(1, pD).c(pD).problem(T.dV, p[6], W.dkv, nullptr, nullptr, W.dkv).run(W.ws, W.gws, st));
+    // d LN(latents) = scale * dQs Wq + d kv_in[latent rows]
+    FF_TRY(Gemm(s.dt, s.Mq, s.D, s.inner).a(0, pI).b(1, pD).c(pD).res_map(s.kv_lat).scale(s.scale)
+               .problem(T.dQs, p[4], W.dln, nullptr, nullptr, s.kv_latent_rows(W.dkv)).run(W.ws, W.gws, st));
+    // norm_latents backward, accumulated onto the residual path: d x_in
+    FF_TRY(rs_ln_bwd(W, lnp[1], &ln_sets[1], ln_args(s.dt, s.Mq, s.D, x_map, pD, pD), W.dln, x_in, nullptr, p[2], L.mean_l, L.rstd_l, dx_in, T.dx_mid, g[2],
+                     g[3], st));
+    // norm_media backward: d x_f accumulates over the layers (needed for d time_pos_emb even with CLIP frozen)
+    return rs_ln_bwd(W, lnp[2], &ln_sets[2], s.ln_media(s.kv_media), W.dkv, x_f, tpe, p[0], mean_m, rstd_m, dx_f, dx_f_res, g[0], g[1], st);
+}
+
+// d latents = sum over the batch of d x_0 (:179);  d time_pos_emb[t] = sum_{b, n} d x_f[b, t, n] (:166)
+static int rs_input_grads(const RsDims& s, const void* dx0, const void* dxf, void* d_latents, void* d_tpe, void* ws, size_t ws_bytes, hipStream_t st) {
+    FF_TRY(rows_reduce(s.dt, s.Mq, s.D, s.pD, s.q, 1, dx0, d_latents, ws, ws_bytes, st));
+    // d time_pos_emb rows of frames the batch does not have: exact zeros.  A kernel, not hipMemsetAsync: with the memset, replays of a
+    // captured training step left int32-looking bytes of some other buffer in those rows (tests/test_hip_bounds.py::
+    // test_unused_time_embedding_gradient_rows_are_zero, graphed and piecewise); a launch on the stream keeps its order and the zeros.
+    if (s.nte > s.T) FF_TRY(zero_bytes((char*)d_tpe + (size_t)s.T * s.D * s.es, (size_t)(s.nte - s.T) * s.D * s.es, st));
+    return rows_reduce(s.dt, s.Mf, s.D, s.pD, s.F, s.v, dxf, d_tpe, ws, ws_bytes, st);
+}
+
+// ---- the stack-level call: all layers in one call ----
 static int resampler_fwd(const ff_resampler_desc* d, const void* x_f, const void* const* P, void* out, void* saved, size_t saved_bytes,
                          void* scratch, size_t scratch_bytes, hipStream_t st) {
     FF_TRY(rs_check(d));
@@ -179,47 +305,15 @@ static int resampler_fwd(const ff_resampler_desc* d, const void* x_f, const void
     RsScratch W;
     FF_CHECK(rs_saved_layout(s, saved, saved_bytes, S) <= saved_bytes, FF_ERR_WORKSPACE, "resampler_fwd: saved buffer too small");
     FF_CHECK(rs_scratch_layout(s, scratch, scratch_bytes, false, W) <= scratch_bytes, FF_ERR_WORKSPACE, "resampler_fwd: scratch too small");
-    const int Mq = s.Bn * s.q, Mkv = s.Bn * s.R, Mf = s.Bn * s.F;
-    const RowMap pD = plain_rows(s.D), pI = plain_rows(s.inner), pF = plain_rows(s.ffi);
-    const RowMap lat_bcast = RowMap{s.D, 0, s.q};                                   // latents (q, D) repeated over the batch (:179)
-    const RowMap kv_media = RowMap{s.D, (long long)s.R * s.D, s.F};                // media rows inside kv_in
-    const RowMap kv_lat = RowMap{s.D, (long long)s.R * s.D, s.q};                  // latent rows inside kv_in (base + F*D)
     const void *latents = P[0], *tpe = P[1];
-
-    {   // statistics of x_f + time_pos_emb, shared by the norm_media of every layer (:166, :52)
-        LnArgs a = ln_args(s.dt, Mf, s.D, pD, pD, pD);
-        a.add_rows_per_seg = s.F; a.add_div = s.v;
-        FF_TRY(layernorm_fwd(a, x_f, tpe, nullptr, nullptr, nullptr, S.mean_m, S.rstd_m, st));
-    }
+    FF_TRY(rs_media_stats(s, x_f, tpe, S.mean_m, S.rstd_m, st));
     for (int l = 0; l < s.depth; l++) {
         const void* const* p = P + FF_RESAMPLER_GLOBAL_PARAMS + FF_RESAMPLER_LAYER_PARAMS * l;
-        RsLayerSaved& L = S.L[l];
-        const void* x_in = l == 0 ? latents : L.x_in;
-        const RowMap x_map = l == 0 ? lat_bcast : pD;
         void* x_next = l + 1 < s.depth ? S.L[l + 1].x_in : S.x_last;
-        char* kv_lat_base = (char*)L.kv_in + (size_t)s.F * s.D * s.es;
-        {   // norm_media -> media rows of kv_in (:52,65)
-            LnArgs a = ln_args(s.dt, Mf, s.D, pD, kv_media, pD);
-            a.add_rows_per_seg = s.F; a.add_div = s.v; a.stats_given = 1;
-            FF_TRY(layernorm_fwd(a, x_f, tpe, p[0], p[1], L.kv_in, S.mean_m, S.rstd_m, st));
-        }
-        {   // norm_latents -> latent rows of kv_in (:53,65)
-            LnArgs a = ln_args(s.dt, Mq, s.D, x_map, kv_lat, pD);
-            FF_TRY(layernorm_fwd(a, x_in, nullptr, p[2], p[3], kv_lat_base, L.mean_l, L.rstd_l, st));
-        }
-        // q = to_q(latents) * scale (:57,79)
-        FF_TRY(Gemm(s.dt, Mq, s.inner, s.D).a(0, kv_lat).b(0, pD).c(pI).scale(s.scale).problem(kv_lat_base, p[4], L.Qs).run(W.ws, W.ws_bytes, st));
-        // k, v = to_k / to_v (cat(media, latents)) (:69-70), one grouped launch
-        FF_TRY(Gemm(s.dt, Mkv, s.inner, s.D).a(0, pD).b(0, pD).c(pI).problem(L.kv_in, p[5], L.K).problem(L.kv_in, p[6], L.V).run(W.ws, W.ws_bytes, st));
-        FF_TRY(attention_fwd(rs_attn_desc(s), L.Qs, L.K, L.V, nullptr, L.O, L.lse, st));   // :85-92
-        // x = x + to_out(o) (:96, :182)
-        FF_TRY(Gemm(s.dt, Mq, s.D, s.inner).a(0, pI).b(0, pI).c(pD).res_map(x_map).problem(L.O, p[7], L.x_mid, nullptr, nullptr, x_in).run(W.ws, W.ws_bytes, st));
-        // x = x + ffw(x) (:183; utils.py:45-50)
-        FF_TRY(layernorm_fwd(ln_args(s.dt, Mq, s.D, pD, pD, pD), L.x_mid, nullptr, p[8], p[9], L.xn_f, L.mean_f, L.rstd_f, st));
-        FF_TRY(Gemm(s.dt, Mq, s.ffi, s.D).a(0, pD).b(0, pD).c(pF).act(s.act).problem(L.xn_f, p[10], L.Aact, L.Hpre).run(W.ws, W.ws_bytes, st));
-        FF_TRY(Gemm(s.dt, Mq, s.D, s.ffi).a(0, pF).b(0, pF).c(pD).problem(L.Aact, p[11], x_next, nullptr, nullptr, L.x_mid).run(W.ws, W.ws_bytes, st));
+        FF_TRY(rs_layer_forward(s, p, x_f, tpe, S.mean_m, S.rstd_m, l == 0 ? latents : S.L[l].x_in, l == 0 ? s.lat_bcast : s.pD, x_next, S.L[l], W.c.ws,
+                                W.c.ws_bytes, st));
     }
-    return layernorm_fwd(ln_args(s.dt, Mq, s.D, pD, pD, pD), S.x_last, nullptr, P[2], P[3], out, S.mean_o, S.rstd_o, st);   // :187
+    return rs_final_norm(s, S.x_last, P[2], P[3], out, S.mean_o, S.rstd_o, st);
 }
 
 static int resampler_bwd(const ff_resampler_desc* d, const void* x_f, const void* const* P, const void* dout, const void* saved,
@@ -231,107 +325,64 @@ static int resampler_bwd(const ff_resampler_desc* d, const void* x_f, const void
     RsScratch W;
     FF_CHECK(rs_saved_layout(s, (void*)saved, saved_bytes, S) <= saved_bytes, FF_ERR_WORKSPACE, "resampler_bwd: saved buffer too small");
     FF_CHECK(rs_scratch_layout(s, scratch, scratch_bytes, true, W) <= scratch_bytes, FF_ERR_WORKSPACE, "resampler_bwd: scratch too small");
-    const int Mq = s.Bn * s.q, Mkv = s.Bn * s.R, Mf = s.Bn * s.F;
-    const RowMap pD = plain_rows(s.D), pI = plain_rows(s.inner), pF = plain_rows(s.ffi);
-    const RowMap lat_bcast = RowMap{s.D, 0, s.q};
-    const RowMap kv_media = RowMap{s.D, (long long)s.R * s.D, s.F};
-    const RowMap kv_lat = RowMap{s.D, (long long)s.R * s.D, s.q};
+    const RowMap pD = s.pD, pI = s.pI, pF = s.pF;
     const void *latents = P[0], *tpe = P[1];
     void* dxf = dx_f ? dx_f : W.dxf;
-    // attention workspace lives behind the shared workspace
-    float* attn_ws = (float*)((char*)W.ws + W.ws_bytes - align_up((size_t)s.Bn * s.H * s.q * 4));
-    const size_t gws = W.ws_bytes - align_up((size_t)s.Bn * s.H * s.q * 4);
+    void* const ws = W.c.ws;
+    const size_t gws = W.c.gws;
 
-    // ---- data-gradient chain (critical path); weight-gradient operands are left in W.L[l] ----
+    // ---- data-gradient chain (critical path); weight-gradient operands are left in W.dx_out[l], W.L[l] ----
     // The final reductions of the LayerNorm backwards (d gamma / d beta) are not on that chain either: their partials stay in W.lnp and
     // one launch per kLnFinishMax of them finishes all 3 depth + 1 after the chain.
     LnPending ln_sets[3 * kMaxDepth + 1];
-    auto ln_bwd = [&](int slot, const LnArgs& a, const void* dy_, const void* x_, const void* add_, const void* gamma_, const float* mean_,
-                      const float* rstd_, void* dx_, const void* dx_res_, void* dg_, void* db_) -> int {
-        if (W.lnp[slot])
-            return layernorm_bwd(a, dy_, x_, add_, gamma_, mean_, rstd_, dx_, dx_res_, dg_, db_, W.lnp[slot], layernorm_bwd_partial_bytes(a.rows, a.cols), st,
-                                 nullptr, &ln_sets[slot]);       // (leaves ln_sets[slot].partial null if it had to run the unfused path)
-        return layernorm_bwd(a, dy_, x_, add_, gamma_, mean_, rstd_, dx_, dx_res_, dg_, db_, W.ws, gws, st);
-    };
     // final norm (:187): d x at the output of the last layer
-    FF_TRY(ln_bwd(3 * s.depth, ln_args(s.dt, Mq, s.D, pD, pD, pD), dout, S.x_last, nullptr, P[2], S.mean_o, S.rstd_o, W.L[s.depth - 1].dx_out, nullptr,
-                  G[2], G[3]));
+    FF_TRY(rs_ln_bwd(W.c, W.lnp[3 * s.depth], &ln_sets[3 * s.depth], s.ln_latents(), dout, S.x_last, nullptr, P[2], S.mean_o, S.rstd_o,
+                     W.dx_out[s.depth - 1], nullptr, G[2], G[3], st));
     for (int l = s.depth - 1; l >= 0; l--) {
         const void* const* p = P + FF_RESAMPLER_GLOBAL_PARAMS + FF_RESAMPLER_LAYER_PARAMS * l;
         void* const* g = G + FF_RESAMPLER_GLOBAL_PARAMS + FF_RESAMPLER_LAYER_PARAMS * l;
-        const RsLayerSaved& L = S.L[l];
-        const RsLayerStash& T = W.L[l];
-        const void* x_in = l == 0 ? latents : L.x_in;
-        const RowMap x_map = l == 0 ? lat_bcast : pD;
-        char* dkv_lat_base = (char*)W.dkv + (size_t)s.F * s.D * s.es;
-        void* dx_below = l == 0 ? W.dx0 : W.L[l - 1].dx_out;                                   // d x at this layer's input
-        // ---- FeedForward backward (x_next = x_mid + W3 act(W1 LN(x_mid))) ----
-        FF_TRY(Gemm(s.dt, Mq, s.ffi, s.D).a(0, pD).b(1, pF).c(pF).act_bwd(s.act).problem(T.dx_out, p[11], T.dH, nullptr, L.Hpre).run(W.ws, gws, st));
-        FF_TRY(Gemm(s.dt, Mq, s.D, s.ffi).a(0, pF).b(1, pD).c(pD).problem(T.dH, p[10], W.dxn).run(W.ws, gws, st));
-        FF_TRY(ln_bwd(3 * l, ln_args(s.dt, Mq, s.D, pD, pD, pD), W.dxn, L.x_mid, nullptr, p[8], L.mean_f, L.rstd_f, T.dx_mid, T.dx_out, g[8], g[9]));   // T.dx_mid = d x_mid
-        // ---- attention backward (x_mid = x_in + Wo O) ----
-        FF_TRY(Gemm(s.dt, Mq, s.inner, s.D).a(0, pD).b(1, pI).c(pI).problem(T.dx_mid, p[7], W.dO).run(W.ws, gws, st));
-        FF_TRY(attention_bwd(rs_attn_desc(s), L.Qs, L.K, L.V, nullptr, L.O, W.dO, L.lse, T.dQs, T.dK, T.dV, attn_ws,
-                             (size_t)s.Bn * s.H * s.q * 4, st));
-        // d kv_in = dK Wk + dV Wv
-        FF_TRY(Gemm(s.dt, Mkv, s.D, s.inner).a(0, pI).b(1, pD).c(pD).problem(T.dK, p[5], W.dkv).run(W.ws, gws, st));
-        FF_TRY(Gemm(s.dt, Mkv, s.D, s.inner).a(0, pI).b(1, pD).c(pD).problem(T.dV, p[6], W.dkv, nullptr, nullptr, W.dkv).run(W.ws, gws, st));
-        // d LN(latents) = scale * dQs Wq + d kv_in[latent rows]
-        FF_TRY(Gemm(s.dt, Mq, s.D, s.inner).a(0, pI).b(1, pD).c(pD).res_map(kv_lat).scale(s.scale)
-                   .problem(T.dQs, p[4], W.dln, nullptr, nullptr, dkv_lat_base).run(W.ws, gws, st));
-        // norm_latents backward, accumulated onto the residual path: d x_in
-        FF_TRY(ln_bwd(3 * l + 1, ln_args(s.dt, Mq, s.D, x_map, pD, pD), W.dln, x_in, nullptr, p[2], L.mean_l, L.rstd_l, dx_below, T.dx_mid, g[2], g[3]));
-        {   // norm_media backward: d x_f accumulates over the layers (needed for d time_pos_emb even with CLIP frozen)
-            LnArgs a = ln_args(s.dt, Mf, s.D, pD, kv_media, pD);
-            a.add_rows_per_seg = s.F; a.add_div = s.v;
-            FF_TRY(ln_bwd(3 * l + 2, a, W.dkv, x_f, tpe, p[0], S.mean_m, S.rstd_m, dxf, l == s.depth - 1 ? nullptr : dxf, g[0], g[1]));
-        }
+        void* dx_below = l == 0 ? W.dx0 : W.dx_out[l - 1];                                   // d x at this layer's input
+        FF_TRY(rs_layer_backward(s, p, g, x_f, tpe, S.mean_m, S.rstd_m, l == 0 ? latents : S.L[l].x_in, l == 0 ? s.lat_bcast : pD, S.L[l], W.dx_out[l],
+                                 dx_below, dxf, l == s.depth - 1 ? nullptr : dxf, W.c, W.L[l], W.lnp + 3 * l, ln_sets + 3 * l, st));
     }
     FF_TRY(layernorm_bwd_finish(s.dt, ln_sets, 3 * s.depth + 1, st));
     // ---- weight gradients, grouped over up to kGemmMaxZ layers per launch ----
     constexpr int kRsGroup = 4;      // layers per grouped weight-gradient launch (their tile counts are whole rounds of the chip already)
     for (int l0 = 0; l0 < s.depth; l0 += kRsGroup) {
         const int l1 = std::min(s.depth, l0 + kRsGroup);
-        Gemm g3(s.dt, s.D, s.ffi, Mq), g1(s.dt, s.ffi, s.D, Mq), go(s.dt, s.D, s.inner, Mq), gq(s.dt, s.inner, s.D, Mq);
+        Gemm g3(s.dt, s.D, s.ffi, s.Mq), g1(s.dt, s.ffi, s.D, s.Mq), go(s.dt, s.D, s.inner, s.Mq), gq(s.dt, s.inner, s.D, s.Mq);
         g3.a(1, pD).b(1, pF).c(pF);                       // d W3 = d x_out^T . act(H)
         g1.a(1, pF).b(1, pD).c(pD);                       // d W1 = d H^T . LN(x_mid)
         go.a(1, pD).b(1, pI).c(pI);                       // d Wo = d x_mid^T . O
-        gq.a(1, pI).b(1, kv_lat).c(pD).scale(s.scale);    // d Wq = scale * d Qs^T . LN(latents)   (the latent rows of kv_in)
+        gq.a(1, pI).b(1, s.kv_lat).c(pD).scale(s.scale);  // d Wq = scale * d Qs^T . LN(latents)   (the latent rows of kv_in)
         for (int l = l0; l < l1; l++) {
             void* const* g = G + FF_RESAMPLER_GLOBAL_PARAMS + FF_RESAMPLER_LAYER_PARAMS * l;
             const RsLayerSaved& L = S.L[l];
-            const RsLayerStash& T = W.L[l];
-            g3.problem(T.dx_out, L.Aact, g[11]);
+            const RsLayerGrads& T = W.L[l];
+            g3.problem(W.dx_out[l], L.Aact, g[11]);
             g1.problem(T.dH, L.xn_f, g[10]);
             go.problem(T.dx_mid, L.O, g[7]);
-            gq.problem(T.dQs, (const char*)L.kv_in + (size_t)s.F * s.D * s.es, g[4]);
+            gq.problem(T.dQs, s.kv_latent_rows(L.kv_in), g[4]);
         }
-        FF_TRY(g3.run(W.ws, gws, st));
-        FF_TRY(g1.run(W.ws, gws, st));
-        FF_TRY(go.run(W.ws, gws, st));
-        FF_TRY(gq.run(W.ws, gws, st));
+        FF_TRY(g3.run(ws, gws, st));
+        FF_TRY(g1.run(ws, gws, st));
+        FF_TRY(go.run(ws, gws, st));
+        FF_TRY(gq.run(ws, gws, st));
     }
     {   // d Wk, d Wv = d K^T / d V^T . kv_in: two problems per layer
-        Gemm gkv(s.dt, s.inner, s.D, Mkv);
+        Gemm gkv(s.dt, s.inner, s.D, s.Mkv);
         gkv.a(1, pI).b(1, pD).c(pD);
         for (int l = 0; l < s.depth; l++) {
             void* const* g = G + FF_RESAMPLER_GLOBAL_PARAMS + FF_RESAMPLER_LAYER_PARAMS * l;
             gkv.problem(W.L[l].dK, S.L[l].kv_in, g[5]);
             gkv.problem(W.L[l].dV, S.L[l].kv_in, g[6]);
             if (gkv.P.nz == kRsGroup || l == s.depth - 1) {
-                FF_TRY(gkv.run(W.ws, gws, st));
+                FF_TRY(gkv.run(ws, gws, st));
                 gkv.P.nz = 0;
             }
         }
     }
-    void* dx_in = W.dx0;
-    // d latents = sum over the batch of d x_0 (:179);  d time_pos_emb[t] = sum_{b, n} d x_f[b, t, n] (:166)
-    FF_TRY(rows_reduce(s.dt, Mq, s.D, pD, s.q, 1, dx_in, G[0], W.ws, gws, st));
-    // d time_pos_emb rows of frames the batch does not have: exact zeros.  A kernel, not hipMemsetAsync: with the memset, replays of a
-    // captured training step left int32-looking bytes of some other buffer in those rows (tests/test_hip_bounds.py::
-    // test_unused_time_embedding_gradient_rows_are_zero, graphed and piecewise); a launch on the stream keeps its order and the zeros.
-    if (s.nte > s.T) FF_TRY(zero_bytes((char*)G[1] + (size_t)s.T * s.D * s.es, (size_t)(s.nte - s.T) * s.D * s.es, st));
-    return rows_reduce(s.dt, Mf, s.D, pD, s.F, s.v, dxf, G[1], W.ws, gws, st);
+    return rs_input_grads(s, W.dx0, dxf, G[0], G[1], ws, gws, st);
 }
 
 // =====================================================================================================
@@ -339,56 +390,33 @@ static int resampler_bwd(const ff_resampler_desc* d, const void* x_f, const void
 // perceiver_resampler.py:181-183 is a per-layer loop; a caller that drives it layer by layer gets every layer's parameter gradients FINAL
 // when that layer's backward call returns - one data-parallel bucket per layer, leaving while the layer below runs backward - at the price
 // of what only the stack-level call can do (weight gradients of four layers per launch, LayerNorm finals of all layers in three launches).
+// The launches are the shared ones above; what is written here is what differs: the buffers, and how a layer's weight gradients and
+// LayerNorm finals are finished.
 // =====================================================================================================
 struct RsProSaved { float *mean_m, *rstd_m; };
 static size_t rs_pro_layout(const RsDims& s, void* base, size_t cap, RsProSaved& o) {
     Arena a(base, cap);
-    o.mean_m = a.take<float>((size_t)s.Bn * s.F * 4);
-    o.rstd_m = a.take<float>((size_t)s.Bn * s.F * 4);
+    o.mean_m = a.take<float>((size_t)s.Mf * 4);
+    o.rstd_m = a.take<float>((size_t)s.Mf * 4);
     return align_up(a.used);
 }
 static size_t rs_layer_saved_layout(const RsDims& s, void* base, size_t cap, RsLayerSaved& L) {
     Arena a(base, cap);
-    const size_t rows_q = (size_t)s.Bn * s.q, rows_kv = (size_t)s.Bn * s.R;
     L.x_in = nullptr;                           // the caller's tensor
-    L.mean_l = a.take<float>(rows_q * 4);
-    L.rstd_l = a.take<float>(rows_q * 4);
-    L.kv_in = a.take(rows_kv * s.D * s.es);
-    L.Qs = a.take(rows_q * s.inner * s.es);
-    L.K = a.take(rows_kv * s.inner * s.es);
-    L.V = a.take(rows_kv * s.inner * s.es);
-    L.lse = a.take<float>((size_t)s.Bn * s.H * s.q * 4);
-    L.O = a.take(rows_q * s.inner * s.es);
-    L.x_mid = a.take(rows_q * s.D * s.es);
-    L.mean_f = a.take<float>(rows_q * 4);
-    L.rstd_f = a.take<float>(rows_q * 4);
-    L.xn_f = a.take(rows_q * s.D * s.es);
-    L.Hpre = a.take(rows_q * s.ffi * s.es);
-    L.Aact = a.take(rows_q * s.ffi * s.es);
+    rs_take_layer_saved(s, a, L);
     return align_up(a.used);
 }
 struct RsLayerScratch {
-    void *dxn, *dO, *dkv, *dln, *dx_mid, *dH, *dQs, *dK, *dV, *ws;
+    RsChain c;
+    RsLayerGrads g;
     float* lnp[3];
-    size_t ws_bytes;
 };
 static size_t rs_layer_scratch_layout(const RsDims& s, void* base, size_t cap, RsLayerScratch& o) {
     Arena a(base, cap);
-    const size_t rows_q = (size_t)s.Bn * s.q, rows_kv = (size_t)s.Bn * s.R;
-    o.ws_bytes = rs_ws_bytes(s);
-    o.ws = a.take(o.ws_bytes);
-    o.dxn = a.take(rows_q * s.D * s.es);
-    o.dO = a.take(rows_q * s.inner * s.es);
-    o.dkv = a.take(rows_kv * s.D * s.es);
-    o.dln = a.take(rows_q * s.D * s.es);
-    o.dx_mid = a.take(rows_q * s.D * s.es);
-    o.dH = a.take(rows_q * s.ffi * s.es);
-    o.dQs = a.take(rows_q * s.inner * s.es);
-    o.dK = a.take(rows_kv * s.inner * s.es);
-    o.dV = a.take(rows_kv * s.inner * s.es);
-    const bool lnd = layernorm_bwd_deferrable(s.dt, s.D);
-    for (int i = 0; i < 3; i++)       // [0] ff norm, [1] norm_latents, [2] norm_media
-        o.lnp[i] = lnd ? a.take<float>(layernorm_bwd_partial_bytes(i == 2 ? s.Bn * s.F : (int)rows_q, s.D)) : nullptr;
+    rs_take_ws(s, a, o.c);
+    rs_take_chain(s, a, o.c);
+    rs_take_layer_grads(s, a, o.g);
+    rs_take_ln_partials(s, a, layernorm_bwd_deferrable(s.dt, s.D), o.lnp);
     return align_up(a.used);
 }
 
@@ -398,9 +426,7 @@ static int rs_prologue_fwd(const ff_resampler_desc* d, const void* x_f, const vo
     const RsDims s(*d);
     RsProSaved S;
     FF_CHECK(rs_pro_layout(s, pro, pro_bytes, S) <= pro_bytes, FF_ERR_WORKSPACE, "resampler_prologue_fwd: saved buffer too small");
-    LnArgs a = ln_args(s.dt, s.Bn * s.F, s.D, plain_rows(s.D), plain_rows(s.D), plain_rows(s.D));
-    a.add_rows_per_seg = s.F; a.add_div = s.v;       // statistics of x_f + time_pos_emb, shared by the norm_media of every layer (:166, :52)
-    return layernorm_fwd(a, x_f, tpe, nullptr, nullptr, nullptr, S.mean_m, S.rstd_m, st);
+    return rs_media_stats(s, x_f, tpe, S.mean_m, S.rstd_m, st);
 }
 
 static int rs_layer_fwd(const ff_resampler_desc* d, const void* x_f, const void* tpe, const void* pro, size_t pro_bytes, const void* x_in,
@@ -415,24 +441,7 @@ static int rs_layer_fwd(const ff_resampler_desc* d, const void* x_f, const void*
     FF_CHECK(rs_pro_layout(s, (void*)pro, pro_bytes, Pr) <= pro_bytes, FF_ERR_WORKSPACE, "resampler_layer_fwd: prologue buffer too small");
     FF_CHECK(rs_layer_saved_layout(s, saved, saved_bytes, L) <= saved_bytes, FF_ERR_WORKSPACE, "resampler_layer_fwd: saved buffer too small");
     FF_CHECK(rs_layer_scratch_layout(s, scratch, scratch_bytes, W) <= scratch_bytes, FF_ERR_WORKSPACE, "resampler_layer_fwd: scratch too small");
-    const int Mq = s.Bn * s.q, Mkv = s.Bn * s.R, Mf = s.Bn * s.F;
-    const RowMap pD = plain_rows(s.D), pI = plain_rows(s.inner), pF = plain_rows(s.ffi);
-    const RowMap x_map = x_is_latents ? RowMap{s.D, 0, s.q} : pD;                    // latents (q, D) repeated over the batch (:179)
-    const RowMap kv_media = RowMap{s.D, (long long)s.R * s.D, s.F}, kv_lat = RowMap{s.D, (long long)s.R * s.D, s.q};
-    char* kv_lat_base = (char*)L.kv_in + (size_t)s.F * s.D * s.es;
-    {   // norm_media -> media rows of kv_in (:52,65)
-        LnArgs a = ln_args(s.dt, Mf, s.D, pD, kv_media, pD);
-        a.add_rows_per_seg = s.F; a.add_div = s.v; a.stats_given = 1;
-        FF_TRY(layernorm_fwd(a, x_f, tpe, p[0], p[1], L.kv_in, Pr.mean_m, Pr.rstd_m, st));
-    }
-    FF_TRY(layernorm_fwd(ln_args(s.dt, Mq, s.D, x_map, kv_lat, pD), x_in, nullptr, p[2], p[3], kv_lat_base, L.mean_l, L.rstd_l, st));   // :53,65
-    FF_TRY(Gemm(s.dt, Mq, s.inner, s.D).a(0, kv_lat).b(0, pD).c(pI).scale(s.scale).problem(kv_lat_base, p[4], L.Qs).run(W.ws, W.ws_bytes, st));   // :57,79
-    FF_TRY(Gemm(s.dt, Mkv, s.inner, s.D).a(0, pD).b(0, pD).c(pI).problem(L.kv_in, p[5], L.K).problem(L.kv_in, p[6], L.V).run(W.ws, W.ws_bytes, st));   // :69-70
-    FF_TRY(attention_fwd(rs_attn_desc(s), L.Qs, L.K, L.V, nullptr, L.O, L.lse, st));                                                  // :85-92
-    FF_TRY(Gemm(s.dt, Mq, s.D, s.inner).a(0, pI).b(0, pI).c(pD).res_map(x_map).problem(L.O, p[7], L.x_mid, nullptr, nullptr, x_in).run(W.ws, W.ws_bytes, st));   // :96, :182
-    FF_TRY(layernorm_fwd(ln_args(s.dt, Mq, s.D, pD, pD, pD), L.x_mid, nullptr, p[8], p[9], L.xn_f, L.mean_f, L.rstd_f, st));          // :183; utils.py:45-50
-    FF_TRY(Gemm(s.dt, Mq, s.ffi, s.D).a(0, pD).b(0, pD).c(pF).act(s.act).problem(L.xn_f, p[10], L.Aact, L.Hpre).run(W.ws, W.ws_bytes, st));
-    return Gemm(s.dt, Mq, s.D, s.ffi).a(0, pF).b(0, pF).c(pD).problem(L.Aact, p[11], x_out, nullptr, nullptr, L.x_mid).run(W.ws, W.ws_bytes, st);
+    return rs_layer_forward(s, p, x_f, tpe, Pr.mean_m, Pr.rstd_m, x_in, x_is_latents ? s.lat_bcast : s.pD, x_out, L, W.c.ws, W.c.ws_bytes, st);
 }
 
 static int rs_layer_bwd(const ff_resampler_desc* d, const void* x_f, const void* tpe, const void* pro, size_t pro_bytes, const void* x_in,
@@ -447,46 +456,19 @@ static int rs_layer_bwd(const ff_resampler_desc* d, const void* x_f, const void*
     FF_CHECK(rs_pro_layout(s, (void*)pro, pro_bytes, Pr) <= pro_bytes, FF_ERR_WORKSPACE, "resampler_layer_bwd: prologue buffer too small");
     FF_CHECK(rs_layer_saved_layout(s, (void*)saved, saved_bytes, L) <= saved_bytes, FF_ERR_WORKSPACE, "resampler_layer_bwd: saved buffer too small");
     FF_CHECK(rs_layer_scratch_layout(s, scratch, scratch_bytes, W) <= scratch_bytes, FF_ERR_WORKSPACE, "resampler_layer_bwd: scratch too small");
-    const int Mq = s.Bn * s.q, Mkv = s.Bn * s.R, Mf = s.Bn * s.F;
-    const RowMap pD = plain_rows(s.D), pI = plain_rows(s.inner), pF = plain_rows(s.ffi);
-    const RowMap x_map = x_is_latents ? RowMap{s.D, 0, s.q} : pD;
-    const RowMap kv_media = RowMap{s.D, (long long)s.R * s.D, s.F}, kv_lat = RowMap{s.D, (long long)s.R * s.D, s.q};
-    float* attn_ws = (float*)((char*)W.ws + W.ws_bytes - align_up((size_t)s.Bn * s.H * s.q * 4));
-    const size_t gws = W.ws_bytes - align_up((size_t)s.Bn * s.H * s.q * 4);
-    char* dkv_lat_base = (char*)W.dkv + (size_t)s.F * s.D * s.es;
-    const char* kv_lat_base = (const char*)L.kv_in + (size_t)s.F * s.D * s.es;
+    const RowMap pD = s.pD, pI = s.pI, pF = s.pF;
+    void* const ws = W.c.ws;
+    const size_t gws = W.c.gws;
     LnPending ln_sets[3];
-    auto ln_bwd = [&](int slot, const LnArgs& a, const void* dy_, const void* x_, const void* add_, const void* gamma_, const float* mean_,
-                      const float* rstd_, void* dx_, const void* dx_res_, void* dg_, void* db_) -> int {
-        if (W.lnp[slot])
-            return layernorm_bwd(a, dy_, x_, add_, gamma_, mean_, rstd_, dx_, dx_res_, dg_, db_, W.lnp[slot], layernorm_bwd_partial_bytes(a.rows, a.cols), st,
-                                 nullptr, &ln_sets[slot]);
-        return layernorm_bwd(a, dy_, x_, add_, gamma_, mean_, rstd_, dx_, dx_res_, dg_, db_, W.ws, gws, st);
-    };
-    // ---- FeedForward backward (x_out = x_mid + W3 act(W1 LN(x_mid))) ----
-    FF_TRY(Gemm(s.dt, Mq, s.ffi, s.D).a(0, pD).b(1, pF).c(pF).act_bwd(s.act).problem(dx_out, p[11], W.dH, nullptr, L.Hpre).run(W.ws, gws, st));
-    FF_TRY(Gemm(s.dt, Mq, s.D, s.ffi).a(0, pF).b(1, pD).c(pD).problem(W.dH, p[10], W.dxn).run(W.ws, gws, st));
-    FF_TRY(ln_bwd(0, ln_args(s.dt, Mq, s.D, pD, pD, pD), W.dxn, L.x_mid, nullptr, p[8], L.mean_f, L.rstd_f, W.dx_mid, dx_out, g[8], g[9]));
-    // ---- attention backward (x_mid = x_in + Wo O) ----
-    FF_TRY(Gemm(s.dt, Mq, s.inner, s.D).a(0, pD).b(1, pI).c(pI).problem(W.dx_mid, p[7], W.dO).run(W.ws, gws, st));
-    FF_TRY(attention_bwd(rs_attn_desc(s), L.Qs, L.K, L.V, nullptr, L.O, W.dO, L.lse, W.dQs, W.dK, W.dV, attn_ws, (size_t)s.Bn * s.H * s.q * 4, st));
-    FF_TRY(Gemm(s.dt, Mkv, s.D, s.inner).a(0, pI).b(1, pD).c(pD).problem(W.dK, p[5], W.dkv).run(W.ws, gws, st));
-    FF_TRY(Gemm(s.dt, Mkv, s.D, s.inner).a(0, pI).b(1, pD).c(pD).problem(W.dV, p[6], W.dkv, nullptr, nullptr, W.dkv).run(W.ws, gws, st));
-    FF_TRY(Gemm(s.dt, Mq, s.D, s.inner).a(0, pI).b(1, pD).c(pD).res_map(kv_lat).scale(s.scale)
-               .problem(W.dQs, p[4], W.dln, nullptr, nullptr, dkv_lat_base).run(W.ws, gws, st));
-    FF_TRY(ln_bwd(1, ln_args(s.dt, Mq, s.D, x_map, pD, pD), W.dln, x_in, nullptr, p[2], L.mean_l, L.rstd_l, dx_in, W.dx_mid, g[2], g[3]));
-    {   // norm_media backward: d x_f accumulates over the layers (needed for d time_pos_emb even with CLIP frozen)
-        LnArgs a = ln_args(s.dt, Mf, s.D, pD, kv_media, pD);
-        a.add_rows_per_seg = s.F; a.add_div = s.v;
-        FF_TRY(ln_bwd(2, a, W.dkv, x_f, tpe, p[0], Pr.mean_m, Pr.rstd_m, dx_f, dx_f_accumulate ? dx_f : nullptr, g[0], g[1]));
-    }
+    FF_TRY(rs_layer_backward(s, p, g, x_f, tpe, Pr.mean_m, Pr.rstd_m, x_in, x_is_latents ? s.lat_bcast : pD, L, dx_out, dx_in, dx_f,
+                             dx_f_accumulate ? dx_f : nullptr, W.c, W.g, W.lnp, ln_sets, st));
     FF_TRY(layernorm_bwd_finish(s.dt, ln_sets, 3, st));
     // ---- this layer's weight gradients, final when the call returns ----
-    FF_TRY(Gemm(s.dt, s.D, s.ffi, Mq).a(1, pD).b(1, pF).c(pF).problem(dx_out, L.Aact, g[11]).run(W.ws, gws, st));          // d W3 = d x_out^T . act(H)
-    FF_TRY(Gemm(s.dt, s.ffi, s.D, Mq).a(1, pF).b(1, pD).c(pD).problem(W.dH, L.xn_f, g[10]).run(W.ws, gws, st));           // d W1 = d H^T . LN(x_mid)
-    FF_TRY(Gemm(s.dt, s.D, s.inner, Mq).a(1, pD).b(1, pI).c(pI).problem(W.dx_mid, L.O, g[7]).run(W.ws, gws, st));         // d Wo = d x_mid^T . O
-    FF_TRY(Gemm(s.dt, s.inner, s.D, Mq).a(1, pI).b(1, kv_lat).c(pD).scale(s.scale).problem(W.dQs, kv_lat_base, g[4]).run(W.ws, gws, st));   // d Wq
-    return Gemm(s.dt, s.inner, s.D, Mkv).a(1, pI).b(1, pD).c(pD).problem(W.dK, L.kv_in, g[5]).problem(W.dV, L.kv_in, g[6]).run(W.ws, gws, st);  // d Wk, d Wv
+    FF_TRY(Gemm(s.dt, s.D, s.ffi, s.Mq).a(1, pD).b(1, pF).c(pF).problem(dx_out, L.Aact, g[11]).run(ws, gws, st));          // d W3 = d x_out^T . act(H)
+    FF_TRY(Gemm(s.dt, s.ffi, s.D, s.Mq).a(1, pF).b(1, pD).c(pD).problem(W.g.dH, L.xn_f, g[10]).run(ws, gws, st));         // d W1 = d H^T . LN(x_mid)
+    FF_TRY(Gemm(s.dt, s.D, s.inner, s.Mq).a(1, pD).b(1, pI).c(pI).problem(W.g.dx_mid, L.O, g[7]).run(ws, gws, st));       // d Wo = d x_mid^T . O
+    FF_TRY(Gemm(s.dt, s.inner, s.D, s.Mq).a(1, pI).b(1, s.kv_lat).c(pD).scale(s.scale).problem(W.g.dQs, s.kv_latent_rows(L.kv_in), g[4]).run(ws, gws, st));   // d Wq
+    return Gemm(s.dt, s.inner, s.D, s.Mkv).a(1, pI).b(1, pD).c(pD).problem(W.g.dK, L.kv_in, g[5]).problem(W.g.dV, L.kv_in, g[6]).run(ws, gws, st);  // d Wk, d Wv
 }
 
 static int rs_prologue_bwd(const ff_resampler_desc* d, const void* dx0, const void* dx_f, void* d_latents, void* d_tpe, void* scratch,
@@ -496,11 +478,7 @@ static int rs_prologue_bwd(const ff_resampler_desc* d, const void* dx0, const vo
     const RsDims s(*d);
     RsLayerScratch W;
     FF_CHECK(rs_layer_scratch_layout(s, scratch, scratch_bytes, W) <= scratch_bytes, FF_ERR_WORKSPACE, "resampler_prologue_bwd: scratch too small");
-    const RowMap pD = plain_rows(s.D);
-    // d latents = sum over the batch of d x_0 (:179);  d time_pos_emb[t] = sum_{b, n} d x_f[b, t, n] (:166)
-    FF_TRY(rows_reduce(s.dt, s.Bn * s.q, s.D, pD, s.q, 1, dx0, d_latents, W.ws, W.ws_bytes, st));
-    if (s.nte > s.T) FF_TRY(zero_bytes((char*)d_tpe + (size_t)s.T * s.D * s.es, (size_t)(s.nte - s.T) * s.D * s.es, st));   // see resampler_bwd
-    return rows_reduce(s.dt, s.Bn * s.F, s.D, pD, s.F, s.v, dx_f, d_tpe, W.ws, W.ws_bytes, st);
+    return rs_input_grads(s, dx0, dx_f, d_latents, d_tpe, W.c.ws, W.c.ws_bytes, st);
 }
 
 static int rs_epilogue_fwd(const ff_resampler_desc* d, const void* x_last, const void* gamma, const void* beta, void* out, void* epi, size_t epi_bytes,
@@ -508,25 +486,22 @@ static int rs_epilogue_fwd(const ff_resampler_desc* d, const void* x_last, const
     FF_TRY(rs_check(d));
     FF_CHECK(x_last && gamma && beta && out && epi, FF_ERR_SHAPE, "resampler_epilogue_fwd: null argument");
     const RsDims s(*d);
-    const size_t rows_q = (size_t)s.Bn * s.q;
+    const size_t rows_q = s.Mq;
     FF_CHECK(epi_bytes >= 2 * align_up(rows_q * 4), FF_ERR_WORKSPACE, "resampler_epilogue_fwd: saved buffer too small");
-    float* mean = (float*)epi;
-    float* rstd = (float*)((char*)epi + align_up(rows_q * 4));
-    return layernorm_fwd(ln_args(s.dt, (int)rows_q, s.D, plain_rows(s.D), plain_rows(s.D), plain_rows(s.D)), x_last, nullptr, gamma, beta, out, mean, rstd, st);   // :187
+    return rs_final_norm(s, x_last, gamma, beta, out, (float*)epi, (float*)((char*)epi + align_up(rows_q * 4)), st);
 }
 static int rs_epilogue_bwd(const ff_resampler_desc* d, const void* dout, const void* x_last, const void* gamma, const void* epi, size_t epi_bytes,
                            void* dx_last, void* dgamma, void* dbeta, void* scratch, size_t scratch_bytes, hipStream_t st) {
     FF_TRY(rs_check(d));
     FF_CHECK(dout && x_last && gamma && epi && dx_last && dgamma && dbeta && scratch, FF_ERR_SHAPE, "resampler_epilogue_bwd: null argument");
     const RsDims s(*d);
-    const size_t rows_q = (size_t)s.Bn * s.q;
+    const size_t rows_q = s.Mq;
     FF_CHECK(epi_bytes >= 2 * align_up(rows_q * 4), FF_ERR_WORKSPACE, "resampler_epilogue_bwd: saved buffer too small");
     RsLayerScratch W;
     FF_CHECK(rs_layer_scratch_layout(s, scratch, scratch_bytes, W) <= scratch_bytes, FF_ERR_WORKSPACE, "resampler_epilogue_bwd: scratch too small");
     const float* mean = (const float*)epi;
     const float* rstd = (const float*)((const char*)epi + align_up(rows_q * 4));
-    return layernorm_bwd(ln_args(s.dt, (int)rows_q, s.D, plain_rows(s.D), plain_rows(s.D), plain_rows(s.D)), dout, x_last, nullptr, gamma, mean, rstd, dx_last,
-                         nullptr, dgamma, dbeta, W.ws, W.ws_bytes, st);
+    return layernorm_bwd(s.ln_latents(), dout, x_last, nullptr, gamma, mean, rstd, dx_last, nullptr, dgamma, dbeta, W.c.ws, W.c.ws_bytes, st);
 }
 
 // =====================================================================================================

@@ -309,7 +309,7 @@ class _ResamplerFn(torch.autograd.Function):
         out = _new((x_f.shape[0], cfg[3], x_f.shape[3]), x_f.dtype, dev)
         ffi.check(lib.ff_resampler_fwd(desc, x_f.data_ptr(), ffi.ptr_array(params), out.data_ptr(), saved.data_ptr(), saved.numel(),
                                        scratch.data_ptr(), scratch.numel(), ffi.stream_handle(dev)), "ff_resampler_fwd")
-        ctx.cfg = cfg
+        ctx.desc = desc
         ctx.save_for_backward(x_f, saved, *params)
         return out
 
@@ -317,8 +317,7 @@ class _ResamplerFn(torch.autograd.Function):
     def backward(ctx, dout: torch.Tensor):
         lib = ffi.lib()
         x_f, saved, *params = ctx.saved_tensors
-        desc = _resampler_desc(x_f, ctx.cfg)
-        dev = x_f.device
+        desc, dev = ctx.desc, x_f.device
         dout = dout.contiguous()
         flat, grads = _flat_grads(params)
         dx_f = _new_like(x_f) if ctx.needs_input_grad[0] else None
@@ -362,7 +361,7 @@ class _RsPrologueFn(torch.autograd.Function):
         pro = _empty_bytes(lib.ff_resampler_prologue_saved_bytes(desc), x_f.device)
         ffi.check(lib.ff_resampler_prologue_fwd(desc, x_f.data_ptr(), tpe.data_ptr(), pro.data_ptr(), pro.numel(), ffi.stream_handle(x_f.device)),
                   "ff_resampler_prologue_fwd")
-        ctx.cfg, ctx.rs_pass = cfg, rs_pass
+        ctx.desc, ctx.rs_pass = desc, rs_pass
         ctx.save_for_backward(x_f, tpe, latents)
         token = torch.zeros(1, dtype=torch.float32, device=x_f.device)       # what the layers consume: orders this node's backward behind theirs
         ctx.mark_non_differentiable(pro)
@@ -375,7 +374,7 @@ class _RsPrologueFn(torch.autograd.Function):
         rp = ctx.rs_pass
         if rp.dxf is None or rp.dx0 is None:
             raise ffi.FusionLibraryError("resampler (layer-wise): the prologue's backward ran before the layers' - the autograd graph was cut between them")
-        desc = _resampler_desc(x_f, ctx.cfg)
+        desc = ctx.desc
         flat, grads = _flat_grads([latents, tpe])
         scratch = _empty_bytes(lib.ff_resampler_layer_scratch_bytes(desc), x_f.device)
         ffi.check(lib.ff_resampler_prologue_bwd(desc, rp.dx0.data_ptr(), rp.dxf.data_ptr(), grads[0].data_ptr(), grads[1].data_ptr(), scratch.data_ptr(),
@@ -400,7 +399,7 @@ class _RsLayerFn(torch.autograd.Function):
         ffi.check(lib.ff_resampler_layer_fwd(desc, x_f.data_ptr(), tpe.data_ptr(), pro.data_ptr(), pro.numel(), x.data_ptr(), 1 if first else 0,
                                              ffi.ptr_array(params), out.data_ptr(), saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(),
                                              ffi.stream_handle(dev)), "ff_resampler_layer_fwd")
-        ctx.cfg, ctx.rs_pass, ctx.first, ctx.last = cfg, rs_pass, first, last
+        ctx.desc, ctx.rs_pass, ctx.first = desc, rs_pass, first
         ctx.save_for_backward(x, x_f, tpe, pro, saved, *params)
         return out
 
@@ -408,8 +407,7 @@ class _RsLayerFn(torch.autograd.Function):
     def backward(ctx, dout):
         lib = ffi.lib()
         x, x_f, tpe, pro, saved, *params = ctx.saved_tensors
-        desc = _resampler_desc(x_f, ctx.cfg)
-        dev = x_f.device
+        desc, dev = ctx.desc, x_f.device
         rp = ctx.rs_pass
         dout = dout.contiguous()
         flat, grads = _flat_grads(params)
@@ -439,7 +437,7 @@ class _RsEpilogueFn(torch.autograd.Function):
         out = _new_like(x)
         ffi.check(lib.ff_resampler_epilogue_fwd(desc, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), epi.data_ptr(), epi.numel(),
                                                 ffi.stream_handle(x.device)), "ff_resampler_epilogue_fwd")
-        ctx.cfg, ctx.xf_shape = cfg, tuple(x_f.shape)
+        ctx.desc = desc
         ctx.save_for_backward(x, gamma, beta, epi)
         return out
 
@@ -447,9 +445,7 @@ class _RsEpilogueFn(torch.autograd.Function):
     def backward(ctx, dout):
         lib = ffi.lib()
         x, gamma, beta, epi = ctx.saved_tensors
-        b, T, v, d = ctx.xf_shape
-        depth, heads, dim_head, num_latents, nte, ff_mult, act = ctx.cfg
-        desc = ffi.ResamplerDesc(ffi.dtype_code(x.dtype), b, T, v, d, depth, heads, dim_head, num_latents, nte, ff_mult, ffi.ACTS[act])
+        desc = ctx.desc
         dout = dout.contiguous()
         flat, grads = _flat_grads([gamma, beta])
         dx = _new_like(x)

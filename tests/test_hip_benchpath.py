@@ -153,7 +153,9 @@ def test_hoisted_deferred_blocks_ragged_batch_long_text(dtype):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
 def test_config_B_resampler_full_batch(dtype, layerwise):
     """The resampler of config B at its full batch: (32, 1, 257, 1024) CLIP-L features, depth 6, grouped weight gradients over 4 + 2 layers
-    (stack-level call) resp. one library call per layer (the data-parallel launch structure: ff_resampler_layer_*)."""
+    (stack-level call) resp. one library call per layer (the data-parallel launch structure: ff_resampler_layer_*).  The two call forms
+    issue the same forward launches and the same data-gradient chain, so out and d x_f agree bit for bit (the parameter gradients need not:
+    grouped against single weight-gradient launches); the layer-by-layer case holds the stack-level call to that."""
     dim, depth, b = 1024, 6, 32
     p = resampler_params(dim, depth, HEADS, DH, 64, 4, 4, tag="BPrs")
     m = build_resampler(p, dim, depth, HEADS, DH, 64, 4, 4, "gelu", dtype)
@@ -174,6 +176,14 @@ def test_config_B_resampler_full_batch(dtype, layerwise):
     bad = {k: v for k, v in worst.items() if not v < t["grad"]}
     print(f"[benchpath resampler {dtype}] worst parameter-gradient errors:", sorted(worst.items(), key=lambda kv: -kv[1])[:4], flush=True)
     assert not bad, bad
+    if layerwise:
+        m.layerwise = False
+        m.zero_grad(set_to_none=True)
+        xs = xd.detach().clone().requires_grad_(True)
+        ys = m(xs)
+        ys.backward(dyd)
+        assert torch.equal(ys, y), "out: the stack-level and the layer-by-layer call differ"
+        assert torch.equal(xs.grad, xd.grad), "d x_f: the stack-level and the layer-by-layer call differ"
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
