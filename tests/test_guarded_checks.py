@@ -1,12 +1,15 @@
 """The checkers of tests/test_hip_bounds.py, checked themselves on the CPU: the guards (tests/guarded.py) catch writes past a buffer's end,
 into the padding between rows and unwritten elements; the row / element checks (tests/util.py) catch defects of a GEMM that the whole-tensor
-relative error `rel(...) < 8e-3` (the bf16 tolerance of the parity tests) lets through."""
+relative error `rel(...) < 8e-3` (the bf16 tolerance of the parity tests) lets through; the per-element AdamW check (util.adamw_bound_ok)
+passes a float32 restatement of the kernel's formula in every storage mode and catches each way of getting the rule wrong that the
+parity tests' `rel(p, ref) < 1e-2` passes."""
 import numpy as np
 import pytest
 import torch
 
 from guarded import GuardViolation, Guards, guarded_allocations
-from util import gemm_bound_ok, gemm_ref, rel, rel_rows, rnd
+import optim_cases as oc
+from util import adamw_bound_ok, adamw_ref_step, gemm_bound_ok, gemm_ref, rel, rel_rows, rnd
 
 
 def _bf16(x):
@@ -200,3 +203,118 @@ def test_rel_rows_exact_zero_rows_and_small_rows():
     got[1, 2, 3, 0] *= 1.5
     worst, row = rel_rows(got, att, (0, 2, 1))
     assert row == (1, 3, 2) and worst > 0.01
+
+
+# ---- the per-element AdamW check against a float32 restatement of the kernel (tests/optim_cases.py) and defects injected into it -----------
+OWN = oc.owned()
+
+
+def test_the_tensor_list_refills_the_pointer_table_with_a_multi_chunk_tensor():
+    """more than 32 non-empty tensors, the 33rd (the first of the second launch) of more than one 32768-element chunk, a zero-element
+    tensor inside the list, two vector-sized views off the 16-byte grid, and nothing overlapping in the arena"""
+    sizes = [n for n, _ in oc.TENSORS if n > 0]
+    assert len(sizes) > 32 and sizes[32] > 32768 and 0 in [n for n, _ in oc.TENSORS[1:-1]]
+    assert sum(1 for n, off in oc.TENSORS if off and n % 8 == 0) >= 2
+    lay, total = oc.layout()
+    assert all(a + n + oc.GAP <= b for (a, n), (b, _) in zip(lay, lay[1:])) and lay[0][0] >= oc.GAP and lay[-1][0] + lay[-1][1] + oc.GAP <= total
+    assert all((a - off) % 64 == 0 for (a, _), (_, off) in zip(lay, oc.TENSORS)) and OWN.numel() == sum(n for n, _ in oc.TENSORS)
+
+
+def _adamw_inputs(mode, hp, step):
+    """(p, g, m, v, w) in their storage types at the inputs of tests/test_hip_optim_bounds.py: zero state before step 1, otherwise the
+    injected state"""
+    T, ST, master = oc.MODES[mode]
+    p = torch.from_numpy(oc.p_values(1))[OWN].to(T)
+    g = torch.from_numpy(oc.values(100 + step, hp["g_scale"]))[OWN].to(T)
+    if step == 1:
+        m, v = torch.zeros(p.numel(), dtype=ST), torch.zeros(p.numel(), dtype=ST)
+    else:
+        m, v = (torch.from_numpy(x).to(ST) for x in oc.injected_state(hp, p.numel()))
+    return p, g, m, v, (p.float() if master else None)
+
+
+def _adamw_check(mode, hp, clipped, step, old, new):
+    """every stored result of one step against adamw_ref_step from `old`: [(name, ok, worst ratio, flat index)]"""
+    T, ST, master = oc.MODES[mode]
+    p, g, m, v, w = old
+    coef = oc.clip_coef64(g, hp)[1] if clipped else 1.0
+    refs, terms = adamw_ref_step(w if master else p, g, m, v, step, hp["lr"], *hp["betas"], hp["eps"], hp["weight_decay"], hp["grad_scale"], coef)
+    got = ((new[3], torch.float32) if master else (new[0], T), (new[1], ST), (new[2], ST))
+    out = [(name,) + adamw_bound_ok(x, r, t, sd) for name, (x, sd), r, t in zip("pmv", got, refs, terms)]
+    if master:
+        out.append(("p=bf16(master)", torch.equal(new[0].view(torch.int16), new[3].to(torch.bfloat16).view(torch.int16)), 0.0, 0))
+    return out
+
+
+@pytest.mark.parametrize("clipped", [False, True], ids=["unclipped", "clipped"])
+@pytest.mark.parametrize("hpn", ["A", "B"])
+@pytest.mark.parametrize("mode", list(oc.MODES))
+def test_adamw_restatement_passes_the_element_bound(mode, hpn, clipped):
+    """Steps 1 to 3 from zero state (each checked from the state the previous one stored) and step 1000 from the injected state."""
+    hp = oc.HP[hpn]
+    for first, n in ((1, 3), (1000, 1)):
+        p, _, m, v, w = _adamw_inputs(mode, hp, first)
+        for step in range(first, first + n):
+            g = _adamw_inputs(mode, hp, step)[1]
+            if clipped:
+                assert oc.clip_coef64(g, hp)[1] < 0.5
+            new = oc.adamw_f32_step(p, g, m, v, w, step, hp, mode, clipped)
+            for name, ok, worst, idx in _adamw_check(mode, hp, clipped, step, (p, g, m, v, w), new):
+                assert ok, (step, name, worst, idx)
+            p, m, v, w = new
+
+
+def _splice(first, end):
+    def f(old, new):
+        out = [x if x is None else x.clone() for x in new]
+        for k, src in enumerate((old[0], old[2], old[3], old[4])):
+            if src is not None:
+                out[k][first:end] = src[first:end]
+        return tuple(out)
+    return f
+
+
+_SEG = oc.segments()
+_T3591 = next(s for s, (n, _) in zip(_SEG, oc.TENSORS) if n == 3591)
+_T65536 = next(s for s, (n, _) in zip(_SEG, oc.TENSORS) if n == 65536)
+#            name: (hyper-parameter set, clipped, step, mutate argument of the restatement, or a function splicing old values into the result)
+MUTATIONS = {"parameters-unchanged": ("A", False, 2, "keep-p"),
+             "no-weight-decay": ("A", False, 2, "no-decay"),
+             "no-bias-correction": ("A", False, 2, "no-bias-correction"),
+             "eps-inside-sqrt": ("B", False, 2, "eps-in-sqrt"),
+             "linear-second-moment": ("A", False, 2, "linear-v"),
+             "last-7-of-3591-untouched": ("A", False, 2, _splice(_T3591[1] - 7, _T3591[1])),
+             "one-2048-piece-skipped": ("A", False, 2, _splice(_T65536[0] + 32768 + 2048, _T65536[0] + 32768 + 4096)),
+             "grad-scale-ignored": ("B", False, 2, "no-grad-scale"),
+             "clip-coefficient-ignored": ("A", True, 2, "no-clip")}
+
+
+@pytest.mark.parametrize("mode", list(oc.MODES))
+@pytest.mark.parametrize("name", list(MUTATIONS))
+def test_adamw_element_bound_catches(name, mode):
+    """One step from the injected state with one defect; in every storage mode at least one element of the stored results is outside its
+    bound (and, for the partial defects, that element is inside the stretch that was skipped)."""
+    hpn, clipped, step, how = MUTATIONS[name]
+    hp = oc.HP[hpn]
+    old = _adamw_inputs(mode, hp, step)
+    good = oc.adamw_f32_step(*old, step, hp, mode, clipped)
+    assert all(ok for _, ok, _, _ in _adamw_check(mode, hp, clipped, step, old, good))
+    bad = how(old, good) if callable(how) else oc.adamw_f32_step(*old, step, hp, mode, clipped, mutate=how)
+    failed = [(n, worst, idx) for n, ok, worst, idx in _adamw_check(mode, hp, clipped, step, old, bad) if not ok]
+    assert failed, name
+    if name == "last-7-of-3591-untouched":
+        assert all(_T3591[1] - 7 <= idx < _T3591[1] for _, _, idx in failed)
+    if name == "one-2048-piece-skipped":
+        assert all(_T65536[0] + 34816 <= idx < _T65536[0] + 36864 for _, _, idx in failed)
+
+
+def test_adamw_bound_counts_nan_as_inf_and_names_the_element():
+    ref = torch.linspace(0.2, 0.4, 50, dtype=torch.float64)
+    got = ref.float()
+    assert adamw_bound_ok(got, ref, ref.abs(), torch.float32, c=1.0)[0]
+    got[17] = float("nan")
+    assert adamw_bound_ok(got, ref, ref.abs(), torch.float32, c=1.0) == (False, np.inf, 17)
+    one = torch.tensor([1.0], dtype=torch.float64)                  # half an ulp of the storage type and no more: 2^-8 at 1 in bf16
+    assert adamw_bound_ok(one + 2.0 ** -8, one, one * 0, torch.bfloat16, c=0.0)[0]
+    assert not adamw_bound_ok(one + 2.0 ** -8 + 2.0 ** -20, one, one * 0, torch.bfloat16, c=0.0)[0]
+    assert not adamw_bound_ok(one + 2.0 ** -23, one, one * 0, torch.float32, c=0.0)[0]

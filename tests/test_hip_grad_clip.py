@@ -14,7 +14,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import flamingo_oracle as O
-from util import as64, dev, rel, rnd
+from util import ADAMW_C_PARITY, adamw_state, adamw_step_ok, as64, dev, rel, rnd
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,9 +112,17 @@ def test_fused_adamw_clipped_matches_oracle_and_torch(mode, c):
                 ref[i] = tuple(as64(torch.as_tensor(t).to(torch.float32)) for t in ref[i])
             elif dtype == torch.bfloat16:
                 ref[i] = tuple(as64(torch.as_tensor(t).to(torch.bfloat16)) for t in ref[i])
+        before = [adamw_state(opt_a, a) for a in ours]
         opt_a.step()
         torch.nn.utils.clip_grad_norm_(theirs, c)
         opt_b.step()
+        for i, a in enumerate(ours):        # this step alone, element by element, from the state the kernel had stored (util.adamw_bound_ok)
+            new, storages = adamw_state(opt_a, a)       # (the fp32 master copy and fp32 moments exist from the first step on)
+            ok, bad = adamw_step_ok(before[i][0], new, gs[i], storages, step, HP["lr"], 0.9, 0.95, 1e-8, 0.05, coef=min(1.0, c / (norm + 1e-6)),
+                                    c=ADAMW_C_PARITY)
+            assert ok, (step, SHAPES[i], bad)
+            if master:
+                assert torch.equal(a.detach(), new[0].to(torch.bfloat16)), (step, SHAPES[i])
         assert abs(float(opt_a.grad_norm) - norm) <= 1e-5 * norm, (float(opt_a.grad_norm), norm)
     assert c < min(norms) or c > max(norms)
     tol = 1e-6 if mode == "f32" else 1e-2

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import flamingo_oracle as O
-from util import as64, dev, rel, rnd
+from util import ADAMW_C_PARITY, adamw_state, adamw_step_ok, as64, dev, rel, rnd
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(1,), (1280,), (513, 7), (5120, 1280), (64, 1024), (3,)]      # includes the 1-element alphas and ragged tails
@@ -26,8 +26,13 @@ def test_fused_adamw_matches_oracle_and_torch(dtype):
             ref[i] = O.adamw_step(p64, as64(g), m64, v64, step, lr=hp["lr"], beta1=0.9, beta2=0.95, eps=1e-8, weight_decay=0.05)
             if dtype == torch.bfloat16:     # the kernel stores p, m, v in bf16 after every step: mirror that rounding in the oracle
                 ref[i] = tuple(as64(torch.as_tensor(t).to(torch.bfloat16)) for t in ref[i])
+        before = [adamw_state(opt_a, a) for a in ours]
         opt_a.step()
         opt_b.step()
+        for i, a in enumerate(ours):        # this step alone, element by element, from the state the kernel had stored (util.adamw_bound_ok)
+            new, storages = adamw_state(opt_a, a)
+            ok, bad = adamw_step_ok(before[i][0], new, a.grad, storages, step, hp["lr"], 0.9, 0.95, 1e-8, 0.05, c=ADAMW_C_PARITY)
+            assert ok, (step, SHAPES[i], bad)
     tol = 1e-6 if dtype == torch.float32 else 1e-2
     for i, (a, b) in enumerate(zip(ours, theirs)):
         assert rel(a, ref[i][0]) < tol, SHAPES[i]
