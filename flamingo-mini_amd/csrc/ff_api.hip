@@ -945,7 +945,7 @@ static int kv_project_bwd(const ff_kvproj_desc* d, const void* vf, const void* c
 // =====================================================================================================
 // C ABI
 // =====================================================================================================
-extern "C" int ff_version(void) { return 5; }
+extern "C" int ff_version(void) { return 6; }
 extern "C" const char* ff_arch(void) { return "gfx950"; }
 extern "C" const char* ff_last_error(void) { return ff::g_err; }
 

@@ -36,7 +36,8 @@ struct AdamTable {
 // nontemporal accesses so that they do not evict what the next kernels read (37.52 -> 37.40 ms/step at config B in a same-box A/B)
 // CLIP: every gradient is also multiplied by *t.grad_coef (gradient clipping by global norm, ff_grad_clip_coef); the kernels without it
 // are the ones the unclipped step always ran.
-template <typename T, typename ST, bool MASTER, int VEC, int MODE = 0, bool CLIP = false>
+// GT: storage type of the gradients - T, or float where the gradients are the fp32 accumulators of ff_grad_accumulate (ff_adamw_step_acc).
+template <typename T, typename ST, bool MASTER, int VEC, int MODE = 0, bool CLIP = false, typename GT = T>
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     int ti = 0;
 #pragma unroll 1
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     const long long n = t.n[ti];
     const long long base = (long long)((int)blockIdx.x - t.block_start[ti]) * kAdamChunk;
     T* p = (T*)t.p[ti];
-    const T* g = (const T*)t.g[ti];
+    const GT* g = (const GT*)t.g[ti];
     ST* m = (ST*)t.m[ti];
     ST* v = (ST*)t.v[ti];
     float* w = t.w[ti];
@@ -162,9 +163,19 @@ static void adamw_dispatch(int dtype, bool master, int state_dtype, dim3 grid, h
     }
 }
 
+// bf16 parameters with fp32 gradients (ff_adamw_step_acc): the three storage modes of adamw_dispatch, MODE 1, GT = float
+template <bool CLIP>
+static void adamw_dispatch_acc(bool master, int state_dtype, dim3 grid, hipStream_t stream, const AdamTable& t) {
+    const dim3 block(256);
+    if (master) adamw_kernel<bf16, float, true, 8, 1, CLIP, float><<<grid, block, 0, stream>>>(t);
+    else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1, CLIP, float><<<grid, block, 0, stream>>>(t);
+    else adamw_kernel<bf16, bf16, false, 8, 1, CLIP, float><<<grid, block, 0, stream>>>(t);
+}
+
+// acc_grads: the gradients are fp32 whatever d->dtype is (for fp32 parameters that is what the fp32 kernels read anyway)
 static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, void* const* exp_avg,
                         void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef, const long long* numels,
-                        hipStream_t stream) {
+                        hipStream_t stream, bool acc_grads = false) {
     FF_CHECK(d && params && grads && exp_avg && exp_avg_sq && numels, FF_ERR_SHAPE, "ff_adamw_step: null argument");
     FF_CHECK(d->dtype == FF_DTYPE_F32 || d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_adamw_step: dtype %d", d->dtype);
     FF_CHECK(state_dtype == d->dtype || state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: moments must be stored in the parameter dtype or in fp32");
@@ -197,7 +208,10 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
         t.count = cnt;
         const dim3 grid(blocks);
         if (master) FF_CHECK(state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: fp32 master copies go with fp32 moments");
-        if (grad_coef) adamw_dispatch<true>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
+        if (acc_grads && d->dtype == FF_DTYPE_BF16) {
+            if (grad_coef) adamw_dispatch_acc<true>(master != nullptr, state_dtype, grid, stream, t);
+            else adamw_dispatch_acc<false>(master != nullptr, state_dtype, grid, stream, t);
+        } else if (grad_coef) adamw_dispatch<true>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
         else adamw_dispatch<false>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
         FF_TRY(check_launch("adamw"));
     }
@@ -326,6 +340,87 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const GradTable t) {
     for (long long i = tail + threadIdx.x; i < end; i += 256) g[i] = from_f32<T>(to_f32(g[i]) * c);
 }
 
+// ---- fp32 gradient accumulation over micro-batches (HF Trainer's gradient_accumulation_steps) ---------------------------------------------
+// acc = (OVERWRITE ? 0 : acc) + scale * g in the AdamW table's chunks: g in bf16 or fp32 is read once, the fp32 accumulator is read (unless
+// OVERWRITE: the first micro-batch of a step never looks at what the accumulator holds) and written once - all streamed nontemporally,
+// four independent 16-byte gradient loads (and their accumulator loads) per thread in flight before the first multiply-add.
+// (Open: in isolation, on one 512 M-element tensor, the overwriting fold moves 3.7 TB/s with nontemporal stores and 5.3 TB/s with plain
+// ones, the adding fold 5.2 against 5.4 TB/s - not adopted before it is measured inside the step, where plain stores may evict what the
+// next kernels read: DESIGN.md, gradient accumulation.)
+struct AccTable {
+    const void* g[kAdamTensors];
+    float* a[kAdamTensors];
+    long long n[kAdamTensors];
+    int block_start[kAdamTensors + 1];
+    int count;
+    float scale;
+};
+
+template <typename T, bool OVERWRITE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccTable t) {
+    constexpr int VEC = Vec<T>::N, PIECES = 4;
+    int ti = 0;
+#pragma unroll 1
+    while (ti + 1 < t.count && (int)blockIdx.x >= t.block_start[ti + 1]) ti++;
+    const long long n = t.n[ti];
+    const long long base = (long long)((int)blockIdx.x - t.block_start[ti]) * kAdamChunk;
+    const long long end = min(n, base + (long long)kAdamChunk);
+    const T* g = (const T*)t.g[ti];
+    float* a = t.a[ti];
+    const float s = t.scale;
+    auto lda = [&](long long i, float (&o)[VEC]) {                  // VEC accumulator elements: one (fp32 gradients) or two 16-byte loads
+#pragma unroll
+        for (int c = 0; c < VEC / 4; c++) {
+            float part[4];
+            Vec<float>::load_nt(a + i + c * 4, part);
+#pragma unroll
+            for (int e = 0; e < 4; e++) o[c * 4 + e] = part[e];
+        }
+    };
+    auto sta = [&](long long i, const float (&o)[VEC]) {
+#pragma unroll
+        for (int c = 0; c < VEC / 4; c++) {
+            float part[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) part[e] = o[c * 4 + e];
+            Vec<float>::store_nt(a + i + c * 4, part);
+        }
+    };
+    // the first fold is the rounded product itself (a multiply, so that -0 stays -0); every later one is ONE fused multiply-add
+    auto fold = [&](float gf, float af) { return OVERWRITE ? s * gf : fmaf(s, gf, af); };
+    long long tail = base;                          // elements from here to `end` go one by one
+    if (((uintptr_t)g | (uintptr_t)a) % 16 == 0) {  // (base is a multiple of the chunk, so every vector below is 16-byte aligned)
+        const long long vend = base + (end - base) / VEC * VEC;
+        tail = vend;
+        long long i = base + (long long)threadIdx.x * VEC;
+        for (; i + (PIECES - 1) * 256 * VEC < vend; i += PIECES * 256 * VEC) {
+            float gf[PIECES][VEC], af[PIECES][VEC];
+#pragma unroll
+            for (int k = 0; k < PIECES; k++) Vec<T>::load_nt(g + i + k * 256 * VEC, gf[k]);
+            if constexpr (!OVERWRITE) {
+#pragma unroll
+                for (int k = 0; k < PIECES; k++) lda(i + k * 256 * VEC, af[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < PIECES; k++) {
+#pragma unroll
+                for (int e = 0; e < VEC; e++) af[k][e] = fold(gf[k][e], OVERWRITE ? 0.f : af[k][e]);
+                sta(i + k * 256 * VEC, af[k]);
+            }
+        }
+        for (; i < vend; i += 256 * VEC) {          // (a tensor's last, partial chunk)
+            float gf[VEC], af[VEC];
+            Vec<T>::load_nt(g + i, gf);
+            if constexpr (!OVERWRITE) lda(i, af);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) af[e] = fold(gf[e], OVERWRITE ? 0.f : af[e]);
+            sta(i, af);
+        }
+    }
+    for (long long i = tail + threadIdx.x; i < end; i += 256)       // ragged tail (< VEC elements), or an unaligned tensor's whole chunk
+        a[i] = fold(to_f32(g[i]), OVERWRITE ? 0.f : a[i]);
+}
+
 static long long grad_slots(int n_tensors, const long long* numels) {
     long long slots = 0;
     for (int i = 0; i < n_tensors; i++)
@@ -383,6 +478,12 @@ extern "C" int ff_adamw_step_clipped(const ff_adamw_desc* d, int state_dtype, vo
     FF_CHECK(grad_coef, FF_ERR_SHAPE, "ff_adamw_step_clipped: grad_coef is null");
     return ff::adamw_launch(d, state_dtype, params, grads, exp_avg, exp_avg_sq, master, lr_dev, grad_coef, numels, (hipStream_t)stream);
 }
+extern "C" int ff_adamw_step_acc(const ff_adamw_desc* d, int state_dtype, void* const* params, const float* const* grads32, void* const* exp_avg,
+                                 void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef,
+                                 const long long* numels, ff_stream_t stream) {
+    return ff::adamw_launch(d, state_dtype, params, (const void* const*)grads32, exp_avg, exp_avg_sq, master, lr_dev, grad_coef, numels,
+                            (hipStream_t)stream, true);
+}
 extern "C" long long ff_grad_sumsq_partials(int n_tensors, const long long* numels) {
     return n_tensors > 0 && numels ? ff::grad_slots(n_tensors, numels) : 0;
 }
@@ -424,4 +525,45 @@ extern "C" int ff_scale_grads(int dtype, int n_tensors, void* const* grads, cons
         if (dtype == FF_DTYPE_F32) grad_scale_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
         else grad_scale_kernel<bf16><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
     });
+}
+extern "C" int ff_grad_accumulate(int dtype, int n_tensors, const void* const* grads, float* const* acc, const long long* numels, float scale,
+                                  int overwrite, ff_stream_t stream) {
+    using namespace ff;
+    const char* what = "ff_grad_accumulate";
+    FF_CHECK(dtype == FF_DTYPE_F32 || dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "%s: dtype %d", what, dtype);
+    FF_CHECK(n_tensors >= 0 && (n_tensors == 0 || (grads && acc && numels)), FF_ERR_SHAPE, "%s: null argument", what);
+    AccTable t;
+    t.scale = scale;
+    int i = 0;
+    while (i < n_tensors) {                         // launches of <= kAdamTensors tensors and <= kGradMaxBlocks workgroups, as grad_launches
+        int cnt = 0;
+        long long blocks = 0;
+        while (i < n_tensors && cnt < kAdamTensors) {
+            if (numels[i] > 0) {
+                const long long b = (numels[i] + kAdamChunk - 1) / kAdamChunk;
+                FF_CHECK(b <= kGradMaxBlocks, FF_ERR_SHAPE, "%s: tensor %d has %lld elements", what, i, numels[i]);
+                if (blocks + b > kGradMaxBlocks) break;
+                FF_CHECK(grads[i] && acc[i], FF_ERR_SHAPE, "%s: tensor %d has a null pointer", what, i);
+                t.g[cnt] = grads[i]; t.a[cnt] = acc[i]; t.n[cnt] = numels[i];
+                t.block_start[cnt] = (int)blocks;
+                blocks += b;
+                cnt++;
+            }
+            i++;
+        }
+        if (!cnt) break;
+        t.block_start[cnt] = (int)blocks;
+        t.count = cnt;
+        const dim3 grid((unsigned)blocks);
+        hipStream_t s = (hipStream_t)stream;
+        if (dtype == FF_DTYPE_F32) {
+            if (overwrite) grad_accumulate_kernel<float, true><<<grid, 256, 0, s>>>(t);
+            else grad_accumulate_kernel<float, false><<<grid, 256, 0, s>>>(t);
+        } else {
+            if (overwrite) grad_accumulate_kernel<bf16, true><<<grid, 256, 0, s>>>(t);
+            else grad_accumulate_kernel<bf16, false><<<grid, 256, 0, s>>>(t);
+        }
+        FF_TRY(check_launch(what));
+    }
+    return FF_OK;
 }

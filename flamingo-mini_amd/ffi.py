@@ -16,7 +16,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # kernels' A/B switches read the environment), or a path; default = the shipped library
 _which = os.environ.get("FLAMINGO_FUSION_LIB", "")
 LIB_PATH = os.path.join(PKG_DIR, "libflamingo_fusion_debug.so") if _which == "debug" else (_which or os.path.join(PKG_DIR, "libflamingo_fusion.so"))
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 FF_OK = 0
 DTYPE_F32, DTYPE_BF16 = 0, 1
@@ -147,6 +147,8 @@ _SIGNATURES = {
     "ff_grad_sumsq_reduce": (_I, [_P, C.c_longlong, _P, _I, _P]),
     "ff_grad_clip_coef": (_I, [_P, C.c_float, _P, _P, _P]),
     "ff_scale_grads": (_I, [_I, _I, _P, _P, _P, _P]),
+    "ff_grad_accumulate": (_I, [_I, _I, _P, _P, _P, C.c_float, _I, _P]),
+    "ff_adamw_step_acc": (_I, [C.POINTER(AdamWDesc), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ff_xattn_block_bwd_kv": (_I, [C.POINTER(XattnDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _SZ, _P]),
     "ff_kv_project_workspace_bytes": (_SZ, [C.POINTER(KvProjDesc), _I]),
     "ff_kv_project_fwd": (_I, [C.POINTER(KvProjDesc), _P, _P, _P, _P, _SZ, _P]),

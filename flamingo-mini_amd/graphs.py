@@ -108,19 +108,43 @@ def _check_sync_exchange(where: str) -> None:
 class GraphedTrainStep:
     """check_every: every that many replays (and after the warm-up, and in close()) the step reads the error word of the in-launch hand-offs
     of the fused cross-attention kernels (functional.check_sync_exchange - one device synchronisation) and raises SyncExchangeTimeout if a
-    launch was ever denied co-residency: a replayed graph cannot train through a timed-out hand-off unnoticed.  0 = only at those two points."""
+    launch was ever denied co-residency: a replayed graph cannot train through a timed-out hand-off unnoticed.  0 = only at those two points.
+
+    micro_batches=k > 1: gradient accumulation inside the one graph.  Every tensor of the batch is split into k equal chunks along dim 0 and
+    the captured step is k x (forward, backward, optimizer.accumulate(1 / k)) followed by one optimizer.step(): the gradients are summed in
+    fp32 accumulators (FusedAdamW.accumulate), and every backward finds `.grad is None`, so the deferred weight-gradient launches stay.  The
+    returned loss is the mean of the k micro-batch losses - the HF Trainer's convention, a mean of means: it equals the full batch's loss
+    only when every micro-batch holds the same number of target tokens.  Needs an optimizer with accumulate() and no reducer
+    (data-parallel accumulation keeps its no_sync() path)."""
 
     def __init__(self, model: torch.nn.Module, optimizer: Optional[torch.optim.Optimizer], example_batch: Dict[str, torch.Tensor],
                  warmup: int = 3, loss_fn: Optional[Callable] = None, reducer=None, check_every: int = 128,
-                 autocast: Optional[torch.dtype] = None):
+                 autocast: Optional[torch.dtype] = None, micro_batches: int = 1):
+        k = int(micro_batches)
+        if k < 1:
+            raise ValueError(f"micro_batches must be >= 1, got {micro_batches}")
+        if k > 1:
+            if not hasattr(optimizer, "accumulate"):
+                raise ValueError("GraphedTrainStep(micro_batches > 1) needs an optimizer with accumulate() (FusedAdamW)")
+            if reducer is not None:
+                raise ValueError("GraphedTrainStep(micro_batches > 1) cannot be combined with a reducer: data-parallel accumulation "
+                                 "keeps its no_sync() path")
+            for name, v in example_batch.items():
+                if torch.is_tensor(v) and (v.dim() == 0 or v.shape[0] % k):
+                    raise ValueError(f"GraphedTrainStep(micro_batches={k}): batch tensor {name!r} of shape {tuple(v.shape)} cannot be "
+                                     f"split into {k} equal chunks along dim 0")
         if not torch.cuda.is_available():
             raise RuntimeError("GraphedTrainStep needs a GPU")
         self.model, self.optimizer, self.reducer = model, optimizer, reducer
+        self.micro_batches = k
         self.check_every, self._replays = int(check_every), 0
         self.autocast = autocast        # torch.bfloat16 / torch.float16: the forward runs under torch.autocast (fp32 parameters, the reference's recipe)
         _refuse_live_autograd_graphs(model)
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
         self._loss_fn = loss_fn or (lambda out: out.loss)
+        # micro-batch i = views of rows [i n / k, (i + 1) n / k) of the static inputs: a replay reads what __call__ copied in
+        self._micro = None if k == 1 else [{name: (v[i * (v.shape[0] // k):(i + 1) * (v.shape[0] // k)] if torch.is_tensor(v) else v)
+                                            for name, v in self.static.items()} for i in range(k)]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                       # warm-up off the default stream: lazy init, autotuning, allocator pools
@@ -158,6 +182,8 @@ class GraphedTrainStep:
 
     def _eager(self) -> torch.Tensor:
         self.model.zero_grad(set_to_none=True)              # gradients are re-created (not accumulated) by every backward
+        if self._micro is not None:
+            return self._eager_micro_batches()
         with _autocast(self.autocast):
             loss = self._loss_fn(self.model(**self.static))
         loss.backward()
@@ -166,6 +192,20 @@ class GraphedTrainStep:
         if self.optimizer is not None:
             self.optimizer.step()
         return loss
+
+    def _eager_micro_batches(self) -> torch.Tensor:
+        k = self.micro_batches
+        if hasattr(self.optimizer, "reset_accumulation"):
+            self.optimizer.reset_accumulation()             # (a cycle somebody left open would be stepped with this one)
+        total = None
+        for micro in self._micro:
+            with _autocast(self.autocast):
+                loss = self._loss_fn(self.model(**micro))
+            loss.backward()
+            self.optimizer.accumulate(1.0 / k)              # .grad -> fp32 accumulator, .grad = None: the next backward defers again
+            total = loss.detach() if total is None else total + loss.detach()
+        self.optimizer.step()
+        return total / k
 
     def __call__(self, batch: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
         """Replay one step.  `batch` (same keys / shapes / dtypes as the example) is copied into the static inputs; None reuses them.

@@ -19,7 +19,16 @@ reduction to the norm and the coefficient on the device (ff_grad_sumsq_reduce, f
 gradient by the coefficient as it reads it (ff_adamw_step_clipped); `.grad` stays unscaled.  `grad_norm` is the pre-clip norm of the last
 step (what HF logs as grad_norm), a device scalar that keeps its storage, so it is valid after a graph replay too.  Nothing synchronises
 with the host: GraphedTrainStep captures the clipped step as it is.  With data parallelism, GradientAllReducer.finish() has averaged the
-gradients before step() reads them, so the norm is the global one; ShardedAdamW takes its own max_grad_norm."""
+gradients before step() reads them, so the norm is the global one; ShardedAdamW takes its own max_grad_norm.
+
+Gradient accumulation (the reference's recipe sets `--gradient_accumulation_steps`): `accumulate(scale)` after every micro-batch's backward
+folds each `.grad` into an fp32 accumulator of the parameter's shape (ff_grad_accumulate: one fused multiply-add per element, the first
+fold of a step overwrites, so nothing is zeroed) and sets `.grad = None`; the next `step()` takes the accumulators as the gradients
+(ff_adamw_step_acc, the clip norm from ff_grad_sumsq over them).  Against autograd's own `grad += g`: the sum of bf16 gradients is kept in
+fp32 instead of being rounded to 8 bits after every micro-batch, and because every backward finds `.grad is None` the gated blocks keep
+their deferred, grouped weight-gradient launches in every micro-batch.  The accumulators cost 4 bytes per trainable parameter and live
+outside `state`, so `state_dict()` stays torch.optim.AdamW's.  Nothing synchronises: graphs.GraphedTrainStep(micro_batches=k) captures
+k x (forward, backward, accumulate(1 / k)) + step() as one graph."""
 from __future__ import annotations
 
 import ctypes as C
@@ -46,6 +55,9 @@ class FusedAdamW(torch.optim.Optimizer):
             state_dtype = torch.float32                   # fp32 masters go with fp32 moments
         self.master_dtype, self.state_dtype = master_dtype, state_dtype
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, capturable=capturable))
+        self._acc = {}                                    # accumulate(): parameter -> its fp32 accumulator (kept from cycle to cycle)
+        self._acc_fresh = set()                           # ... the parameters folded at least once since the last step()
+        self._acc_open = False                            # ... a cycle is open: step() reads the accumulators
         if self.max_grad_norm is not None and len({p.device for g in self.param_groups for p in g["params"]}) > 1:
             raise ValueError("FusedAdamW(max_grad_norm=...) needs every parameter on one device (the global norm is reduced on it)")
 
@@ -54,6 +66,46 @@ class FusedAdamW(torch.optim.Optimizer):
         """max_grad_norm: the total L2 norm of the gradients (grad_scale applied) BEFORE clipping, from the last step - a 0-dim fp32 device
         tensor whose storage is the same every step (None before the first step, and without max_grad_norm)."""
         return None if self._clip is None else self._clip["norm"]
+
+    @torch.no_grad()
+    def accumulate(self, scale: float = 1.0) -> None:
+        """Fold every `.grad` into the parameter's fp32 accumulator, acc = (first fold since the last step() ? 0 : acc) + scale * grad, and
+        set `.grad = None` (one ff_grad_accumulate call per gradient dtype and device).  Opens an accumulation cycle: the next step() reads
+        the accumulators.  Enqueues on the current stream only - no allocation after the first cycle, no synchronisation (capturable)."""
+        from . import functional as _F
+        lib = ffi.lib()
+        calls = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                ffi.require_cuda(p, g)
+                if g.dtype not in (torch.float32, torch.bfloat16) or not g.is_contiguous() or g.numel() != p.numel():
+                    raise ffi.FusionLibraryError("FusedAdamW.accumulate needs contiguous float32 / bfloat16 gradients of the parameter's size")
+                acc = self._acc.get(p)
+                if acc is None or acc.shape != p.shape or acc.device != g.device:
+                    acc = self._acc[p] = _F._new(p.shape, torch.float32, g.device)      # never zeroed: the first fold overwrites
+                    self._acc_fresh.discard(p)
+                calls.setdefault((g.dtype, g.device, p not in self._acc_fresh), []).append((p, g, acc))
+        for (dtype, device, overwrite), items in calls.items():      # (a parameter whose first gradient of the cycle comes late: its own call)
+            n = len(items)
+            ffi.check(lib.ff_grad_accumulate(ffi.dtype_code(dtype), n, ffi.ptr_array([g for _, g, _ in items]), ffi.ptr_array([a for _, _, a in items]),
+                                             (C.c_longlong * n)(*[g.numel() for _, g, _ in items]), float(scale), int(overwrite),
+                                             ffi.stream_handle(device)), "ff_grad_accumulate")
+            for p, _, _ in items:
+                p.grad = None
+                self._acc_fresh.add(p)
+        self._acc_open = True
+
+    def accumulated_grad(self, p) -> Optional[torch.Tensor]:
+        """The fp32 accumulator of `p` if it was folded into since the last step(), else None."""
+        return self._acc[p] if p in self._acc_fresh else None
+
+    def reset_accumulation(self) -> None:
+        """Drop an open accumulation cycle without stepping (the accumulators keep their storage; the next accumulate() overwrites)."""
+        self._acc_fresh.clear()
+        self._acc_open = False
 
     @torch.no_grad()
     def step(self, closure=None, *, only=None, advance: bool = True, grad_coef: Optional[torch.Tensor] = None):
@@ -73,6 +125,13 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        acc = self._acc_open                              # accumulate() was called since the last step: the accumulators are the gradients
+        if acc:
+            if only is not None:
+                raise ValueError("FusedAdamW.step(only=...) cannot be combined with accumulate(): the accumulation cycle is stepped as a whole")
+            if any(p.grad is not None for group in self.param_groups for p in group["params"]):
+                raise RuntimeError("FusedAdamW.step(): an accumulation cycle is open and a parameter still holds a .grad - the last backward "
+                                   "was not folded; call accumulate() after every backward (or reset_accumulation() to drop the cycle)")
         lib = ffi.lib()
         if advance and not torch.cuda.is_current_stream_capturing():
             # an eager training loop cannot run through a timed-out in-launch hand-off of the fused cross-attention kernels unnoticed:
@@ -83,14 +142,15 @@ class FusedAdamW(torch.optim.Optimizer):
             only = frozenset(only)
             if not all(g.get("capturable", False) for g in self.param_groups):
                 raise ValueError("FusedAdamW.step(only=...) needs capturable=True (step counts live in device scalars shared by the partial calls)")
-        coef = self._clip_coef(lib) if self.max_grad_norm is not None else grad_coef
+        coef = self._clip_coef(lib, acc) if self.max_grad_norm is not None else grad_coef
         for gi, group in enumerate(self.param_groups):
             capturable = group.get("capturable", False)
             if capturable and advance:
                 self._advance_device_steps(group)
-            for bucket in self._buckets(gi, group, only):
+            for bucket in self._buckets(gi, group, only, acc):
                 params, grad_ptrs, n = bucket["params"], bucket["grad_ptrs"], len(bucket["params"])
-                self._refresh_grad_ptrs(bucket)
+                if not acc:
+                    self._refresh_grad_ptrs(bucket)
                 lr_dev = None
                 if capturable:
                     step, step_dev = 0, group["_step_dev"][bucket["device"]].data_ptr()
@@ -100,7 +160,11 @@ class FusedAdamW(torch.optim.Optimizer):
                     step, step_dev = bucket["step"], None
                 desc = ffi.AdamWDesc(bucket["dtype_code"], n, step, group["lr"], group["betas"][0], group["betas"][1], group["eps"],
                                      group["weight_decay"], group["grad_scale"], step_dev)
-                if coef is None:
+                if acc:
+                    ffi.check(lib.ff_adamw_step_acc(desc, bucket["state_code"], bucket["param_ptrs"], bucket["acc_ptrs"], bucket["m_ptrs"], bucket["v_ptrs"],
+                                                    bucket["w_ptrs"], lr_dev, None if coef is None else coef.data_ptr(), bucket["numels"],
+                                                    ffi.stream_handle(bucket["device"])), "ff_adamw_step_acc")
+                elif coef is None:
                     ffi.check(lib.ff_adamw_step_mixed(desc, bucket["state_code"], bucket["param_ptrs"], grad_ptrs, bucket["m_ptrs"], bucket["v_ptrs"],
                                                       bucket["w_ptrs"], lr_dev, bucket["numels"], ffi.stream_handle(bucket["device"])),
                               "ff_adamw_step_mixed")
@@ -108,6 +172,8 @@ class FusedAdamW(torch.optim.Optimizer):
                     ffi.check(lib.ff_adamw_step_clipped(desc, bucket["state_code"], bucket["param_ptrs"], grad_ptrs, bucket["m_ptrs"], bucket["v_ptrs"],
                                                         bucket["w_ptrs"], lr_dev, coef.data_ptr(), bucket["numels"], ffi.stream_handle(bucket["device"])),
                               "ff_adamw_step_clipped")
+        if acc:
+            self.reset_accumulation()                     # the cycle is closed: the next accumulate() overwrites
         return loss
 
     @staticmethod
@@ -118,10 +184,11 @@ class FusedAdamW(torch.optim.Optimizer):
                 raise ffi.FusionLibraryError("FusedAdamW needs contiguous gradients of the parameter's dtype")
             bucket["grad_ptrs"][i] = g.data_ptr()
 
-    def _clip_coef(self, lib) -> Optional[torch.Tensor]:
+    def _clip_coef(self, lib, acc: bool = False) -> Optional[torch.Tensor]:
         """max_grad_norm: enqueue the global norm of every gradient of every group (grad_scale applied) and the clip coefficient; returns
-        the device scalar the AdamW launches of this step read.  No host synchronisation (capturable)."""
-        buckets = [(group, b) for gi, group in enumerate(self.param_groups) for b in self._buckets(gi, group)]
+        the device scalar the AdamW launches of this step read.  No host synchronisation (capturable).  acc: the gradients are the fp32
+        accumulators."""
+        buckets = [(group, b) for gi, group in enumerate(self.param_groups) for b in self._buckets(gi, group, None, acc)]
         if not buckets:
             return None
         devices = {b["device"] for _, b in buckets}
@@ -139,8 +206,10 @@ class FusedAdamW(torch.optim.Optimizer):
         stream = ffi.stream_handle(device)
         partials, total, off = clip["partials"], clip["partials"].numel(), 0
         for (group, b), k in zip(buckets, slots):     # slots continue from bucket to bucket (dtypes, groups)
-            self._refresh_grad_ptrs(b)
-            ffi.check(lib.ff_grad_sumsq(b["dtype_code"], len(b["params"]), b["grad_ptrs"], b["numels"], float(group["grad_scale"] or 1.0),
+            if not acc:
+                self._refresh_grad_ptrs(b)
+            ffi.check(lib.ff_grad_sumsq(ffi.DTYPE_F32 if acc else b["dtype_code"], len(b["params"]), b["acc_ptrs"] if acc else b["grad_ptrs"], b["numels"],
+                                        float(group["grad_scale"] or 1.0),
                                         partials.data_ptr() + 4 * off, total - off, stream), "ff_grad_sumsq")
             off += k
         ffi.check(lib.ff_grad_sumsq_reduce(partials.data_ptr(), off, clip["sum"].data_ptr(), 0, stream), "ff_grad_sumsq_reduce")
@@ -156,21 +225,29 @@ class FusedAdamW(torch.optim.Optimizer):
                     t.fill_(float(group["lr"]))
                     group.setdefault("_lr_on_dev", {})[dev] = group["lr"]
 
-    def _buckets(self, gi, group, only=None):
+    def _buckets(self, gi, group, only=None, acc=False):
         """Parameters with a gradient, grouped by (dtype, device, step count); the pointer tables of everything that does not
-        change between steps (parameters, moments, sizes) are built once and reused while the same parameters have gradients."""
-        active = [p for p in group["params"] if p.grad is not None and (only is None or id(p) in only)]
+        change between steps (parameters, moments, sizes) are built once and reused while the same parameters have gradients.
+        acc: the parameters folded by accumulate() in the open cycle instead, their fp32 accumulators as `acc_ptrs` (the same cache slot,
+        so the host-mode step count has one owner whichever kind of step ran last)."""
+        if acc:
+            active = [p for p in group["params"] if p in self._acc_fresh]
+        else:
+            active = [p for p in group["params"] if p.grad is not None and (only is None or id(p) in only)]
         cache = self.__dict__.setdefault("_bucket_cache", {})
         key = tuple(id(p) for p in active)
+        if acc:
+            key = ("acc",) + key
         slot = gi if only is None else (gi, only)
         hit = cache.get(slot)
-        if hit is not None and hit[0] == key and all(b["param_ptrs"][0] == b["params"][0].data_ptr() for b in hit[1]):
+        if hit is not None and hit[0] == key and all(b["param_ptrs"][0] == b["params"][0].data_ptr() for b in hit[1]) and \
+                (not acc or all(b["acc_ptrs"][0] == self._acc[b["params"][0]].data_ptr() for b in hit[1])):
             return hit[1]
         self._sync_host_steps()
         from . import functional as _F
         table = {}
         for p in active:
-            ffi.require_cuda(p, p.grad)
+            ffi.require_cuda(p, self._acc[p] if acc else p.grad)
             if not p.is_contiguous():
                 raise ffi.FusionLibraryError("FusedAdamW needs contiguous parameters")
             st = self.state[p]
@@ -190,6 +267,7 @@ class FusedAdamW(torch.optim.Optimizer):
             buckets.append(dict(params=params, device=device, dtype_code=ffi.dtype_code(dtype), step=step, state_code=ffi.dtype_code(sdt),
                                 w_ptrs=ffi.ptr_array([self.state[p]["master"] for p in params]) if has_master else None,
                                 param_ptrs=ffi.ptr_array(params), grad_ptrs=(C.c_void_p * n)(),
+                                acc_ptrs=ffi.ptr_array([self._acc[p] for p in params]) if acc else None,
                                 m_ptrs=ffi.ptr_array([self.state[p]["exp_avg"] for p in params]),
                                 v_ptrs=ffi.ptr_array([self.state[p]["exp_avg_sq"] for p in params]),
                                 numels=(C.c_longlong * n)(*[p.numel() for p in params])))
@@ -202,7 +280,7 @@ class FusedAdamW(torch.optim.Optimizer):
         counters = group.setdefault("_step_dev", {})
         lrs = group.setdefault("_lr_dev", {})
         for p in group["params"]:
-            if p.grad is not None and p.device not in counters:
+            if (p.grad is not None or p in self._acc_fresh) and p.device not in counters:
                 host_steps = [int(self.state[q]["step"]) for q in group["params"] if q in self.state and "step" in self.state[q]]
                 counters[p.device] = torch.full((), float(max(host_steps, default=0)), dtype=torch.float32, device=p.device)
                 lrs[p.device] = torch.full((), float(group["lr"]), dtype=torch.float32, device=p.device)

@@ -46,7 +46,8 @@ enum { FF_ACT_NONE = -1, FF_ACT_GELU = 0, FF_ACT_SQRELU = 1, FF_ACT_RELU = 2 }; 
 
 int ff_version(void);          /* ABI version, bumped on any signature change (3: ff_gemm_desc.tile / .stages replace ff_gemm_set_tuning;
                                 * 4: ff_xattn_desc.sync, ff_xattn_sync_bytes / _status, ff_resampler_layer_* / _prologue_* / _epilogue_*;
-                                * 5: gradient clipping: ff_grad_sumsq*, ff_grad_clip_coef, ff_scale_grads, ff_adamw_step_clipped) */
+                                * 5: gradient clipping: ff_grad_sumsq*, ff_grad_clip_coef, ff_scale_grads, ff_adamw_step_clipped;
+                                * 6: fp32 gradient accumulation: ff_grad_accumulate, ff_adamw_step_acc) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -409,6 +410,22 @@ int ff_grad_sumsq(int dtype, int n_tensors, const void* const* grads, const long
 int ff_grad_sumsq_reduce(const float* partials, long long n_partials, double* sum, int accumulate, ff_stream_t stream);
 int ff_grad_clip_coef(const double* sum, float max_norm, float* norm, float* coef, ff_stream_t stream);
 int ff_scale_grads(int dtype, int n_tensors, void* const* grads, const long long* numels, const float* coef, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * fp32 gradient accumulation over micro-batches (ABI 6): HF Trainer's --gradient_accumulation_steps (training/train.sh) without the bf16
+ * `grad += g` of autograd, which rounds the running sum to 8 significant bits after every micro-batch.
+ *   ff_grad_accumulate     acc[i][e] = (overwrite ? 0 : acc[i][e]) + scale * (float)grads[i][e] - one fp32 fused multiply-add per element
+ *                          (overwrite: the rounded product).  grads: n_tensors contiguous tensors of `dtype` (FF_DTYPE_F32 / FF_DTYPE_BF16),
+ *                          never written; acc: fp32, same sizes.  overwrite != 0 never READS acc (it may hold anything, NaN included): the
+ *                          first micro-batch of a step needs no memset pass.  Tensors of any alignment; zero-element tensors are skipped.
+ *   ff_adamw_step_acc      ff_adamw_step_mixed / _clipped reading FP32 gradients whatever d->dtype is (the accumulators); grad_coef may be
+ *                          NULL (unclipped).  The clip norm over accumulators is ff_grad_sumsq(FF_DTYPE_F32, ...).
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_grad_accumulate(int dtype, int n_tensors, const void* const* grads, float* const* acc, const long long* numels, float scale,
+                       int overwrite, ff_stream_t stream);
+int ff_adamw_step_acc(const ff_adamw_desc* d, int state_dtype, void* const* params, const float* const* grads32, void* const* exp_avg,
+                      void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef, const long long* numels,
+                      ff_stream_t stream);
 
 
 /* ------------------------------------------------------------------------------------------------------
