@@ -7,6 +7,28 @@
 
 namespace ff {
 
+// Which products round on their own is written out here, not left to the compiler: it contracts the same expression in one pair of a
+// vector's elements and not in the next, and differently once the code around it changes.  The one fused step is the fmaf below.
+#pragma clang fp contract(off)
+
+// One element, the plain formula: right down to x = -26 and what every activation a model produces takes.
+template <bool BWD> FF_DEV float quick_gelu_plain(float x, float g) {
+    const float s = 1.f / (1.f + __expf(-1.702f * x));
+    return BWD ? g * s * fmaf(1.702f * x, 1.f - s, 1.f) : x * s;
+}
+
+// One element below x = -26: exp(-1.702 x) is inf from x = -52 down (the sigmoid 0 where x sigmoid is still 1e-37), and before that the
+// sigmoid is a denormal.  Here exp(-1.702 x) is taken 2^-64 times smaller where it exceeds 2^64, so that neither it nor the sigmoid,
+// 2^64 times larger, leaves the normal range; the result is multiplied by 2^-64 last: exact, or the one rounding into a denormal.
+// Where the exponential is below 2^64 this is the plain formula, bit for bit (__expf(y) is exp2(y log2 e)).
+template <bool BWD> FF_DEV float quick_gelu_far(float x, float g) {
+    const float w = (-1.702f * x) * 1.44269504f;
+    const bool far = w > 64.f;
+    const float u = far ? 0x1p-64f : 1.f;
+    const float s = 1.f / (u + __builtin_amdgcn_exp2f(far ? w - 64.f : w));
+    return (BWD ? g * s * fmaf(1.702f * x, 1.f - s * u, 1.f) : x * s) * u;
+}
+
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void quick_gelu_kernel(long long n, const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ out) {
     pin_args(n, x, dy, out);
@@ -16,18 +38,23 @@ __global__ __launch_bounds__(256) void quick_gelu_kernel(long long n, const T* _
         float v[N], g[N];
         Vec<T>::load(x + i * N, v);
         if (BWD) Vec<T>::load(dy + i * N, g);
+        float lo = v[0];
 #pragma unroll
-        for (int e = 0; e < N; e++) {
-            const float s = 1.f / (1.f + __expf(-1.702f * v[e]));
-            v[e] = BWD ? g[e] * s * (1.f + 1.702f * v[e] * (1.f - s)) : v[e] * s;
+        for (int e = 1; e < N; e++) lo = fminf(lo, v[e]);
+        if (lo < -26.f) {   // some element of this vector needs the scaled form (never, for activations of a trained tower)
+#pragma unroll
+            for (int e = 0; e < N; e++) v[e] = quick_gelu_far<BWD>(v[e], BWD ? g[e] : 0.f);
+        } else {
+#pragma unroll
+            for (int e = 0; e < N; e++) v[e] = quick_gelu_plain<BWD>(v[e], BWD ? g[e] : 0.f);
         }
         Vec<T>::store(out + i * N, v);
     }
     if (blockIdx.x == 0) {   // ragged tail
         const long long i = nvec * N + threadIdx.x;
         if (i < n) {
-            const float xv = to_f32(x[i]), s = 1.f / (1.f + __expf(-1.702f * xv));
-            out[i] = from_f32<T>(BWD ? to_f32(dy[i]) * s * (1.f + 1.702f * xv * (1.f - s)) : xv * s);
+            const float xv = to_f32(x[i]), gv = BWD ? to_f32(dy[i]) : 0.f;
+            out[i] = from_f32<T>(xv < -26.f ? quick_gelu_far<BWD>(xv, gv) : quick_gelu_plain<BWD>(xv, gv));
         }
     }
 }

@@ -3,6 +3,8 @@
 // The reference materialises the shifted copy, a log-softmax and its backward (~10 kernels over batch*seq*vocab elements);
 // here the forward reads the logits once (online max / sum-exp per row, one workgroup per token) and the backward reads them
 // once more and writes d logits directly in the unshifted layout (last position = 0).  fp32 math on fp32 / bf16 logits.
+#include <cfloat>
+
 #include "ff_common.h"
 #include "ff_internal.h"
 
@@ -34,7 +36,10 @@ __global__ __launch_bounds__(256) void shifted_ce_fwd_kernel(int L, int V, const
     pin_args(L, V, logits, labels, ignore_index, loss_row, lse);
     const int r = blockIdx.x, b = r / (L - 1), i = r - b * (L - 1);
     const T* row = logits + ((long long)b * L + i) * V;
-    float m = -INFINITY, s = 0.f;
+    // (m, s) stands for s exp(m): with s = 0 any finite m is the empty sum.  m must not start at -inf: a thread whose first logit is -inf
+    // (a masked vocabulary entry) would add exp(-inf - -inf) = NaN.  From -FLT_MAX a -inf logit adds exp(-inf) = 0 and every other first
+    // logit is a new maximum (or equal: + exp(0)); +inf and NaN logits still end in a NaN row, as in torch.
+    float m = -FLT_MAX, s = 0.f;
     for_row_vectors(row, V, [&](int, float x) {
         if (x > m) { s = s * __expf(m - x) + 1.f; m = x; }
         else s += __expf(x - m);
@@ -42,9 +47,11 @@ __global__ __launch_bounds__(256) void shifted_ce_fwd_kernel(int L, int V, const
     // combine (m, s) pairs: wave, then block
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
+        // each product rounds on its own (no fma): both lanes of a pair get the same bits, and finite rows keep the lse they always had
+#pragma clang fp contract(off)
         const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
         const float mn = fmaxf(m, m2);
-        s = (m == -INFINITY ? 0.f : s * __expf(m - mn)) + (m2 == -INFINITY ? 0.f : s2 * __expf(m2 - mn));
+        s = s * __expf(m - mn) + s2 * __expf(m2 - mn);
         m = mn;
     }
     const int w = threadIdx.x >> 6;

@@ -817,10 +817,20 @@ def xattn_block(y: torch.Tensor, visual_features: Optional[torch.Tensor], tt: to
 # ----------------------------------------------------------------------------------------------------
 # QuickGELU of the CLIP tower
 # ----------------------------------------------------------------------------------------------------
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """t, contiguous and on the 16-byte grid the vector kernels need: a contiguous view that starts off it (flat[1:1 + n]) is copied"""
+    t = t.contiguous()
+    if t.data_ptr() % 16:
+        a = _new_like(t)
+        a.copy_(t)
+        return a
+    return t
+
+
 class _QuickGeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        x = x.contiguous()
+        x = _aligned16(x)
         y = _new_like(x)
         ffi.check(ffi.lib().ff_quick_gelu_fwd(ffi.dtype_code(x.dtype), x.numel(), x.data_ptr(), y.data_ptr(), ffi.stream_handle(x.device)),
                   "ff_quick_gelu_fwd")
@@ -830,7 +840,7 @@ class _QuickGeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = _aligned16(dy)
         dx = _new_like(x)
         ffi.check(ffi.lib().ff_quick_gelu_bwd(ffi.dtype_code(x.dtype), x.numel(), x.data_ptr(), dy.data_ptr(), dx.data_ptr(),
                                               ffi.stream_handle(x.device)), "ff_quick_gelu_bwd")
@@ -866,7 +876,13 @@ class _ShiftedCEFn(torch.autograd.Function):
         lib = ffi.lib()
         logits, labels, lse = ctx.saved_tensors
         b, L, V = logits.shape
-        dlogits = _new_like(logits)
+        # the kernel writes 16-byte vectors at the logits' own phase relative to the 16-byte grid: a contiguous view that starts off the
+        # grid gets its gradient at the same phase of a buffer one vector longer
+        phase = logits.data_ptr() % 16 // logits.element_size()
+        if phase:
+            dlogits = _new(logits.numel() + 16 // logits.element_size(), logits.dtype, logits.device)[phase:phase + logits.numel()].view(b, L, V)
+        else:
+            dlogits = _new_like(logits)
         g = grad_rows.contiguous().float()
         ffi.check(lib.ff_shifted_ce_bwd(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ctx.ignore_index,
                                         lse.data_ptr(), g.data_ptr(), dlogits.data_ptr(), ffi.stream_handle(logits.device)), "ff_shifted_ce_bwd")

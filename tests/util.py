@@ -259,3 +259,130 @@ def adamw_step_ok(old, new, g, storages, step, lr, beta1, beta2, eps, weight_dec
         if not ok:
             bad.append(f"{name}: element {idx} is {worst:.4g} x its bound")
     return not bad, "; ".join(bad)
+
+
+# ---- shifted cross-entropy and QuickGELU, element by element (tests/test_hip_loss_bounds.py; the checkers' own tests: test_guarded_checks.py) ----
+# rel() over d logits is dominated by the onehot element (about -g) of every row: the softmax part, the scalar head and tail columns of a row
+# and any single row are held far more loosely than its figure suggests.  These compare every element with float64 from what the kernel saw.
+def shifted_ce_ref(logits, labels, g, ignore_index=-100):
+    """Shifted next-token cross-entropy in float64 from the logits as stored (b, L, V), labels (b, L), g (b (L - 1),) the gradient of each
+    loss row.  A dict of float64 CPU tensors:
+      lse, loss (b (L - 1),): logsumexp of row (b, i) and lse - x[label[b, i + 1]], 0 for an ignored label;
+      d (b, L, V): (exp(x - lse) - onehot) g, exactly 0 for the last position and for ignored rows;
+      t_lse = |lse| + 1, t_loss = |lse| + |x_t| + 1 (0 for an ignored label: its loss is exactly 0),
+      t_d = |g| (p (1 + |x - lse| + |lse|) + onehot): what a float32 rounding error of each is proportional to - the sum and its logarithm,
+      the subtraction, and for d the rounding of x - lse (and of lse itself) in the exponent; flush = 2^-126 |g|, a flushed denormal p."""
+    x, g = _t64(logits), _t64(g).reshape(-1)
+    lab = labels.detach().cpu().long()
+    b, L, V = x.shape
+    xs, tgt = x[:, :-1], lab[:, 1:]
+    valid = tgt != ignore_index
+    lse = torch.logsumexp(xs, dim=-1)
+    xt = xs.gather(-1, tgt.clamp(0, V - 1).unsqueeze(-1)).squeeze(-1)
+    loss = torch.where(valid, lse - xt, torch.zeros_like(lse))
+    p = (xs - lse.unsqueeze(-1)).exp()
+    onehot = torch.zeros_like(xs).scatter_(-1, tgt.clamp(0, V - 1).unsqueeze(-1), 1.0) * valid.unsqueeze(-1)
+    gr = (g.reshape(b, L - 1) * valid).unsqueeze(-1)
+    zero = torch.zeros_like(xs)
+    d, t_d, flush = (torch.zeros_like(x) for _ in range(3))
+    d[:, :-1] = torch.where(valid.unsqueeze(-1), (p - onehot) * gr, zero)
+    size = torch.where(p == 0, zero, p * (1.0 + (xs - lse.unsqueeze(-1)).abs() + lse.abs().unsqueeze(-1)))      # p = 0 at a -inf logit
+    t_d[:, :-1] = torch.where(valid.unsqueeze(-1), gr.abs() * (size + onehot), zero)
+    flush[:, :-1] = (2.0 ** -126 * gr.abs()).expand_as(xs)
+    return dict(lse=lse.reshape(-1), loss=loss.reshape(-1), d=d, t_lse=(lse.abs() + 1.0).reshape(-1),
+                t_loss=torch.where(valid, lse.abs() + xt.abs() + 1.0, torch.zeros_like(lse)).reshape(-1), t_d=t_d, flush=flush)
+
+
+def _elem_ratio(got, ref, bound):
+    """(worst |got - ref| / bound, its flat index): nothing excluded, NaN counts as inf, an exact match is 0 whatever the bound"""
+    got, ref, bound = _t64(got).reshape(-1), _t64(ref).reshape(-1), _t64(bound).reshape(-1)
+    assert got.shape == ref.shape == bound.shape, (got.shape, ref.shape, bound.shape)
+    if got.numel() == 0:
+        return 0.0, 0
+    err = (got - ref).abs()
+    ratio = torch.where((err == 0) | (got == ref), torch.zeros_like(err), torch.nan_to_num(err / bound, nan=float("inf"), posinf=float("inf")))
+    i = int(torch.argmax(ratio))
+    return float(ratio[i]), i
+
+
+def _excess(got, ref, terms, fixed):
+    """max of (|got - ref| - fixed) / (2^-24 terms): the error left after the allowance that does not scale with the constant, in units of
+    one float32 rounding of the terms (what the constants below bound); an error within `fixed` alone counts as 0"""
+    got, ref, terms, fixed = (_t64(a).reshape(-1) for a in (got, ref, terms, fixed))
+    if got.numel() == 0:
+        return 0.0
+    over = (got - ref).abs() - fixed
+    ex = torch.where(~(over > 0) & ~torch.isnan(over), torch.zeros_like(over), over / (2.0 ** -24 * terms))
+    return float(torch.nan_to_num(ex, nan=float("inf"), posinf=float("inf")).max())
+
+
+# c_f, c_b, c_q: measured, not derived (tools/loss_c.py, on the CPU): the worst excess of the float32 restatements of the kernels in their
+# operation order (tests/loss_cases.py: ce_fwd_f32 - per-thread online (m, s) over head, vectors and tail, xor-shuffle combine, four-wave
+# combine -, ce_bwd_f32, quick_gelu_f32) over the float64 references, at exactly the inputs of tests/test_hip_loss_bounds.py, both dtypes;
+# times 4, the factor and the reasons of ADAMW_C: the device's __expf / logf and its FMA contraction cannot be shown on the CPU.
+# Worst excess: lse 1.06 (bf16 V = 3), loss 1.24 (bf16 V = 4099 with -inf in the last column) -> c_f = 4 x 1.24; d 0.95 (fp32 V = 1025,
+# -inf in the last column, off the grid; in bf16 half a storage ulp covers nearly everything: <= 0.53) -> c_b = 4 x 0.95; QuickGELU
+# 2.87 (the fp32 derivative at the largest size; forward 2.07; bf16 <= 0.27) -> c_q = 4 x 2.87.
+# On the MI355X (worst error / bound per checker, the [elem] entries of an FF_TOL_REPORT run of tests/test_hip_loss_bounds.py):
+#   lse 0.20 (fp32) / 0.21 (bf16), loss 0.22 / 0.25;
+#   d logits 0.39 in fp32 apart from the two one-dominant-logit patterns, 0.999: there every other p is below 2^-126, v_exp_f32 returns 0,
+#   and the error is p |g| against the 2^-126 |g| the bound's last term allows for exactly that; 0.999 in bf16: an exact result next to a
+#   rounding tie, where half a storage ulp is nearly all of the bound;
+#   QuickGELU forward 0.956 / derivative 0.942 in fp32, both at x = -59.76 and -59.70 on the ramp: results of 4e-43, denormals with eight
+#   significant bits, whose rounding is half a storage ulp - the restatement gives the same two figures at the same elements; 1.000 in
+#   bf16, rounding ties again.  No device figure is above 1.
+CE_C_F = 5.0
+CE_C_B = 3.8
+QGELU_C = 11.5
+
+
+def ce_bound_ok(what, got, ref, storage_dtype=torch.float32, c=None):
+    """One output of the shifted cross-entropy against shifted_ce_ref's dict, element by element, nothing excluded, NaN = inf:
+      what = "lse":   |lse - lse*| <= c_f 2^-24 (|lse*| + 1)
+             "loss":  |loss - loss*| <= c_f 2^-24 (|lse*| + |x_t| + 1)
+             "d":     |d - d*| <= 0.5 ulp_storage(d*) + c_b 2^-24 |g| (p (1 + |x - lse*| + |lse*|) + onehot) + 2^-126 |g|
+    Returns (ok, worst error / bound, flat index of that element)."""
+    if what == "d":
+        bound = 0.5 * _ulp(ref["d"], storage_dtype) + (CE_C_B if c is None else c) * 2.0 ** -24 * ref["t_d"] + ref["flush"]
+        bound = torch.where(ref["t_d"] + ref["flush"] == 0, torch.zeros_like(bound), bound)          # last position, ignored rows: exactly 0
+    else:
+        bound = (CE_C_F if c is None else c) * 2.0 ** -24 * ref["t_" + what]
+    worst, i = _elem_ratio(got, ref[what], bound)
+    _report("elem", worst)
+    return worst <= 1.0, worst, i
+
+
+def ce_excess(what, got, ref, storage_dtype=torch.float32):
+    if what == "d":
+        return _excess(got, ref["d"], ref["t_d"], torch.where(ref["t_d"] + ref["flush"] == 0, torch.zeros_like(ref["d"]),
+                                                              0.5 * _ulp(ref["d"], storage_dtype) + ref["flush"]))
+    return _excess(got, ref[what], ref["t_" + what], torch.zeros_like(ref[what]))
+
+
+QGELU_A = float(np.float32(1.702))
+
+
+def quick_gelu_ref(x, dy=None):
+    """(value, terms) in float64 from x (and dy) as stored, 1.702 rounded to float32 first as the kernel has it: x s with s = sigmoid(1.702 x),
+    or the derivative dy s (1 + 1.702 x (1 - s)).  terms = |value| (1 + 1.702 |x|), where for the derivative |value| is taken as the size of
+    its two terms, |dy| s (1 + 1.702 |x| (1 - s)): the same for x >= 0, but around x = -0.75, where the derivative changes sign, the two
+    cancel, and no float32 evaluation keeps an error proportional to the difference (among 4 M normal inputs some fall within 1e-6 of it)."""
+    x = _t64(x).reshape(-1)
+    s = torch.sigmoid(QGELU_A * x)
+    if dy is None:
+        value = x * s
+        return value, value.abs() * (1.0 + QGELU_A * x.abs())
+    dy = _t64(dy).reshape(-1)
+    return dy * s * (1.0 + QGELU_A * x * (1.0 - s)), dy.abs() * s * (1.0 + QGELU_A * x.abs() * (1.0 - s)) * (1.0 + QGELU_A * x.abs())
+
+
+def quick_gelu_bound_ok(got, ref, terms, storage_dtype, c=None):
+    """Element by element, nothing excluded, NaN = inf:   |got - ref| <= 0.5 ulp_storage(ref) + c_q 2^-24 terms      (quick_gelu_ref's)
+    Returns (ok, worst error / bound, flat index of that element)."""
+    worst, i = _elem_ratio(got, ref, 0.5 * _ulp(_t64(ref).reshape(-1), storage_dtype) + (QGELU_C if c is None else c) * 2.0 ** -24 * _t64(terms).reshape(-1))
+    _report("elem", worst)
+    return worst <= 1.0, worst, i
+
+
+def quick_gelu_excess(got, ref, terms, storage_dtype):
+    return _excess(got, ref, terms, 0.5 * _ulp(_t64(ref).reshape(-1), storage_dtype))
