@@ -27,6 +27,7 @@ struct AdamTable {
     const float* step_dev;   // capturable mode: the step count lives on the device (HIP-graph replays cannot change kernel arguments)
     const float* lr_dev;     // ... and so does the learning rate, when a scheduler is to stay effective under replay
     const float* grad_coef;  // CLIP kernels: device scalar multiplying every (grad_scale'd) gradient - the max-norm clip coefficient
+    const float* skip;       // GUARD kernels: device scalar, != 0 = the step is not taken (ff_grad_guard found a non-finite gradient)
 };
 
 // T: storage type of the parameters' compute copy and of the gradients; ST: storage type of the two moments; MASTER: the update
@@ -37,8 +38,14 @@ struct AdamTable {
 // CLIP: every gradient is also multiplied by *t.grad_coef (gradient clipping by global norm, ff_grad_clip_coef); the kernels without it
 // are the ones the unclipped step always ran.
 // GT: storage type of the gradients - T, or float where the gradients are the fp32 accumulators of ff_grad_accumulate (ff_adamw_step_acc).
-template <typename T, typename ST, bool MASTER, int VEC, int MODE = 0, bool CLIP = false, typename GT = T>
+// GUARD (implies CLIP; ff_adamw_step_guarded): every workgroup reads *t.skip first and returns before it touches a tensor when it is set -
+// a skipped launch is a no-op (no weight decay, no moment decay, no master write).  The read and the branch are wave-uniform.
+template <typename T, typename ST, bool MASTER, int VEC, int MODE = 0, bool CLIP = false, typename GT = T, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
+    static_assert(!GUARD || CLIP, "GUARD implies CLIP");
+    if constexpr (GUARD) {
+        if (*t.skip != 0.f) return;
+    }
     int ti = 0;
 #pragma unroll 1
     while (ti + 1 < t.count && (int)blockIdx.x >= t.block_start[ti + 1]) ti++;
@@ -150,32 +157,33 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     }
 }
 
-template <bool CLIP>
+template <bool CLIP, bool GUARD = false>
 static void adamw_dispatch(int dtype, bool master, int state_dtype, dim3 grid, hipStream_t stream, const AdamTable& t) {
     const dim3 block(256);
-    if (dtype == FF_DTYPE_F32) adamw_kernel<float, float, false, 4, 0, CLIP><<<grid, block, 0, stream>>>(t);
-    else if (master) adamw_kernel<bf16, float, true, 8, 1, CLIP><<<grid, block, 0, stream>>>(t);  // (master copy, gradients, moments: streamed nontemporally)
-    else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1, CLIP><<<grid, block, 0, stream>>>(t);
+    if (dtype == FF_DTYPE_F32) adamw_kernel<float, float, false, 4, 0, CLIP, float, GUARD><<<grid, block, 0, stream>>>(t);
+    else if (master) adamw_kernel<bf16, float, true, 8, 1, CLIP, bf16, GUARD><<<grid, block, 0, stream>>>(t);  // (master copy, gradients, moments: streamed nontemporally)
+    else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1, CLIP, bf16, GUARD><<<grid, block, 0, stream>>>(t);
     else {
         static const int mode = CLIP ? 1 : dbg_switch("FF_ADAMW_MODE", 1);
-        if (mode >= 1) adamw_kernel<bf16, bf16, false, 8, 1, CLIP><<<grid, block, 0, stream>>>(t);
+        if (mode >= 1) adamw_kernel<bf16, bf16, false, 8, 1, CLIP, bf16, GUARD><<<grid, block, 0, stream>>>(t);
         else if constexpr (!CLIP) adamw_kernel<bf16, bf16, false, 8><<<grid, block, 0, stream>>>(t);
     }
 }
 
 // bf16 parameters with fp32 gradients (ff_adamw_step_acc): the three storage modes of adamw_dispatch, MODE 1, GT = float
-template <bool CLIP>
+template <bool CLIP, bool GUARD = false>
 static void adamw_dispatch_acc(bool master, int state_dtype, dim3 grid, hipStream_t stream, const AdamTable& t) {
     const dim3 block(256);
-    if (master) adamw_kernel<bf16, float, true, 8, 1, CLIP, float><<<grid, block, 0, stream>>>(t);
-    else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1, CLIP, float><<<grid, block, 0, stream>>>(t);
-    else adamw_kernel<bf16, bf16, false, 8, 1, CLIP, float><<<grid, block, 0, stream>>>(t);
+    if (master) adamw_kernel<bf16, float, true, 8, 1, CLIP, float, GUARD><<<grid, block, 0, stream>>>(t);
+    else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1, CLIP, float, GUARD><<<grid, block, 0, stream>>>(t);
+    else adamw_kernel<bf16, bf16, false, 8, 1, CLIP, float, GUARD><<<grid, block, 0, stream>>>(t);
 }
 
 // acc_grads: the gradients are fp32 whatever d->dtype is (for fp32 parameters that is what the fp32 kernels read anyway)
+// skip: the GUARD kernels (grad_coef is then given too)
 static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, void* const* exp_avg,
                         void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef, const long long* numels,
-                        hipStream_t stream, bool acc_grads = false) {
+                        hipStream_t stream, bool acc_grads = false, const float* skip = nullptr) {
     FF_CHECK(d && params && grads && exp_avg && exp_avg_sq && numels, FF_ERR_SHAPE, "ff_adamw_step: null argument");
     FF_CHECK(d->dtype == FF_DTYPE_F32 || d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_adamw_step: dtype %d", d->dtype);
     FF_CHECK(state_dtype == d->dtype || state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: moments must be stored in the parameter dtype or in fp32");
@@ -186,6 +194,7 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
     t.step_dev = d->step_dev;
     t.lr_dev = lr_dev;
     t.grad_coef = grad_coef;
+    t.skip = skip;
     t.bc1 = 1.f - powf(d->beta1, (float)std::max(d->step, 1));
     t.bc2_sqrt = sqrtf(1.f - powf(d->beta2, (float)std::max(d->step, 1)));
     t.grad_scale = d->grad_scale == 0.f ? 1.f : d->grad_scale;
@@ -208,7 +217,10 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
         t.count = cnt;
         const dim3 grid(blocks);
         if (master) FF_CHECK(state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: fp32 master copies go with fp32 moments");
-        if (acc_grads && d->dtype == FF_DTYPE_BF16) {
+        if (skip) {
+            if (acc_grads && d->dtype == FF_DTYPE_BF16) adamw_dispatch_acc<true, true>(master != nullptr, state_dtype, grid, stream, t);
+            else adamw_dispatch<true, true>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
+        } else if (acc_grads && d->dtype == FF_DTYPE_BF16) {
             if (grad_coef) adamw_dispatch_acc<true>(master != nullptr, state_dtype, grid, stream, t);
             else adamw_dispatch_acc<false>(master != nullptr, state_dtype, grid, stream, t);
         } else if (grad_coef) adamw_dispatch<true>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
@@ -312,6 +324,30 @@ __global__ void grad_clip_coef_kernel(const double* sum, float max_norm, float* 
     const float c = max_norm / (nrm + 1e-6f);
     if (norm) *norm = nrm;
     if (coef) *coef = c > 1.f ? 1.f : c;
+}
+
+// ff_grad_guard: grad_clip_coef_kernel with a verdict - the step is skipped (bad) iff the sum of squares is non-finite, an external check
+// found a non-finite gradient (torch.amp.GradScaler's found_inf), or the external loss scale has no finite inverse.  Squares are
+// non-negative, so a non-finite gradient always gives a non-finite sum: nothing cancels.  inv = 1 / *ext_scale unscales the gradients
+// through the coefficient (they stay scaled in memory).  The intrinsics keep every operation a separately rounded one (no contraction of
+// nrm + 1e-6 into a multiply-add), so that without ext_* arguments norm and coef are grad_clip_coef_kernel's bit for bit
+__global__ void grad_guard_kernel(const double* sum, float max_norm, const float* ext_found_inf, const float* ext_scale, float* norm,
+                                  float* coef, float* skip, float* take, long long* skipped_total) {
+    if (threadIdx.x != 0) return;
+    const float inv = ext_scale ? __fdiv_rn(1.f, *ext_scale) : 1.f;
+    const double s = sum ? *sum : 0.0;
+    const float nrm = __fmul_rn((float)sqrt(s), inv);
+    const bool bad = !isfinite(s) || (ext_found_inf && *ext_found_inf != 0.f) || !isfinite(inv);
+    float c = 1.f;
+    if (max_norm > 0.f) {
+        c = __fdiv_rn(max_norm, __fadd_rn(nrm, 1e-6f));
+        c = c > 1.f ? 1.f : c;
+    }
+    if (norm) *norm = nrm;
+    *coef = bad ? 0.f : __fmul_rn(inv, c);
+    *skip = bad ? 1.f : 0.f;
+    if (take) *take = bad ? 0.f : 1.f;
+    if (skipped_total && bad) *skipped_total += 1;
 }
 
 template <typename T>
@@ -484,6 +520,13 @@ extern "C" int ff_adamw_step_acc(const ff_adamw_desc* d, int state_dtype, void* 
     return ff::adamw_launch(d, state_dtype, params, (const void* const*)grads32, exp_avg, exp_avg_sq, master, lr_dev, grad_coef, numels,
                             (hipStream_t)stream, true);
 }
+extern "C" int ff_adamw_step_guarded(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, int grads_fp32,
+                                     void* const* exp_avg, void* const* exp_avg_sq, float* const* master, const float* lr_dev,
+                                     const float* grad_coef, const float* skip, const long long* numels, ff_stream_t stream) {
+    FF_CHECK(grad_coef && skip, FF_ERR_SHAPE, "ff_adamw_step_guarded: %s is null", grad_coef ? "skip" : "grad_coef");
+    return ff::adamw_launch(d, state_dtype, params, grads, exp_avg, exp_avg_sq, master, lr_dev, grad_coef, numels, (hipStream_t)stream,
+                            grads_fp32 != 0, skip);
+}
 extern "C" long long ff_grad_sumsq_partials(int n_tensors, const long long* numels) {
     return n_tensors > 0 && numels ? ff::grad_slots(n_tensors, numels) : 0;
 }
@@ -512,6 +555,13 @@ extern "C" int ff_grad_clip_coef(const double* sum, float max_norm, float* norm,
     FF_CHECK(sum && (norm || coef), FF_ERR_SHAPE, "ff_grad_clip_coef: null argument");
     ff::grad_clip_coef_kernel<<<1, 64, 0, (hipStream_t)stream>>>(sum, max_norm, norm, coef);
     return ff::check_launch("ff_grad_clip_coef");
+}
+extern "C" int ff_grad_guard(const double* sum, float max_norm, const float* ext_found_inf, const float* ext_scale, float* norm, float* coef,
+                             float* skip, float* take, long long* skipped_total, ff_stream_t stream) {
+    FF_CHECK(coef && skip, FF_ERR_SHAPE, "ff_grad_guard: %s is null", coef ? "skip" : "coef");
+    FF_CHECK(sum || ext_found_inf, FF_ERR_SHAPE, "ff_grad_guard: neither a sum nor ext_found_inf is given");
+    ff::grad_guard_kernel<<<1, 64, 0, (hipStream_t)stream>>>(sum, max_norm, ext_found_inf, ext_scale, norm, coef, skip, take, skipped_total);
+    return ff::check_launch("ff_grad_guard");
 }
 extern "C" int ff_scale_grads(int dtype, int n_tensors, void* const* grads, const long long* numels, const float* coef, ff_stream_t stream) {
     using namespace ff;

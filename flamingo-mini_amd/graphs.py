@@ -115,7 +115,11 @@ class GraphedTrainStep:
     fp32 accumulators (FusedAdamW.accumulate), and every backward finds `.grad is None`, so the deferred weight-gradient launches stay.  The
     returned loss is the mean of the k micro-batch losses - the HF Trainer's convention, a mean of means: it equals the full batch's loss
     only when every micro-batch holds the same number of target tokens.  Needs an optimizer with accumulate() and no reducer
-    (data-parallel accumulation keeps its no_sync() path)."""
+    (data-parallel accumulation keeps its no_sync() path).
+
+    FusedAdamW(capturable=True, skip_nonfinite=True): the captured step decides on the device whether its gradients are finite and, if not,
+    leaves parameters, optimizer state and step count untouched - one overflowing batch cannot poison the replays after it.  The loss such a
+    replay returns is that step's own, non-finite loss; `optimizer.step_skipped` / `skipped_steps` (device scalars) tell what happened."""
 
     def __init__(self, model: torch.nn.Module, optimizer: Optional[torch.optim.Optimizer], example_batch: Dict[str, torch.Tensor],
                  warmup: int = 3, loss_fn: Optional[Callable] = None, reducer=None, check_every: int = 128,
@@ -346,6 +350,9 @@ class PiecewiseGraphedTrainStep:
         if overlap_optimizer and getattr(optimizer, "max_grad_norm", None) is not None:
             raise ValueError("overlap_optimizer=True updates a segment's parameters before the global gradient norm exists, so it cannot be "
                              "combined with an optimizer with max_grad_norm set: use overlap_optimizer=False to clip")
+        if overlap_optimizer and getattr(optimizer, "skip_nonfinite", False):
+            raise ValueError("overlap_optimizer=True updates a segment's parameters before every gradient of the step exists, so the verdict "
+                             "of an optimizer with skip_nonfinite=True would come too late: use overlap_optimizer=False to skip non-finite steps")
         self.model, self.optimizer, self.reducer = model, optimizer, reducer
         self.pace = pace
         self.overlap_optimizer = bool(overlap_optimizer) and optimizer is not None

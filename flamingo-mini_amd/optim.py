@@ -28,7 +28,25 @@ fold of a step overwrites, so nothing is zeroed) and sets `.grad = None`; the ne
 fp32 instead of being rounded to 8 bits after every micro-batch, and because every backward finds `.grad is None` the gated blocks keep
 their deferred, grouped weight-gradient launches in every micro-batch.  The accumulators cost 4 bytes per trainable parameter and live
 outside `state`, so `state_dict()` stays torch.optim.AdamW's.  Nothing synchronises: graphs.GraphedTrainStep(micro_batches=k) captures
-k x (forward, backward, accumulate(1 / k)) + step() as one graph."""
+k x (forward, backward, accumulate(1 / k)) + step() as one graph.
+
+Non-finite gradients (the reference trains with `--fp16` under HF Trainer's GradScaler, which does not take a step whose gradients hold an
+inf or a NaN): `skip_nonfinite=True` (needs `capturable=True`) decides and skips on the device, so the guard works inside a replayed graph
+where no host check can stand.  DEFINITION: a step is skipped iff the sum of squares of the (grad_scale'd) gradients - fp32 per workgroup,
+fp64 in total, the sweep of clipping - is non-finite.  Squares are non-negative, so nothing cancels: every inf / NaN element is found, and
+so are finite gradients so large that a 32768-element chunk's sum of squares overflows fp32 (a norm beyond about 1.8e19: garbage anyway).
+step() always runs the sweep (ff_grad_sumsq over `.grad` or the open cycle's accumulators, ff_grad_sumsq_reduce), ff_grad_guard in the
+place of ff_grad_clip_coef (norm, coefficient, `step_skipped`, the running `skipped_steps`; max_grad_norm is optional), advances the device
+step counters by 1 - skipped, and updates every bucket with ff_adamw_step_guarded, whose workgroups return before touching a tensor when the
+step is skipped: parameters, both moments, master copies and the step count stay bit for bit what they were, and the next taken step uses
+the bias corrections of step t, not t + 1.  `.grad` is never modified; an accumulation cycle is closed after a skipped step too.  Graphed
+steps capture it as they capture clipping; the loss a replay returns for a skipped step is that step's own, non-finite loss.  With
+GradientAllReducer the averaged gradients are non-finite on every rank as soon as they are on one, so all ranks skip together.
+
+torch.amp.GradScaler (eager): a capturable FusedAdamW sets `_step_supports_amp_scaling`, so `scaler.step(opt)` hands over its device scalars
+`opt.found_inf` / `opt.grad_scale` and calls step() without a host round trip.  step() passes them to ff_grad_guard: the step is skipped on
+found_inf != 0, the gradients are unscaled as they are read (coefficient / scale) - `.grad` keeps the scaled values, `grad_norm` is the norm
+of the unscaled gradients.  The sweep runs only if skip_nonfinite or max_grad_norm asks for it.  Not with an open accumulate() cycle."""
 from __future__ import annotations
 
 import ctypes as C
@@ -41,7 +59,8 @@ from . import ffi
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 grad_scale: float = 1.0, capturable: bool = False, master_dtype=None, state_dtype=None, max_grad_norm: Optional[float] = None):
+                 grad_scale: float = 1.0, capturable: bool = False, master_dtype=None, state_dtype=None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameters")
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
@@ -49,6 +68,8 @@ class FusedAdamW(torch.optim.Optimizer):
         # an optimizer-wide setting (the norm spans every group), so it is no group hyper-parameter and stays out of state_dict()
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self._clip = None                                 # clipping: partials / fp64 sum / norm / coefficient on the device (first step)
+        # optimizer-wide as well (one verdict per step) and out of state_dict(); the step count must live on the device to be conditional
+        self.skip_nonfinite = bool(skip_nonfinite)
         if master_dtype not in (None, torch.float32) or state_dtype not in (None, torch.float32):
             raise ValueError("master_dtype / state_dtype: None (the parameter's dtype) or torch.float32")
         if master_dtype is not None:
@@ -60,12 +81,37 @@ class FusedAdamW(torch.optim.Optimizer):
         self._acc_open = False                            # ... a cycle is open: step() reads the accumulators
         if self.max_grad_norm is not None and len({p.device for g in self.param_groups for p in g["params"]}) > 1:
             raise ValueError("FusedAdamW(max_grad_norm=...) needs every parameter on one device (the global norm is reduced on it)")
+        if self.skip_nonfinite and not all(g.get("capturable", False) for g in self.param_groups):
+            raise ValueError("FusedAdamW(skip_nonfinite=True) needs capturable=True (a skipped step must not advance the step count, so the "
+                             "count lives on the device)")
+        if self.skip_nonfinite and len({p.device for g in self.param_groups for p in g["params"]}) > 1:
+            raise ValueError("FusedAdamW(skip_nonfinite=True) needs every parameter on one device (the verdict is reached on it)")
 
     @property
     def grad_norm(self) -> Optional[torch.Tensor]:
-        """max_grad_norm: the total L2 norm of the gradients (grad_scale applied) BEFORE clipping, from the last step - a 0-dim fp32 device
-        tensor whose storage is the same every step (None before the first step, and without max_grad_norm)."""
-        return None if self._clip is None else self._clip["norm"]
+        """max_grad_norm / skip_nonfinite: the total L2 norm of the gradients (grad_scale applied, a GradScaler's scale removed) BEFORE
+        clipping, from the last step - a 0-dim fp32 device tensor whose storage is the same every step (None before the first step, and
+        when no step computed a norm).  Non-finite for a skipped step."""
+        return None if self._clip is None or not self._clip["swept"] else self._clip["norm"]
+
+    @property
+    def step_skipped(self) -> Optional[torch.Tensor]:
+        """1 if the last step() was skipped for non-finite gradients, else 0: a 0-dim fp32 device tensor whose storage is the same every
+        step (None before the first guarded step)."""
+        return None if self._clip is None else self._clip["skip"]
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """How many steps were skipped so far: a 0-dim int64 device tensor whose storage is the same every step (None before the first
+        guarded step)."""
+        return None if self._clip is None else self._clip["total"]
+
+    @property
+    def _step_supports_amp_scaling(self) -> bool:
+        """torch.amp.GradScaler's protocol: True = GradScaler.step() sets `found_inf` / `grad_scale` (device scalars) on the optimizer and
+        calls step(), which skips and unscales on the device.  Only when every group is capturable (a skipped step must not count);
+        other optimizers keep GradScaler's generic path."""
+        return all(g.get("capturable", False) for g in self.param_groups)
 
     @torch.no_grad()
     def accumulate(self, scale: float = 1.0) -> None:
@@ -115,7 +161,28 @@ class FusedAdamW(torch.optim.Optimizer):
         (the device step counters count training steps, not calls) and must execute before the others.  Not with max_grad_norm: the norm
         needs every gradient of the step before the first update.
         grad_coef: a 0-dim fp32 device tensor every gradient is multiplied by - a clip coefficient computed elsewhere (ShardedAdamW's, over
-        the gradients of every rank); only without max_grad_norm."""
+        the gradients of every rank); only without max_grad_norm.
+        skip_nonfinite, or `found_inf` / `grad_scale` set by torch.amp.GradScaler.step(): the guarded step (module docstring); neither
+        only= (the verdict needs every gradient before the first update) nor grad_coef= (it says nothing about finiteness) goes with it."""
+        ext_found, ext_scale = getattr(self, "found_inf", None), getattr(self, "grad_scale", None)
+        amp = ext_found is not None or ext_scale is not None
+        guard = self.skip_nonfinite or amp
+        if guard and only is not None:
+            raise ValueError("FusedAdamW.step(only=...) cannot skip non-finite gradients: the verdict needs every gradient before the first "
+                             "update (PiecewiseGraphedTrainStep(overlap_optimizer=True) cannot be used with skip_nonfinite or a GradScaler)")
+        if guard and grad_coef is not None:
+            raise ValueError("FusedAdamW.step(grad_coef=...) says nothing about the gradients' finiteness: not with skip_nonfinite or a GradScaler")
+        if amp:
+            if not self._step_supports_amp_scaling:
+                raise ValueError("FusedAdamW: found_inf / grad_scale (torch.amp.GradScaler) need capturable=True in every group")
+            if self._acc_open:
+                raise ValueError("FusedAdamW.step(): found_inf / grad_scale (torch.amp.GradScaler) cannot be combined with an open accumulate() "
+                                 "cycle (scaled accumulation is not supported)")
+            if ext_found is None and not self.skip_nonfinite:
+                raise ValueError("FusedAdamW.step(): grad_scale is set without found_inf")
+            for t in (ext_found, ext_scale):
+                if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+                    raise ValueError("FusedAdamW.step(): found_inf / grad_scale must be one-element float32 device tensors")
         if self.max_grad_norm is not None and only is not None:
             raise ValueError("FusedAdamW.step(only=...) cannot clip gradients: max_grad_norm needs the norm over every gradient before the first "
                              "update (PiecewiseGraphedTrainStep(overlap_optimizer=True) cannot be used with it)")
@@ -142,11 +209,16 @@ class FusedAdamW(torch.optim.Optimizer):
             only = frozenset(only)
             if not all(g.get("capturable", False) for g in self.param_groups):
                 raise ValueError("FusedAdamW.step(only=...) needs capturable=True (step counts live in device scalars shared by the partial calls)")
-        coef = self._clip_coef(lib, acc) if self.max_grad_norm is not None else grad_coef
+        if guard:
+            coef = self._clip_coef(lib, acc, guard=True, ext_found=ext_found, ext_scale=ext_scale)
+        else:
+            coef = self._clip_coef(lib, acc) if self.max_grad_norm is not None else grad_coef
+        guard = guard and coef is not None                # (no gradient anywhere: nothing to do)
         for gi, group in enumerate(self.param_groups):
             capturable = group.get("capturable", False)
             if capturable and advance:
-                self._advance_device_steps(group)
+                # guarded: the counters advance by 1 - skipped, one device add ordered after the guard kernel and before the updates
+                self._advance_device_steps(group, self._clip["take"] if guard else None)
             for bucket in self._buckets(gi, group, only, acc):
                 params, grad_ptrs, n = bucket["params"], bucket["grad_ptrs"], len(bucket["params"])
                 if not acc:
@@ -160,7 +232,12 @@ class FusedAdamW(torch.optim.Optimizer):
                     step, step_dev = bucket["step"], None
                 desc = ffi.AdamWDesc(bucket["dtype_code"], n, step, group["lr"], group["betas"][0], group["betas"][1], group["eps"],
                                      group["weight_decay"], group["grad_scale"], step_dev)
-                if acc:
+                if guard:
+                    ffi.check(lib.ff_adamw_step_guarded(desc, bucket["state_code"], bucket["param_ptrs"], bucket["acc_ptrs"] if acc else grad_ptrs, int(acc),
+                                                        bucket["m_ptrs"], bucket["v_ptrs"], bucket["w_ptrs"], lr_dev, coef.data_ptr(),
+                                                        self._clip["skip"].data_ptr(), bucket["numels"], ffi.stream_handle(bucket["device"])),
+                              "ff_adamw_step_guarded")
+                elif acc:
                     ffi.check(lib.ff_adamw_step_acc(desc, bucket["state_code"], bucket["param_ptrs"], bucket["acc_ptrs"], bucket["m_ptrs"], bucket["v_ptrs"],
                                                     bucket["w_ptrs"], lr_dev, None if coef is None else coef.data_ptr(), bucket["numels"],
                                                     ffi.stream_handle(bucket["device"])), "ff_adamw_step_acc")
@@ -184,26 +261,42 @@ class FusedAdamW(torch.optim.Optimizer):
                 raise ffi.FusionLibraryError("FusedAdamW needs contiguous gradients of the parameter's dtype")
             bucket["grad_ptrs"][i] = g.data_ptr()
 
-    def _clip_coef(self, lib, acc: bool = False) -> Optional[torch.Tensor]:
+    def _clip_coef(self, lib, acc: bool = False, guard: bool = False, ext_found=None, ext_scale=None) -> Optional[torch.Tensor]:
         """max_grad_norm: enqueue the global norm of every gradient of every group (grad_scale applied) and the clip coefficient; returns
         the device scalar the AdamW launches of this step read.  No host synchronisation (capturable).  acc: the gradients are the fp32
-        accumulators."""
+        accumulators.
+        guard: ff_grad_guard instead of ff_grad_clip_coef (the same number of launches), which also writes the verdict; the sweep runs if
+        skip_nonfinite or max_grad_norm asks for it, else the verdict is ext_found (a GradScaler's found_inf) alone."""
         buckets = [(group, b) for gi, group in enumerate(self.param_groups) for b in self._buckets(gi, group, None, acc)]
         if not buckets:
             return None
         devices = {b["device"] for _, b in buckets}
         if len(devices) > 1:
-            raise ValueError("FusedAdamW(max_grad_norm=...) needs every parameter on one device (the global norm is reduced on it)")
+            raise ValueError("FusedAdamW(max_grad_norm=...) needs every parameter on one device (the global norm is reduced on it)"
+                             if not guard else "FusedAdamW: skipping non-finite gradients needs every parameter on one device")
         device = devices.pop()
+        if any(t is not None and t.device != device for t in (ext_found, ext_scale)):
+            raise ValueError("FusedAdamW.step(): found_inf / grad_scale must live on the parameters' device")
+        sweep = not guard or self.skip_nonfinite or self.max_grad_norm is not None
         slots = [int(lib.ff_grad_sumsq_partials(len(b["params"]), b["numels"])) for _, b in buckets]
         clip = self._clip
         if clip is None or clip["device"] != device:
             clip = self._clip = dict(device=device, norm=torch.zeros((), dtype=torch.float32, device=device),
                                      coef=torch.ones((), dtype=torch.float32, device=device),
-                                     sum=torch.zeros((), dtype=torch.float64, device=device), partials=None)
+                                     sum=torch.zeros((), dtype=torch.float64, device=device), partials=None,
+                                     skip=None, take=None, total=None, swept=False)
+        stream = ffi.stream_handle(device)
+        if guard and clip["skip"] is None:
+            clip["skip"] = torch.zeros((), dtype=torch.float32, device=device)
+            clip["take"] = torch.ones((), dtype=torch.float32, device=device)
+            clip["total"] = torch.zeros((), dtype=torch.int64, device=device)
+        clip["swept"] = sweep
+        if not sweep:
+            ffi.check(lib.ff_grad_guard(None, 0.0, ffi.ptr(ext_found), ffi.ptr(ext_scale), None, clip["coef"].data_ptr(), clip["skip"].data_ptr(),
+                                        clip["take"].data_ptr(), clip["total"].data_ptr(), stream), "ff_grad_guard")
+            return clip["coef"]
         if clip["partials"] is None or clip["partials"].numel() < sum(slots):
             clip["partials"] = torch.zeros(max(sum(slots), 1), dtype=torch.float32, device=device)
-        stream = ffi.stream_handle(device)
         partials, total, off = clip["partials"], clip["partials"].numel(), 0
         for (group, b), k in zip(buckets, slots):     # slots continue from bucket to bucket (dtypes, groups)
             if not acc:
@@ -213,8 +306,13 @@ class FusedAdamW(torch.optim.Optimizer):
                                         partials.data_ptr() + 4 * off, total - off, stream), "ff_grad_sumsq")
             off += k
         ffi.check(lib.ff_grad_sumsq_reduce(partials.data_ptr(), off, clip["sum"].data_ptr(), 0, stream), "ff_grad_sumsq_reduce")
-        ffi.check(lib.ff_grad_clip_coef(clip["sum"].data_ptr(), self.max_grad_norm, clip["norm"].data_ptr(), clip["coef"].data_ptr(), stream),
-                  "ff_grad_clip_coef")
+        if guard:
+            ffi.check(lib.ff_grad_guard(clip["sum"].data_ptr(), self.max_grad_norm or 0.0, ffi.ptr(ext_found), ffi.ptr(ext_scale), clip["norm"].data_ptr(),
+                                        clip["coef"].data_ptr(), clip["skip"].data_ptr(), clip["take"].data_ptr(), clip["total"].data_ptr(), stream),
+                      "ff_grad_guard")
+        else:
+            ffi.check(lib.ff_grad_clip_coef(clip["sum"].data_ptr(), self.max_grad_norm, clip["norm"].data_ptr(), clip["coef"].data_ptr(), stream),
+                      "ff_grad_clip_coef")
         return clip["coef"]
 
     def sync_device_hyperparams(self) -> None:
@@ -275,8 +373,9 @@ class FusedAdamW(torch.optim.Optimizer):
         return buckets
 
     # ------------------------------------------------------------------ capturable mode
-    def _advance_device_steps(self, group):
-        """One float32 step counter per (group, device), advanced by a device-side add (captured along with the update)."""
+    def _advance_device_steps(self, group, take=None):
+        """One float32 step counter per (group, device), advanced by a device-side add (captured along with the update): by 1, or by the
+        device scalar `take` (1 - skipped) of a guarded step."""
         counters = group.setdefault("_step_dev", {})
         lrs = group.setdefault("_lr_dev", {})
         for p in group["params"]:
@@ -288,7 +387,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if not torch.cuda.is_current_stream_capturing():
             self.sync_device_hyperparams()
         for counter in counters.values():
-            counter += 1
+            counter += 1 if take is None else take
 
     def _sync_host_steps(self):
         """Write the step counts kept per bucket (host mode) back into the per-parameter state entries."""

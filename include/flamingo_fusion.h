@@ -47,7 +47,8 @@ enum { FF_ACT_NONE = -1, FF_ACT_GELU = 0, FF_ACT_SQRELU = 1, FF_ACT_RELU = 2 }; 
 int ff_version(void);          /* ABI version, bumped on any signature change (3: ff_gemm_desc.tile / .stages replace ff_gemm_set_tuning;
                                 * 4: ff_xattn_desc.sync, ff_xattn_sync_bytes / _status, ff_resampler_layer_* / _prologue_* / _epilogue_*;
                                 * 5: gradient clipping: ff_grad_sumsq*, ff_grad_clip_coef, ff_scale_grads, ff_adamw_step_clipped;
-                                * 6: fp32 gradient accumulation: ff_grad_accumulate, ff_adamw_step_acc) */
+                                * 6: fp32 gradient accumulation: ff_grad_accumulate, ff_adamw_step_acc;
+                                * still 6, additions only: the non-finite gradient guard ff_grad_guard, ff_adamw_step_guarded) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -427,6 +428,31 @@ int ff_adamw_step_acc(const ff_adamw_desc* d, int state_dtype, void* const* para
                       void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef, const long long* numels,
                       ff_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Non-finite gradients (added under ABI 6): a step whose gradients hold an inf or a NaN is NOT taken - what training under a loss scaler
+ * (the reference's `--fp16`, training/train.sh) does - decided and carried out on the device, so that it works inside a replayed HIP graph.
+ * Definition: the step is skipped iff the sum of squares of the (grad_scale'd) gradients - fp32 per workgroup (ff_grad_sumsq), fp64 over
+ * workgroups (ff_grad_sumsq_reduce) - is non-finite.  Squares are non-negative, so nothing cancels: every inf / NaN element is found; so are
+ * finite gradients so large that one 32768-element chunk's sum of squares overflows fp32 (a norm beyond about 1.8e19).
+ *   ff_grad_guard          one thread; every pointer is a device scalar.  ff_grad_clip_coef plus the verdict:
+ *                            inv   = ext_scale ? 1 / *ext_scale : 1                  (a loss scale the gradients still carry)
+ *                            nrm   = (float)sqrt(*sum) * inv                         (*sum read as 0 when sum is NULL: no norm was computed)
+ *                            bad   = !isfinite(*sum) || (ext_found_inf && *ext_found_inf != 0) || !isfinite(inv)
+ *                            *skip = bad ? 1 : 0;   *take = 1 - *skip;   *norm = nrm (a non-finite value is reported as it is)
+ *                            *coef = bad ? 0 : inv * (max_norm > 0 ? min(1, max_norm / (nrm + 1e-6)) : 1);   *skipped_total += bad
+ *                          in fp32, each operation rounded once.  sum may be NULL if ext_found_inf is given; ext_found_inf, ext_scale, norm,
+ *                          take and skipped_total are optional; coef and skip are required (FF_ERR_SHAPE).  For a finite sum, no ext_*
+ *                          arguments and max_norm > 0, *norm and *coef are ff_grad_clip_coef's bit for bit.
+ *   ff_adamw_step_guarded  ff_adamw_step_clipped (grads_fp32 == 0) or ff_adamw_step_acc (grads_fp32 != 0: `grads` are fp32 accumulators)
+ *                          whose every workgroup reads *skip first and returns before it loads or stores a single tensor element when it is
+ *                          != 0: a skipped launch is a no-op - no weight decay, no decay of the moments, no write of the master copies.
+ *                          grad_coef and skip are both required.  The caller advances the device step count by *take, not by 1.
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_grad_guard(const double* sum, float max_norm, const float* ext_found_inf, const float* ext_scale, float* norm, float* coef,
+                  float* skip, float* take, long long* skipped_total, ff_stream_t stream);
+int ff_adamw_step_guarded(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, int grads_fp32,
+                          void* const* exp_avg, void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef,
+                          const float* skip, const long long* numels, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Shifted next-token cross-entropy (modeling_flamingo.py:288-298): position i predicts labels[i+1].
