@@ -151,6 +151,7 @@ _SIGNATURES = {
     "ff_adamw_step_acc": (_I, [C.POINTER(AdamWDesc), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ff_grad_guard": (_I, [_P, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ff_adamw_step_guarded": (_I, [C.POINTER(AdamWDesc), _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ff_sample_token": (_I, [_I, _I, _I, C.c_longlong, _P, C.c_float, _I, C.c_float, _P, _P, _P]),
     "ff_xattn_block_bwd_kv": (_I, [C.POINTER(XattnDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _SZ, _P]),
     "ff_kv_project_workspace_bytes": (_SZ, [C.POINTER(KvProjDesc), _I]),
     "ff_kv_project_fwd": (_I, [C.POINTER(KvProjDesc), _P, _P, _P, _P, _SZ, _P]),

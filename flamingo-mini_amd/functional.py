@@ -904,6 +904,28 @@ def shifted_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, reduction:
     raise ValueError(f"unknown reduction {reduction}")
 
 
+def sample_tokens(logits: torch.Tensor, u: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One token id per row of `logits` (rows, V), float32 / bfloat16 on the GPU, drawn with the row's uniform number u[r] in [0, 1) under
+    temperature, top-k (0 = off; ties with the k-th value are kept) and nucleus filtering (top_p = 1: off): ff_sample_token, one launch, the
+    exact rules are in include/flamingo_fusion.h.  Only the last dimension has to be contiguous: a row view such as logits3d[:, -1] is read
+    in place through its row stride.  With `out` (int64, rows, contiguous) nothing is allocated, so the call can be captured into a graph."""
+    ffi.require_cuda(logits, u, out)
+    if logits.ndim != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"sample_tokens: logits must be (rows, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
+    rows, V = logits.shape
+    if u.dtype != torch.float32 or u.numel() != rows or not u.is_contiguous():
+        raise ValueError(f"sample_tokens: u must be {rows} contiguous float32 values, got {tuple(u.shape)} {u.dtype}")
+    if out is None:
+        out = _new((rows,), torch.long, logits.device)
+    elif out.dtype != torch.long or out.shape != (rows,) or not out.is_contiguous():
+        raise ValueError(f"sample_tokens: out must be {rows} contiguous int64 values, got {tuple(out.shape)} {out.dtype}")
+    ld = logits.stride(0) if rows > 1 else V
+    ffi.check(ffi.lib().ff_sample_token(ffi.dtype_code(logits.dtype), rows, V, ld, logits.data_ptr(), float(temperature), int(top_k), float(top_p),
+                                        u.data_ptr(), out.data_ptr(), ffi.stream_handle(logits.device)), "ff_sample_token")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------
 # primitive wrappers (parity tests / micro-benchmarks): thin, allocation + one C call each
 # ----------------------------------------------------------------------------------------------------

@@ -316,9 +316,14 @@ class _DecodeSession:
     tokens are never media tags).  A decode step then issues exactly the same work on the same addresses every time, so on the GPU it is
     captured once into a HIP graph and replayed (the eager step is host-bound: 72 layers, ~800 launches of a few microseconds each).
     If the capture raises (e.g. a host synchronisation inside the stock LM) the steps run eagerly.  Token-for-token equal to the
-    growing-cache loop of FlamingoModel.generate (tests/test_model_plumbing.py)."""
+    growing-cache loop of FlamingoModel.generate (tests/test_model_plumbing.py).
+    `sampling` = (temperature, top_k, top_p) makes it a SAMPLING session (GPU only): _append draws the token with functional.sample_tokens
+    (one launch on the logits in their own dtype, csrc/ff_sample.hip) instead of the argmax.  The random numbers of a whole call are drawn
+    before the prompt step, outside any capture, into `u_all` (max_length, b): row `pos` serves the token written at position `pos` and the
+    captured step picks it with a device-side index_select on `pos`, so the graph holds no random-number generation and eager and replayed
+    steps consume identical numbers."""
 
-    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph):
+    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None):
         from transformers.cache_utils import StaticCache
         self._model_ref = weakref.ref(model)
         self.b, self.max_length, self.eos, self.graph_wanted = b, max_length, eos, graph
@@ -332,6 +337,10 @@ class _DecodeSession:
         self.pos = torch.zeros((1,), dtype=torch.long, device=device)          # position of `tok` (the token the next step consumes)
         self.tok = torch.zeros((b, 1), dtype=ids_dtype, device=device)
         self.tt_step = torch.zeros((b, 1), dtype=torch.int32, device=device)
+        self.sampling = sampling
+        if sampling is not None:
+            self.u_all = torch.zeros((max_length, b), dtype=torch.float32, device=device)
+            self.nxt = torch.zeros((b,), dtype=torch.long, device=device)
         self.xattn_past = None                                                 # persistent (k, v) per layer, filled by every prompt step
         self.replay = None
         self.capture_failed = False
@@ -353,7 +362,11 @@ class _DecodeSession:
         return self.param_ptrs != self._param_ptrs()
 
     def _append(self, logits):             # choose, apply the eos bookkeeping of generate(), append at `pos`
-        nxt = logits.float().argmax(-1)
+        if self.sampling is None:
+            nxt = logits.float().argmax(-1)
+        else:
+            temperature, top_k, top_p = self.sampling
+            nxt = F.sample_tokens(logits, self.u_all.index_select(0, self.pos).view(-1), temperature, top_k, top_p, out=self.nxt)
         alive = ~self.finished.all()
         if self.eos is not None:
             nxt = torch.where(self.finished, torch.full_like(nxt, self.fill), nxt)
@@ -381,9 +394,11 @@ class _DecodeSession:
         self._append(o.logits[:, -1])
 
     @torch.no_grad()
-    def run(self, ids, ml, am, pixel_values, visual_features):
+    def run(self, ids, ml, am, pixel_values, visual_features, generator=None):
         L0 = ids.shape[1]
         dev = ids.device
+        if self.sampling is not None:
+            self.u_all.copy_(torch.rand((self.max_length, self.b), generator=generator, device=dev, dtype=torch.float32))
         self.cache.reset()
         out = self.model.flamingo(input_ids=ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=(None, self.cache),
                                   pixel_values=pixel_values, visual_features=visual_features, **self._positions(L0))
@@ -561,7 +576,12 @@ class FlamingoModel(PreTrainedModel):
         every later step feeds one token (reference: HF `generate` through prepare_inputs_for_generation / _reorder_cache, :464-548).
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
         implemented here: greedy, multinomial sampling (do_sample, temperature, top_k, top_p) and beam search (num_beams, length_penalty,
-        early_stopping).  Unknown generation arguments raise instead of being ignored."""
+        early_stopping).  Unknown generation arguments raise instead of being ignored.
+        Sampling takes the fixed-shape, graph-replayed path of greedy decoding (_DecodeSession) only when `static_decode=True` is passed
+        explicitly (GPU tensors, a GPT-2- or OPT-backed model, a prompt shorter than max_length - 1); otherwise it runs the dynamic loop
+        below, as it always has.  The two paths draw DIFFERENT token streams from the same seed: the static path draws by inverse CDF in
+        vocabulary order from one uniform number per token (functional.sample_tokens), the dynamic loop with torch.multinomial.  Both are
+        reproducible per seed (`generator`)."""
         if unsupported:
             raise TypeError(f"generate(): unsupported generation arguments {sorted(unsupported)}")
         if not use_cache:
@@ -575,6 +595,11 @@ class FlamingoModel(PreTrainedModel):
             if do_sample:
                 raise ValueError("beam search with sampling is not implemented")
             return self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty)
+        if do_sample and static_decode:                                       # explicit static_decode=True: the sampling kernel has no CPU form
+            F.ffi.require_cuda(ids)
+            if isinstance(self.flamingo, (FlamingoGPT2, FlamingoOPT)) and ids.shape[1] + 1 < max_length:
+                return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
+                                           sampling=(float(temperature), int(top_k), float(top_p)), generator=generator)
         if static_decode is None:       # greedy decoding on the GPU (GPT-2- and OPT-backed models): fixed-shape decode steps, replayed from a HIP graph
             static_decode = ids.is_cuda and self.static_decode
         if static_decode and not do_sample and isinstance(self.flamingo, (FlamingoGPT2, FlamingoOPT)) and ids.shape[1] + 1 < max_length:
@@ -599,9 +624,10 @@ class FlamingoModel(PreTrainedModel):
                 break
         return ids
 
-    def _static_greedy(self, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, graph: Optional[bool] = None):
-        """Greedy decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches and buffers plus, on the GPU, the captured
-        HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, eos / pad) and reused by later calls, so only the
+    def _static_greedy(self, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, graph: Optional[bool] = None,
+                       sampling=None, generator=None):
+        """Greedy (or, with `sampling` = (temperature, top_k, top_p), sampled) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches and buffers plus, on the GPU, the captured
+        HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, eos / pad, sampling settings) and reused by later calls, so only the
         first caption batch of a shape pays for the capture.  a session whose model's parameters were re-allocated since (model.to(), ShardedAdamW) is rebuilt; reset_decode_sessions() drops them all."""
         b = ids.shape[0]
         if graph is None:
@@ -609,7 +635,7 @@ class FlamingoModel(PreTrainedModel):
         sessions = _DECODE_SESSIONS.setdefault(self, {})
         n_media = int(ml.sum(-1).max()) if visual_features is None and pixel_values is None else \
             (visual_features.shape[1] if visual_features is not None else (pixel_values.shape[1] if pixel_values.ndim >= 5 else pixel_values.shape[0]))
-        key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph))
+        key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling)
         sess = sessions.get(key)
         if sess is not None and sess.stale():
             sessions.pop(key)
@@ -617,8 +643,10 @@ class FlamingoModel(PreTrainedModel):
         if sess is None:
             if len(sessions) >= 4:                                            # a handful of shapes at most: each holds a KV cache and a graph
                 sessions.pop(next(iter(sessions)))
-            sess = sessions[key] = _DecodeSession(self, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph)
-        return sess.run(ids, ml, am, pixel_values, visual_features)
+            sess = sessions[key] = _DecodeSession(self, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling)
+        if sampling is None:
+            return sess.run(ids, ml, am, pixel_values, visual_features)
+        return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator)
 
     @property
     def _decode_sessions(self) -> dict:

@@ -48,7 +48,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * 4: ff_xattn_desc.sync, ff_xattn_sync_bytes / _status, ff_resampler_layer_* / _prologue_* / _epilogue_*;
                                 * 5: gradient clipping: ff_grad_sumsq*, ff_grad_clip_coef, ff_scale_grads, ff_adamw_step_clipped;
                                 * 6: fp32 gradient accumulation: ff_grad_accumulate, ff_adamw_step_acc;
-                                * still 6, additions only: the non-finite gradient guard ff_grad_guard, ff_adamw_step_guarded) */
+                                * still 6, additions only: the non-finite gradient guard ff_grad_guard, ff_adamw_step_guarded;
+                                * still 6, addition only: token selection for sampled decoding, ff_sample_token) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -465,6 +466,25 @@ int ff_shifted_ce_fwd(int dtype, int batch, int seq, int vocab, const void* logi
                       float* loss_row, float* lse, ff_stream_t stream);
 int ff_shifted_ce_bwd(int dtype, int batch, int seq, int vocab, const void* logits, const long long* labels, long long ignore_index,
                       const float* lse, const float* grad_row, void* dlogits, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Token selection for sampled decoding (added under ABI 6): temperature, top-k and nucleus (top-p) filtering and the draw, one launch, no
+ * sort, no random-number generation (the caller supplies the uniform numbers), capturable.
+ * logits: `rows` rows of `vocab` elements of `dtype` (FF_DTYPE_F32 / FF_DTYPE_BF16), row r at element r * ld, ld >= vocab; rows need only
+ * element alignment (logits[:, -1] of a (batch, seq, vocab) tensor: ld = seq * vocab).  u: rows fp32 values in [0, 1).  token: rows int64.
+ * Per row, x_i the logits as stored:
+ *   1. K = {i : x_i >= the top_k-th largest x}: ties with that value are all kept.   top_k == 0 or >= vocab: every i.
+ *   2. z_i = x_i / temperature,  q_i = exp(z_i - max z) / sum_{j in K} exp(z_j - max z).
+ *   3. P = {i in K : sum of q_j over the j in K with x_j > x_i (strictly) < top_p}: equal values stay or go together, the maximum always
+ *      stays.   top_p == 1: P = K.
+ *   4. S = sum_{i in P} q_i; token = the smallest i in P whose inclusive prefix sum over P, in index order, exceeds u * S (the last element
+ *      of P if rounding leaves none).
+ * -inf logits (masked entries) are never chosen.  A row that holds a NaN or +inf, or nothing but -inf, gives an unspecified token inside
+ * [0, vocab).  fp32 math in a fixed order: equal inputs give equal tokens, eager or replayed from a graph.
+ * FF_ERR_SHAPE: a null pointer, rows <= 0, vocab <= 0, ld < vocab, temperature not positive and finite, top_k < 0, top_p outside (0, 1].
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_sample_token(int dtype, int rows, int vocab, long long ld, const void* logits, float temperature, int top_k, float top_p,
+                    const float* u, long long* token, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * QuickGELU of the CLIP vision tower, y = x * sigmoid(1.702 x) (transformers.activations.QuickGELUActivation, selected by
