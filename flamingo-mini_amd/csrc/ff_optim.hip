@@ -13,6 +13,69 @@ namespace ff {
 
 constexpr int kAdamTensors = 32;
 constexpr int kAdamChunk = 256 * 128;  // elements per workgroup (16 sweeps of 8-element vectors: the per-workgroup table lookup is amortised)
+constexpr long long kGradMaxBlocks = 1 << 22;       // workgroups per launch (x 256 threads stays far below 2^32; block_start stays an int)
+
+// What every multi-tensor kernel of this file gets as (part of) its kernel argument: up to kAdamTensors tensors, cut into chunks of
+// kAdamChunk elements, one workgroup per chunk; tensor k owns workgroups block_start[k] .. block_start[k + 1] - 1 of the launch.
+struct ChunkTable {
+    long long n[kAdamTensors];
+    int block_start[kAdamTensors + 1];
+    int count;
+};
+
+// this workgroup's chunk: elements base .. end - 1 of tensor ti, which has n elements
+struct Chunk {
+    int ti;
+    long long n, base, end;
+};
+FF_DEV Chunk my_chunk(const ChunkTable& c) {
+    int ti = 0;
+#pragma unroll 1
+    while (ti + 1 < c.count && (int)blockIdx.x >= c.block_start[ti + 1]) ti++;
+    const long long n = c.n[ti];
+    const long long base = (long long)((int)blockIdx.x - c.block_start[ti]) * kAdamChunk;
+    return {ti, n, base, min(n, base + (long long)kAdamChunk)};
+}
+
+static long long chunks_of(long long n) { return (n + kAdamChunk - 1) / kAdamChunk; }
+static long long grad_slots(int n_tensors, const long long* numels) {
+    long long slots = 0;
+    for (int i = 0; i < n_tensors; i++)
+        if (numels[i] > 0) slots += chunks_of(numels[i]);
+    return slots;
+}
+
+// The non-empty tensors of one call in launches of <= kAdamTensors tensors and <= kGradMaxBlocks workgroups.  fill(cnt, i) puts tensor i
+// into entry cnt of the table `c` is part of; launch(blocks, slot) enqueues the kernel on that table, slot = the workgroups of the call's
+// earlier launches.  Both return FF_OK or the error that ends the call.
+template <typename Fill, typename Launch>
+static int chunk_launches(const char* what, ChunkTable& c, int n_tensors, const long long* numels, Fill&& fill, Launch&& launch) {
+    long long slot = 0;
+    int i = 0;
+    while (i < n_tensors) {
+        int cnt = 0;
+        long long blocks = 0;
+        while (i < n_tensors && cnt < kAdamTensors) {
+            if (numels[i] > 0) {
+                const long long b = chunks_of(numels[i]);
+                FF_CHECK(b <= kGradMaxBlocks, FF_ERR_SHAPE, "%s: tensor %d has %lld elements", what, i, numels[i]);
+                if (blocks + b > kGradMaxBlocks) break;
+                FF_TRY(fill(cnt, i));
+                c.n[cnt] = numels[i];
+                c.block_start[cnt] = (int)blocks;
+                blocks += b;
+                cnt++;
+            }
+            i++;
+        }
+        if (!cnt) break;
+        c.block_start[cnt] = (int)blocks;
+        c.count = cnt;
+        FF_TRY(launch((int)blocks, slot));
+        slot += blocks;
+    }
+    return FF_OK;
+}
 
 struct AdamTable {
     void* p[kAdamTensors];
@@ -20,9 +83,7 @@ struct AdamTable {
     void* m[kAdamTensors];
     void* v[kAdamTensors];
     float* w[kAdamTensors];  // fp32 master copies of the parameters (mixed-precision mode), else unused
-    long long n[kAdamTensors];
-    int block_start[kAdamTensors + 1];
-    int count;
+    ChunkTable chunks;
     float lr, beta1, beta2, eps, decay, bc1, bc2_sqrt, grad_scale;
     const float* step_dev;   // capturable mode: the step count lives on the device (HIP-graph replays cannot change kernel arguments)
     const float* lr_dev;     // ... and so does the learning rate, when a scheduler is to stay effective under replay
@@ -33,24 +94,28 @@ struct AdamTable {
 // T: storage type of the parameters' compute copy and of the gradients; ST: storage type of the two moments; MASTER: the update
 // is applied to an fp32 master copy (t.w) and the compute copy is its rounding - what `--fp16` / bf16 autocast training keeps
 // (training/train.sh:24), so that steps far below bf16 resolution of a weight (lr 1e-4) are not lost.
-// MODE 1 (default for the bf16-state kernel; FF_ADAMW_MODE=0 for A/B): gradients and moments, touched once per step, are streamed with
-// nontemporal accesses so that they do not evict what the next kernels read (37.52 -> 37.40 ms/step at config B in a same-box A/B)
+// bf16 parameters (NT): gradients, moments and master copies, touched once per step, are streamed with nontemporal accesses so that they
+// do not evict what the next kernels read (37.52 -> 37.40 ms/step at config B in a same-box A/B); fp32 parameters use plain accesses.
 // CLIP: every gradient is also multiplied by *t.grad_coef (gradient clipping by global norm, ff_grad_clip_coef); the kernels without it
 // are the ones the unclipped step always ran.
 // GT: storage type of the gradients - T, or float where the gradients are the fp32 accumulators of ff_grad_accumulate (ff_adamw_step_acc).
 // GUARD (implies CLIP; ff_adamw_step_guarded): every workgroup reads *t.skip first and returns before it touches a tensor when it is set -
 // a skipped launch is a no-op (no weight decay, no moment decay, no master write).  The read and the branch are wave-uniform.
-template <typename T, typename ST, bool MASTER, int VEC, int MODE = 0, bool CLIP = false, typename GT = T, bool GUARD = false>
+template <typename T, typename ST, bool MASTER, bool CLIP = false, typename GT = T, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     static_assert(!GUARD || CLIP, "GUARD implies CLIP");
+    constexpr int VEC = Vec<T>::N;
+    constexpr bool NT = !std::is_same_v<T, float>;
     if constexpr (GUARD) {
         if (*t.skip != 0.f) return;
     }
+    // my_chunk(t.chunks), written out: with the call hipcc pairs the moment updates of the CLIP kernels with bf16 parameters and fp32 moments
+    // into four fewer packed multiply-adds, and their results change in the last bit
     int ti = 0;
 #pragma unroll 1
-    while (ti + 1 < t.count && (int)blockIdx.x >= t.block_start[ti + 1]) ti++;
-    const long long n = t.n[ti];
-    const long long base = (long long)((int)blockIdx.x - t.block_start[ti]) * kAdamChunk;
+    while (ti + 1 < t.chunks.count && (int)blockIdx.x >= t.chunks.block_start[ti + 1]) ti++;
+    const long long n = t.chunks.n[ti];
+    const long long base = (long long)((int)blockIdx.x - t.chunks.block_start[ti]) * kAdamChunk;
     T* p = (T*)t.p[ti];
     const GT* g = (const GT*)t.g[ti];
     ST* m = (ST*)t.m[ti];
@@ -77,7 +142,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
 #pragma unroll
         for (int c = 0; c < VEC / QN; c++) {
             float part[QN];
-            if constexpr (decltype(stream)::value && MODE >= 1) Vec<Q>::load_nt(q + i + c * QN, part);
+            if constexpr (decltype(stream)::value && NT) Vec<Q>::load_nt(q + i + c * QN, part);
             else Vec<Q>::load(q + i + c * QN, part);
 #pragma unroll
             for (int e = 0; e < QN; e++) o[c * QN + e] = part[e];
@@ -91,7 +156,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
             float part[QN];
 #pragma unroll
             for (int e = 0; e < QN; e++) part[e] = o[c * QN + e];
-            if constexpr (decltype(stream)::value && MODE >= 1) Vec<Q>::store_nt(q + i + c * QN, part);
+            if constexpr (decltype(stream)::value && NT) Vec<Q>::store_nt(q + i + c * QN, part);
             else Vec<Q>::store(q + i + c * QN, part);
         }
     };
@@ -157,26 +222,28 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     }
 }
 
-template <bool CLIP, bool GUARD = false>
-static void adamw_dispatch(int dtype, bool master, int state_dtype, dim3 grid, hipStream_t stream, const AdamTable& t) {
-    const dim3 block(256);
-    if (dtype == FF_DTYPE_F32) adamw_kernel<float, float, false, 4, 0, CLIP, float, GUARD><<<grid, block, 0, stream>>>(t);
-    else if (master) adamw_kernel<bf16, float, true, 8, 1, CLIP, bf16, GUARD><<<grid, block, 0, stream>>>(t);  // (master copy, gradients, moments: streamed nontemporally)
-    else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1, CLIP, bf16, GUARD><<<grid, block, 0, stream>>>(t);
-    else {
-        static const int mode = CLIP ? 1 : dbg_switch("FF_ADAMW_MODE", 1);
-        if (mode >= 1) adamw_kernel<bf16, bf16, false, 8, 1, CLIP, bf16, GUARD><<<grid, block, 0, stream>>>(t);
-        else if constexpr (!CLIP) adamw_kernel<bf16, bf16, false, 8><<<grid, block, 0, stream>>>(t);
-    }
-}
-
-// bf16 parameters with fp32 gradients (ff_adamw_step_acc): the three storage modes of adamw_dispatch, MODE 1, GT = float
-template <bool CLIP, bool GUARD = false>
-static void adamw_dispatch_acc(bool master, int state_dtype, dim3 grid, hipStream_t stream, const AdamTable& t) {
-    const dim3 block(256);
-    if (master) adamw_kernel<bf16, float, true, 8, 1, CLIP, float, GUARD><<<grid, block, 0, stream>>>(t);
-    else if (state_dtype == FF_DTYPE_F32) adamw_kernel<bf16, float, false, 8, 1, CLIP, float, GUARD><<<grid, block, 0, stream>>>(t);
-    else adamw_kernel<bf16, bf16, false, 8, 1, CLIP, float, GUARD><<<grid, block, 0, stream>>>(t);
+// The one place a storage mode and a variant become an instantiation: (4 storage modes with gradients in the parameter's type + the 3
+// bf16-parameter ones with fp32 gradients) x 3 variants = 21 kernels.
+enum AdamVariant { kAdamPlain, kAdamClip, kAdamGuard };
+static void adamw_dispatch(int dtype, bool master, int state_dtype, bool grads32, AdamVariant variant, dim3 grid, hipStream_t stream,
+                           const AdamTable& t) {
+    auto run = [&](auto p, auto s, auto has_master, auto g) {      // the three variants of one (parameter, moment, master, gradient) storage
+        typedef decltype(p) T;
+        typedef decltype(s) ST;
+        typedef decltype(g) GT;
+        constexpr bool MASTER = decltype(has_master)::value;
+        if (variant == kAdamGuard) adamw_kernel<T, ST, MASTER, true, GT, true><<<grid, 256, 0, stream>>>(t);
+        else if (variant == kAdamClip) adamw_kernel<T, ST, MASTER, true, GT, false><<<grid, 256, 0, stream>>>(t);
+        else adamw_kernel<T, ST, MASTER, false, GT, false><<<grid, 256, 0, stream>>>(t);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    const float f{};                                              // (values that only carry their types into `run`)
+    const bf16 h{};
+    if (dtype == FF_DTYPE_F32) run(f, f, no, f);
+    else if (master) grads32 ? run(h, f, yes, f) : run(h, f, yes, h);
+    else if (state_dtype == FF_DTYPE_F32) grads32 ? run(h, f, no, f) : run(h, f, no, h);
+    else grads32 ? run(h, h, no, f) : run(h, h, no, h);
 }
 
 // acc_grads: the gradients are fp32 whatever d->dtype is (for fp32 parameters that is what the fp32 kernels read anyway)
@@ -198,36 +265,17 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
     t.bc1 = 1.f - powf(d->beta1, (float)std::max(d->step, 1));
     t.bc2_sqrt = sqrtf(1.f - powf(d->beta2, (float)std::max(d->step, 1)));
     t.grad_scale = d->grad_scale == 0.f ? 1.f : d->grad_scale;
-    int i = 0;
-    while (i < d->n_tensors) {
-        int cnt = 0, blocks = 0;
-        while (i < d->n_tensors && cnt < kAdamTensors) {
-            if (numels[i] > 0) {
-                FF_CHECK(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && (!master || master[i]), FF_ERR_SHAPE, "ff_adamw_step: tensor %d has a null pointer", i);
-                t.p[cnt] = params[i]; t.g[cnt] = grads[i]; t.m[cnt] = exp_avg[i]; t.v[cnt] = exp_avg_sq[i]; t.n[cnt] = numels[i];
-                t.w[cnt] = master ? master[i] : nullptr;
-                t.block_start[cnt] = blocks;
-                blocks += cdiv(numels[i], kAdamChunk);
-                cnt++;
-            }
-            i++;
-        }
-        if (!cnt) break;
-        t.block_start[cnt] = blocks;
-        t.count = cnt;
-        const dim3 grid(blocks);
+    const AdamVariant variant = skip ? kAdamGuard : grad_coef ? kAdamClip : kAdamPlain;
+    return chunk_launches("ff_adamw_step", t.chunks, d->n_tensors, numels, [&](int cnt, int i) -> int {
+        FF_CHECK(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && (!master || master[i]), FF_ERR_SHAPE, "ff_adamw_step: tensor %d has a null pointer", i);
+        t.p[cnt] = params[i]; t.g[cnt] = grads[i]; t.m[cnt] = exp_avg[i]; t.v[cnt] = exp_avg_sq[i];
+        t.w[cnt] = master ? master[i] : nullptr;
+        return FF_OK;
+    }, [&](int blocks, long long) -> int {
         if (master) FF_CHECK(state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: fp32 master copies go with fp32 moments");
-        if (skip) {
-            if (acc_grads && d->dtype == FF_DTYPE_BF16) adamw_dispatch_acc<true, true>(master != nullptr, state_dtype, grid, stream, t);
-            else adamw_dispatch<true, true>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
-        } else if (acc_grads && d->dtype == FF_DTYPE_BF16) {
-            if (grad_coef) adamw_dispatch_acc<true>(master != nullptr, state_dtype, grid, stream, t);
-            else adamw_dispatch_acc<false>(master != nullptr, state_dtype, grid, stream, t);
-        } else if (grad_coef) adamw_dispatch<true>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
-        else adamw_dispatch<false>(d->dtype, master != nullptr, state_dtype, grid, stream, t);
-        FF_TRY(check_launch("adamw"));
-    }
-    return FF_OK;
+        adamw_dispatch(d->dtype, master != nullptr, state_dtype, acc_grads, variant, dim3(blocks), stream, t);
+        return check_launch("adamw");
+    });
 }
 
 
@@ -237,25 +285,17 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
 // order, ff_grad_clip_coef turns the sum into the norm and the coefficient AdamW (CLIP) or ff_scale_grads applies on the device.
 struct GradTable {
     void* g[kAdamTensors];
-    long long n[kAdamTensors];
-    int block_start[kAdamTensors + 1];
-    int count;
+    ChunkTable chunks;
     float scale;             // sumsq: each gradient is multiplied by it before squaring (grad_scale)
     float* partials;         // sumsq: one slot per workgroup of the launch
     const float* coef;       // scale: device scalar every gradient is multiplied by
 };
-constexpr long long kGradMaxBlocks = 1 << 22;       // workgroups per launch (x 256 threads stays far below 2^32; block_start stays an int)
 
 template <typename T>
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const GradTable t) {
     __shared__ float red[4];
     constexpr int VEC = Vec<T>::N, PIECES = 8;      // 8 independent 16-byte loads per thread in flight before the first square
-    int ti = 0;
-#pragma unroll 1
-    while (ti + 1 < t.count && (int)blockIdx.x >= t.block_start[ti + 1]) ti++;
-    const long long n = t.n[ti];
-    const long long base = (long long)((int)blockIdx.x - t.block_start[ti]) * kAdamChunk;
-    const long long end = min(n, base + (long long)kAdamChunk);
+    const auto [ti, n, base, end] = my_chunk(t.chunks);
     const T* g = (const T*)t.g[ti];
     const float scale = t.scale;
     float acc = 0.f;
@@ -353,12 +393,7 @@ __global__ void grad_guard_kernel(const double* sum, float max_norm, const float
 template <typename T>
 __global__ __launch_bounds__(256) void grad_scale_kernel(const GradTable t) {
     constexpr int VEC = Vec<T>::N;
-    int ti = 0;
-#pragma unroll 1
-    while (ti + 1 < t.count && (int)blockIdx.x >= t.block_start[ti + 1]) ti++;
-    const long long n = t.n[ti];
-    const long long base = (long long)((int)blockIdx.x - t.block_start[ti]) * kAdamChunk;
-    const long long end = min(n, base + (long long)kAdamChunk);
+    const auto [ti, n, base, end] = my_chunk(t.chunks);
     T* g = (T*)t.g[ti];
     const float c = *t.coef;
     long long tail = base;
@@ -386,21 +421,14 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const GradTable t) {
 struct AccTable {
     const void* g[kAdamTensors];
     float* a[kAdamTensors];
-    long long n[kAdamTensors];
-    int block_start[kAdamTensors + 1];
-    int count;
+    ChunkTable chunks;
     float scale;
 };
 
 template <typename T, bool OVERWRITE>
 __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccTable t) {
     constexpr int VEC = Vec<T>::N, PIECES = 4;
-    int ti = 0;
-#pragma unroll 1
-    while (ti + 1 < t.count && (int)blockIdx.x >= t.block_start[ti + 1]) ti++;
-    const long long n = t.n[ti];
-    const long long base = (long long)((int)blockIdx.x - t.block_start[ti]) * kAdamChunk;
-    const long long end = min(n, base + (long long)kAdamChunk);
+    const auto [ti, n, base, end] = my_chunk(t.chunks);
     const T* g = (const T*)t.g[ti];
     float* a = t.a[ti];
     const float s = t.scale;
@@ -457,43 +485,18 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccTable t) 
         a[i] = fold(to_f32(g[i]), OVERWRITE ? 0.f : a[i]);
 }
 
-static long long grad_slots(int n_tensors, const long long* numels) {
-    long long slots = 0;
-    for (int i = 0; i < n_tensors; i++)
-        if (numels[i] > 0) slots += (numels[i] + kAdamChunk - 1) / kAdamChunk;
-    return slots;
-}
-
-// the tensors of one call in launches of <= kAdamTensors tensors and <= kGradMaxBlocks workgroups; launch(table, blocks, first slot)
+// ff_grad_sumsq / ff_scale_grads: launch(blocks, first slot) on `t`, filled with the next tensors of the call
 template <typename F>
 static int grad_launches(const char* what, int n_tensors, void* const* grads, const long long* numels, GradTable& t, F&& launch) {
     FF_CHECK(n_tensors >= 0 && (n_tensors == 0 || (grads && numels)), FF_ERR_SHAPE, "%s: null argument", what);
-    long long slot = 0;
-    int i = 0;
-    while (i < n_tensors) {
-        int cnt = 0;
-        long long blocks = 0;
-        while (i < n_tensors && cnt < kAdamTensors) {
-            if (numels[i] > 0) {
-                const long long b = (numels[i] + kAdamChunk - 1) / kAdamChunk;
-                FF_CHECK(b <= kGradMaxBlocks, FF_ERR_SHAPE, "%s: tensor %d has %lld elements", what, i, numels[i]);
-                if (blocks + b > kGradMaxBlocks) break;
-                FF_CHECK(grads[i], FF_ERR_SHAPE, "%s: tensor %d has a null pointer", what, i);
-                t.g[cnt] = grads[i]; t.n[cnt] = numels[i];
-                t.block_start[cnt] = (int)blocks;
-                blocks += b;
-                cnt++;
-            }
-            i++;
-        }
-        if (!cnt) break;
-        t.block_start[cnt] = (int)blocks;
-        t.count = cnt;
-        launch(t, (int)blocks, slot);
-        FF_TRY(check_launch(what));
-        slot += blocks;
-    }
-    return FF_OK;
+    return chunk_launches(what, t.chunks, n_tensors, numels, [&](int cnt, int i) -> int {
+        FF_CHECK(grads[i], FF_ERR_SHAPE, "%s: tensor %d has a null pointer", what, i);
+        t.g[cnt] = grads[i];
+        return FF_OK;
+    }, [&](int blocks, long long slot) -> int {
+        launch(blocks, slot);
+        return check_launch(what);
+    });
 }
 
 }  // namespace ff
@@ -540,10 +543,10 @@ extern "C" int ff_grad_sumsq(int dtype, int n_tensors, const void* const* grads,
     GradTable t;
     t.scale = scale;
     t.coef = nullptr;
-    return grad_launches("ff_grad_sumsq", n_tensors, (void* const*)grads, numels, t, [&](GradTable& tt, int blocks, long long slot) {
-        tt.partials = partials + slot;
-        if (dtype == FF_DTYPE_F32) grad_sumsq_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
-        else grad_sumsq_kernel<bf16><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
+    return grad_launches("ff_grad_sumsq", n_tensors, (void* const*)grads, numels, t, [&](int blocks, long long slot) {
+        t.partials = partials + slot;
+        if (dtype == FF_DTYPE_F32) grad_sumsq_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(t);
+        else grad_sumsq_kernel<bf16><<<blocks, 256, 0, (hipStream_t)stream>>>(t);
     });
 }
 extern "C" int ff_grad_sumsq_reduce(const float* partials, long long n_partials, double* sum, int accumulate, ff_stream_t stream) {
@@ -571,9 +574,9 @@ extern "C" int ff_scale_grads(int dtype, int n_tensors, void* const* grads, cons
     t.scale = 1.f;
     t.partials = nullptr;
     t.coef = coef;
-    return grad_launches("ff_scale_grads", n_tensors, grads, numels, t, [&](GradTable& tt, int blocks, long long) {
-        if (dtype == FF_DTYPE_F32) grad_scale_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
-        else grad_scale_kernel<bf16><<<blocks, 256, 0, (hipStream_t)stream>>>(tt);
+    return grad_launches("ff_scale_grads", n_tensors, grads, numels, t, [&](int blocks, long long) {
+        if (dtype == FF_DTYPE_F32) grad_scale_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(t);
+        else grad_scale_kernel<bf16><<<blocks, 256, 0, (hipStream_t)stream>>>(t);
     });
 }
 extern "C" int ff_grad_accumulate(int dtype, int n_tensors, const void* const* grads, float* const* acc, const long long* numels, float scale,
@@ -584,36 +587,19 @@ extern "C" int ff_grad_accumulate(int dtype, int n_tensors, const void* const* g
     FF_CHECK(n_tensors >= 0 && (n_tensors == 0 || (grads && acc && numels)), FF_ERR_SHAPE, "%s: null argument", what);
     AccTable t;
     t.scale = scale;
-    int i = 0;
-    while (i < n_tensors) {                         // launches of <= kAdamTensors tensors and <= kGradMaxBlocks workgroups, as grad_launches
-        int cnt = 0;
-        long long blocks = 0;
-        while (i < n_tensors && cnt < kAdamTensors) {
-            if (numels[i] > 0) {
-                const long long b = (numels[i] + kAdamChunk - 1) / kAdamChunk;
-                FF_CHECK(b <= kGradMaxBlocks, FF_ERR_SHAPE, "%s: tensor %d has %lld elements", what, i, numels[i]);
-                if (blocks + b > kGradMaxBlocks) break;
-                FF_CHECK(grads[i] && acc[i], FF_ERR_SHAPE, "%s: tensor %d has a null pointer", what, i);
-                t.g[cnt] = grads[i]; t.a[cnt] = acc[i]; t.n[cnt] = numels[i];
-                t.block_start[cnt] = (int)blocks;
-                blocks += b;
-                cnt++;
-            }
-            i++;
-        }
-        if (!cnt) break;
-        t.block_start[cnt] = (int)blocks;
-        t.count = cnt;
-        const dim3 grid((unsigned)blocks);
+    return chunk_launches(what, t.chunks, n_tensors, numels, [&](int cnt, int i) -> int {
+        FF_CHECK(grads[i] && acc[i], FF_ERR_SHAPE, "%s: tensor %d has a null pointer", what, i);
+        t.g[cnt] = grads[i]; t.a[cnt] = acc[i];
+        return FF_OK;
+    }, [&](int blocks, long long) -> int {
         hipStream_t s = (hipStream_t)stream;
         if (dtype == FF_DTYPE_F32) {
-            if (overwrite) grad_accumulate_kernel<float, true><<<grid, 256, 0, s>>>(t);
-            else grad_accumulate_kernel<float, false><<<grid, 256, 0, s>>>(t);
+            if (overwrite) grad_accumulate_kernel<float, true><<<blocks, 256, 0, s>>>(t);
+            else grad_accumulate_kernel<float, false><<<blocks, 256, 0, s>>>(t);
         } else {
-            if (overwrite) grad_accumulate_kernel<bf16, true><<<grid, 256, 0, s>>>(t);
-            else grad_accumulate_kernel<bf16, false><<<grid, 256, 0, s>>>(t);
+            if (overwrite) grad_accumulate_kernel<bf16, true><<<blocks, 256, 0, s>>>(t);
+            else grad_accumulate_kernel<bf16, false><<<blocks, 256, 0, s>>>(t);
         }
-        FF_TRY(check_launch(what));
-    }
-    return FF_OK;
+        return check_launch(what);
+    });
 }

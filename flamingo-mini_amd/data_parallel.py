@@ -422,6 +422,7 @@ class ShardedAdamW(torch.optim.Optimizer):
     # ---- the kernel call (tests substitute a torch implementation through update_fn on CPU ranks) ----
     def _hip_update(self, p, g, m, v, master, step, coef=None):
         from . import ffi
+        from .optim import adamw_step_call
         lib = ffi.lib()
         step_dev = lr_dev = None
         if self.capturable:
@@ -430,12 +431,8 @@ class ShardedAdamW(torch.optim.Optimizer):
         desc = ffi.AdamWDesc(ffi.dtype_code(p.dtype), 1, step, self.hp["lr"], self.hp["betas"][0], self.hp["betas"][1], self.hp["eps"],
                              self.hp["weight_decay"], 1.0, step_dev)
         one = lambda t: ffi.ptr_array([t])
-        if coef is None:
-            ffi.check(lib.ff_adamw_step_mixed(desc, ffi.dtype_code(m.dtype), one(p), one(g), one(m), one(v), None if master is None else one(master),
-                                              lr_dev, (C.c_longlong * 1)(p.numel()), ffi.stream_handle(p.device)), "ff_adamw_step_mixed")
-        else:
-            ffi.check(lib.ff_adamw_step_clipped(desc, ffi.dtype_code(m.dtype), one(p), one(g), one(m), one(v), None if master is None else one(master),
-                                                lr_dev, coef.data_ptr(), (C.c_longlong * 1)(p.numel()), ffi.stream_handle(p.device)), "ff_adamw_step_clipped")
+        adamw_step_call(lib, desc, ffi.dtype_code(m.dtype), (one(p), one(g), one(m), one(v), None if master is None else one(master),
+                                                             (C.c_longlong * 1)(p.numel())), lr_dev, coef, None, False, ffi.stream_handle(p.device))
 
     # ---- gradient clipping (max_grad_norm) ----
     def _shard_sumsq(self, st, g):
@@ -477,20 +474,9 @@ class ShardedAdamW(torch.optim.Optimizer):
         if self.collectives:
             dist.all_reduce(clip["sum"], op=dist.ReduceOp.SUM, group=self.group)
         if loose:
-            tables = []
-            for dt in (torch.float32, torch.bfloat16):
-                gs = [g for g in loose if g.dtype == dt]
-                if gs:
-                    n = (C.c_longlong * len(gs))(*[g.numel() for g in gs])
-                    tables.append((ffi.dtype_code(dt), gs, n, int(lib.ff_grad_sumsq_partials(len(gs), n))))
-            need = sum(t[3] for t in tables)
-            if clip["loose_partials"] is None or clip["loose_partials"].numel() < need:
-                clip["loose_partials"] = torch.zeros(max(need, 1), dtype=torch.float32, device=dev)
-            lp, off = clip["loose_partials"], 0
-            for code, gs, n, k in tables:
-                ffi.check(lib.ff_grad_sumsq(code, len(gs), ffi.ptr_array(gs), n, 1.0, lp.data_ptr() + 4 * off, lp.numel() - off, stream), "ff_grad_sumsq")
-                off += k
-            ffi.check(lib.ff_grad_sumsq_reduce(lp.data_ptr(), off, clip["sum"].data_ptr(), 1, stream), "ff_grad_sumsq_reduce")
+            from .optim import grad_sumsq_sweep, grad_tables
+            clip["loose_partials"] = grad_sumsq_sweep(lib, grad_tables(loose, "ShardedAdamW(max_grad_norm=...)"), clip["loose_partials"], clip["sum"],
+                                                      True, dev, stream)
         ffi.check(lib.ff_grad_clip_coef(clip["sum"].data_ptr(), self.max_grad_norm, clip["norm"].data_ptr(), clip["coef"].data_ptr(), stream),
                   "ff_grad_clip_coef")
         return clip["coef"]

@@ -232,23 +232,9 @@ class FusedAdamW(torch.optim.Optimizer):
                     step, step_dev = bucket["step"], None
                 desc = ffi.AdamWDesc(bucket["dtype_code"], n, step, group["lr"], group["betas"][0], group["betas"][1], group["eps"],
                                      group["weight_decay"], group["grad_scale"], step_dev)
-                if guard:
-                    ffi.check(lib.ff_adamw_step_guarded(desc, bucket["state_code"], bucket["param_ptrs"], bucket["acc_ptrs"] if acc else grad_ptrs, int(acc),
-                                                        bucket["m_ptrs"], bucket["v_ptrs"], bucket["w_ptrs"], lr_dev, coef.data_ptr(),
-                                                        self._clip["skip"].data_ptr(), bucket["numels"], ffi.stream_handle(bucket["device"])),
-                              "ff_adamw_step_guarded")
-                elif acc:
-                    ffi.check(lib.ff_adamw_step_acc(desc, bucket["state_code"], bucket["param_ptrs"], bucket["acc_ptrs"], bucket["m_ptrs"], bucket["v_ptrs"],
-                                                    bucket["w_ptrs"], lr_dev, None if coef is None else coef.data_ptr(), bucket["numels"],
-                                                    ffi.stream_handle(bucket["device"])), "ff_adamw_step_acc")
-                elif coef is None:
-                    ffi.check(lib.ff_adamw_step_mixed(desc, bucket["state_code"], bucket["param_ptrs"], grad_ptrs, bucket["m_ptrs"], bucket["v_ptrs"],
-                                                      bucket["w_ptrs"], lr_dev, bucket["numels"], ffi.stream_handle(bucket["device"])),
-                              "ff_adamw_step_mixed")
-                else:
-                    ffi.check(lib.ff_adamw_step_clipped(desc, bucket["state_code"], bucket["param_ptrs"], grad_ptrs, bucket["m_ptrs"], bucket["v_ptrs"],
-                                                        bucket["w_ptrs"], lr_dev, coef.data_ptr(), bucket["numels"], ffi.stream_handle(bucket["device"])),
-                              "ff_adamw_step_clipped")
+                adamw_step_call(lib, desc, bucket["state_code"], (bucket["param_ptrs"], bucket["acc_ptrs"] if acc else grad_ptrs, bucket["m_ptrs"],
+                                                                  bucket["v_ptrs"], bucket["w_ptrs"], bucket["numels"]),
+                                lr_dev, coef, self._clip["skip"] if guard else None, acc, ffi.stream_handle(bucket["device"]))
         if acc:
             self.reset_accumulation()                     # the cycle is closed: the next accumulate() overwrites
         return loss
@@ -278,7 +264,6 @@ class FusedAdamW(torch.optim.Optimizer):
         if any(t is not None and t.device != device for t in (ext_found, ext_scale)):
             raise ValueError("FusedAdamW.step(): found_inf / grad_scale must live on the parameters' device")
         sweep = not guard or self.skip_nonfinite or self.max_grad_norm is not None
-        slots = [int(lib.ff_grad_sumsq_partials(len(b["params"]), b["numels"])) for _, b in buckets]
         clip = self._clip
         if clip is None or clip["device"] != device:
             clip = self._clip = dict(device=device, norm=torch.zeros((), dtype=torch.float32, device=device),
@@ -295,17 +280,12 @@ class FusedAdamW(torch.optim.Optimizer):
             ffi.check(lib.ff_grad_guard(None, 0.0, ffi.ptr(ext_found), ffi.ptr(ext_scale), None, clip["coef"].data_ptr(), clip["skip"].data_ptr(),
                                         clip["take"].data_ptr(), clip["total"].data_ptr(), stream), "ff_grad_guard")
             return clip["coef"]
-        if clip["partials"] is None or clip["partials"].numel() < sum(slots):
-            clip["partials"] = torch.zeros(max(sum(slots), 1), dtype=torch.float32, device=device)
-        partials, total, off = clip["partials"], clip["partials"].numel(), 0
-        for (group, b), k in zip(buckets, slots):     # slots continue from bucket to bucket (dtypes, groups)
-            if not acc:
+        if not acc:
+            for _, b in buckets:
                 self._refresh_grad_ptrs(b)
-            ffi.check(lib.ff_grad_sumsq(ffi.DTYPE_F32 if acc else b["dtype_code"], len(b["params"]), b["acc_ptrs"] if acc else b["grad_ptrs"], b["numels"],
-                                        float(group["grad_scale"] or 1.0),
-                                        partials.data_ptr() + 4 * off, total - off, stream), "ff_grad_sumsq")
-            off += k
-        ffi.check(lib.ff_grad_sumsq_reduce(partials.data_ptr(), off, clip["sum"].data_ptr(), 0, stream), "ff_grad_sumsq_reduce")
+        tables = [(ffi.DTYPE_F32 if acc else b["dtype_code"], len(b["params"]), b["acc_ptrs"] if acc else b["grad_ptrs"], b["numels"],
+                   float(group["grad_scale"] or 1.0)) for group, b in buckets]
+        clip["partials"] = grad_sumsq_sweep(lib, tables, clip["partials"], clip["sum"], False, device, stream)
         if guard:
             ffi.check(lib.ff_grad_guard(clip["sum"].data_ptr(), self.max_grad_norm or 0.0, ffi.ptr(ext_found), ffi.ptr(ext_scale), clip["norm"].data_ptr(),
                                         clip["coef"].data_ptr(), clip["skip"].data_ptr(), clip["take"].data_ptr(), clip["total"].data_ptr(), stream),
@@ -448,6 +428,55 @@ class FusedAdamW(torch.optim.Optimizer):
         return out
 
 
+def adamw_step_call(lib, desc, state_code, ptrs, lr_dev, coef, skip, grads_fp32, stream) -> None:
+    """The one call site of the AdamW entry points.  ptrs: the pointer tables (params, grads, exp_avg, exp_avg_sq, master or None, numels);
+    coef / skip: the 0-dim device tensors of the clip coefficient and of the guard's verdict, or None; grads_fp32: the gradients are the
+    fp32 accumulators of ff_grad_accumulate.  skip -> ff_adamw_step_guarded, else grads_fp32 -> ff_adamw_step_acc (coef optional), else
+    coef -> ff_adamw_step_clipped, else ff_adamw_step_mixed."""
+    p, g, m, v, w, numels = ptrs
+    c = None if coef is None else coef.data_ptr()
+    if skip is not None:
+        name, args = "ff_adamw_step_guarded", (p, g, int(grads_fp32), m, v, w, lr_dev, c, skip.data_ptr())
+    elif grads_fp32:
+        name, args = "ff_adamw_step_acc", (p, g, m, v, w, lr_dev, c)
+    elif coef is None:
+        name, args = "ff_adamw_step_mixed", (p, g, m, v, w, lr_dev)
+    else:
+        name, args = "ff_adamw_step_clipped", (p, g, m, v, w, lr_dev, c)
+    ffi.check(getattr(lib, name)(desc, state_code, *args, numels, stream), name)
+
+
+def grad_tables(grads, who: str) -> list:
+    """Contiguous fp32 / bf16 gradient tensors as one (dtype code, n, pointer table, numels, scale 1.0) per dtype: what grad_sumsq_sweep
+    and ff_scale_grads take."""
+    tables = []
+    for dt in (torch.float32, torch.bfloat16):
+        gs = [g for g in grads if g.dtype == dt]
+        if gs:
+            if not all(g.is_contiguous() for g in gs):
+                raise ffi.FusionLibraryError(f"{who} needs contiguous gradients")
+            tables.append((ffi.dtype_code(dt), len(gs), ffi.ptr_array(gs), (C.c_longlong * len(gs))(*[g.numel() for g in gs]), 1.0))
+    if sum(t[1] for t in tables) != len(grads):
+        raise ffi.FusionLibraryError(f"{who} handles float32 and bfloat16 gradients")
+    return tables
+
+
+def grad_sumsq_sweep(lib, tables, partials, total, accumulate: bool, device, stream):
+    """The sum-of-squares sweep: *total = (accumulate ? *total : 0) + the sum of (scale * g)^2 over every tensor of `tables` [(dtype code, n,
+    pointer table, numels, scale)] - one ff_grad_sumsq per table, their per-workgroup slots continuing from table to table, and one
+    ff_grad_sumsq_reduce (fp64).  partials: the caller's slot buffer from an earlier sweep or None; returns the buffer used (a new one
+    where that was too small - every slot that is read is written first, so it is not zeroed).  Enqueues only."""
+    slots = [int(lib.ff_grad_sumsq_partials(n, numels)) for _, n, _, numels, _ in tables]
+    if partials is None or partials.numel() < sum(slots):
+        partials = torch.empty(max(sum(slots), 1), dtype=torch.float32, device=device)
+    off = 0
+    for (code, n, ptrs, numels, scale), k in zip(tables, slots):      # slots continue from table to table (dtypes, groups)
+        ffi.check(lib.ff_grad_sumsq(code, n, ptrs, numels, scale, partials.data_ptr() + 4 * off, partials.numel() - off, stream), "ff_grad_sumsq")
+        off += k
+    ffi.check(lib.ff_grad_sumsq_reduce(partials.data_ptr(), off, total.data_ptr(), int(accumulate), stream), "ff_grad_sumsq_reduce")
+    return partials
+
+
 def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False) -> torch.Tensor:
     """torch.nn.utils.clip_grad_norm_ (norm_type 2) on the device: the total L2 norm of the gradients of `parameters` (fp32 0-dim tensor,
     summed in fp32 per workgroup and in fp64 over workgroups, also for bf16 gradients) is returned, and every gradient is multiplied in
@@ -467,29 +496,15 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_i
     device = devices.pop()
     lib = ffi.lib()
     stream = ffi.stream_handle(device)
-    tables = []
-    for dt in (torch.float32, torch.bfloat16):
-        gs = [g for g in grads if g.dtype == dt]
-        if gs:
-            if not all(g.is_contiguous() for g in gs):
-                raise ffi.FusionLibraryError("clip_grad_norm_ needs contiguous gradients")
-            tables.append((ffi.dtype_code(dt), len(gs), ffi.ptr_array(gs), (C.c_longlong * len(gs))(*[g.numel() for g in gs])))
-    if sum(n for _, n, _, _ in tables) != len(grads):
-        raise ffi.FusionLibraryError("clip_grad_norm_ handles float32 and bfloat16 gradients")
-    slots = [int(lib.ff_grad_sumsq_partials(n, numels)) for _, n, _, numels in tables]
-    partials = torch.empty(max(sum(slots), 1), dtype=torch.float32, device=device)
+    tables = grad_tables(grads, "clip_grad_norm_")
     total = torch.empty((), dtype=torch.float64, device=device)
     norm = torch.empty((), dtype=torch.float32, device=device)
     coef = torch.empty((), dtype=torch.float32, device=device)
-    off = 0
-    for (code, n, ptrs, numels), k in zip(tables, slots):
-        ffi.check(lib.ff_grad_sumsq(code, n, ptrs, numels, 1.0, partials.data_ptr() + 4 * off, partials.numel() - off, stream), "ff_grad_sumsq")
-        off += k
-    ffi.check(lib.ff_grad_sumsq_reduce(partials.data_ptr(), off, total.data_ptr(), 0, stream), "ff_grad_sumsq_reduce")
+    grad_sumsq_sweep(lib, tables, None, total, False, device, stream)
     ffi.check(lib.ff_grad_clip_coef(total.data_ptr(), float(max_norm), norm.data_ptr(), coef.data_ptr(), stream), "ff_grad_clip_coef")
     if error_if_nonfinite and not bool(torch.isfinite(norm)):
         raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be clipped. "
                            "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
-    for code, n, ptrs, numels in tables:
+    for code, n, ptrs, numels, _ in tables:
         ffi.check(lib.ff_scale_grads(code, n, ptrs, numels, coef.data_ptr(), stream), "ff_scale_grads")
     return norm

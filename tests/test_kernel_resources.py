@@ -51,3 +51,19 @@ def test_one_workgroup_per_cu_kernels_fit_their_waves():
             assert r["occupancy"] >= 2 and r["scratch"] == 0, r
         if "xa_qattn_fwd_res_kernel" in r["mangled"] or "xa_dattn_bwd_res_kernel" in r["mangled"]:
             assert r["occupancy"] >= 2 and r["scratch"] == 0, r
+
+
+def test_optimizer_kernels_keep_their_occupancy_without_scratch():
+    """ff_optim's kernels are HBM-bound streams that hide latency with resident waves.  Floors in waves per SIMD: 4 for every adamw_kernel
+    instantiation (5 only for bf16 moments with bf16 gradients), 7 for the sum-of-squares and accumulate kernels, 8 for grad_scale_kernel."""
+    floors = {"adamw_kernel": 4, "grad_sumsq_kernel": 7, "grad_accumulate_kernel": 7, "grad_scale_kernel": 8}
+    seen = dict.fromkeys(floors, 0)
+    for r in ROWS:
+        if r["unit"] != "ff_optim":
+            continue
+        assert r["scratch"] == 0, (r["name"], r["scratch"])
+        for family, floor in floors.items():
+            if family in r["mangled"]:
+                assert r["occupancy"] >= floor, (r["name"], r["vgprs"], r["occupancy"], floor)
+                seen[family] += 1
+    assert all(seen.values()), seen
