@@ -1,0 +1,424 @@
+// Beam search on the captured decode step: the selection with all of its bookkeeping (ff_beam_step) and the in-place reorder of the static
+// LM cache by beam index (ff_beam_gather).  The rules are in include/flamingo_fusion.h; they restate FlamingoModel._beam_search.
+// ff_beam_step is two launches:
+//   beam_rows_kernel   one 256-thread workgroup per row (= one beam of one sequence), built like sample_token_kernel: a bf16 row of up to
+//                      65536 columns is staged once in LDS as order-preserving 16-bit keys; lse = max + log(sum exp(x - max)); the 2 nb-th
+//                      largest value of the row is found by bisection on the key; then the row's best 2 nb candidates under the rule's order
+//                      (score descending, column ascending) are collected: everything whose score  f(x) = (x - lse) + score[row]  is above
+//                      f(that value), then the lowest columns with a score equal to it.  f is monotone in x, so this is the row's top 2 nb
+//                      by SCORE even where two different logits round to one score.  A sequence's top 2 nb over nb V candidates lies in the
+//                      union of its rows' top 2 nb.
+//   beam_merge_kernel  one wave per sequence: ranks the nb x 2 nb candidates by counting (keys are integers: a total order whatever the
+//                      row held), then lane 0 walks the best 2 nb as the Python loop does and writes the state block.
+// Every sum has a fixed order (thread-local in column order, xor butterfly in the wave, wave 0..3): equal inputs give equal bits.
+#include <cmath>
+
+#include "ff_common.h"
+#include "ff_internal.h"
+
+namespace ff {
+
+constexpr int kBeamScratch = 2304;            // n_gt[256] ints | n_eq[256] ints | red[16] words | cand score[16] | cand column[16]: the key image starts behind them
+constexpr int kBeamStageMax = 65536;          // columns of a staged row (128 KiB of keys)
+constexpr int kBeamCand = 2 * FF_BEAM_MAX;    // candidates a row contributes at most
+
+// order-preserving key of a float: a > b  <=>  key(a) > key(b) for all non-NaN values (-0 is +0).  A bf16 value's key is the top 16 bits.
+template <int BITS> FF_DEV unsigned beam_key(float v) {
+    unsigned b = __float_as_uint(v);
+    if (b == 0x80000000u) b = 0;
+    return ((b >> 31) ? ~b : (b | 0x80000000u)) >> (32 - BITS);
+}
+template <int BITS> FF_DEV float beam_value(unsigned k) {
+    const unsigned k32 = k << (32 - BITS);
+    return __uint_as_float((k32 >> 31) ? (k32 & 0x7FFFFFFFu) : (~k32 & (0xFFFFFFFFu << (32 - BITS))));
+}
+
+// f(column, value) over a row whose start is only element-aligned: scalar head up to the next 16-byte boundary, 16-byte vectors with four
+// requests in flight (one workgroup has its CU to itself), scalar tail.  A thread sees its columns in the order of the plain loop.
+template <typename T, typename F>
+FF_DEV void beam_row_vectors4(const T* row, int V, F&& f) {
+    constexpr int N = Vec<T>::N;
+    int head = (int)(((16u - (unsigned)((unsigned long long)row & 15u)) & 15u) / sizeof(T));
+    head = head < V ? head : V;
+    const int nvec = (V - head) / N, tail0 = head + nvec * N;
+    if ((int)threadIdx.x < head) f((int)threadIdx.x, to_f32(row[threadIdx.x]));
+    for (int v = threadIdx.x; v < nvec; v += 1024) {
+        typename Vec<T>::raw q[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int vj = v + 256 * j;
+            q[j] = *(const typename Vec<T>::raw*)(row + head + (vj < nvec ? vj : v) * N);       // (out of range: the first vector again, unused)
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int vj = v + 256 * j;
+            if (vj < nvec) {
+#pragma unroll
+                for (int e = 0; e < N; e++) f(head + vj * N + e, (float)q[j][e]);
+            }
+        }
+    }
+    for (int c = tail0 + threadIdx.x; c < V; c += 256) f(c, to_f32(row[c]));
+}
+
+FF_DEV int beam_block_sum_int(int v, int* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+FF_DEV unsigned beam_block_max_uint(unsigned v, unsigned* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
+        v = v > w ? v : w;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const unsigned a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
+    return a > b ? a : b;
+}
+
+// cand_score / cand_col: [rows][K], this row's best K candidates in no particular order (the merge ranks them)
+template <typename T, bool STAGED>
+__global__ __launch_bounds__(256) void beam_rows_kernel(int V, long long ld, const T* __restrict__ logits, int K, const float* __restrict__ score,
+                                                        float* __restrict__ cand_score, int* __restrict__ cand_col) {
+    constexpr int BITS = sizeof(T) == 2 ? 16 : 32;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    pin_args(V, ld, logits, K, score, cand_score, cand_col);
+    int* n_gt = (int*)smem_raw;
+    int* n_eq = (int*)(smem_raw + 1024);
+    float* red = (float*)(smem_raw + 2048);
+    float* cs = (float*)(smem_raw + 2112);
+    int* cc = (int*)(smem_raw + 2176);
+    unsigned short* sk = (unsigned short*)(smem_raw + kBeamScratch);              // STAGED: keys of columns [0, 8 ceil(V / 8)), the padding 0
+    const int tid = threadIdx.x;
+    const T* row = logits + (long long)blockIdx.x * ld;
+
+    // f(key) for every column in a fixed thread / order assignment; STAGED also visits the padding keys (0: see the callers)
+    // (every lambda here is forced inline: behind a call its captured counters would live in scratch memory)
+    auto each = [&](auto&& f) __attribute__((always_inline)) {
+        if constexpr (STAGED) {
+            const int nvec = (V + 7) >> 3;
+            for (int v = tid; v < nvec; v += 1024) {
+                uint4 q[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) q[j] = v + 256 * j < nvec ? *(const uint4*)(sk + (v + 256 * j) * 8) : uint4{0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const unsigned w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+                    for (int e = 0; e < 4; e++) { f(w[e] & 0xFFFFu); f(w[e] >> 16); }
+                }
+            }
+        } else {
+            beam_row_vectors4(row, V, [&](int, float x) __attribute__((always_inline)) { f(beam_key<BITS>(x)); });
+        }
+    };
+    // thread t's own columns [t C, (t + 1) C) in column order, C a multiple of 8: f(column, key), column < V
+    const int C = ((((V + 255) >> 8) + 7) >> 3) << 3;
+    const int c0 = tid * C < V ? tid * C : V, c1 = c0 + C < V ? c0 + C : V;
+    auto own = [&](auto&& f) __attribute__((always_inline)) {
+        if constexpr (STAGED) {
+            for (int c = c0; c < c1; c += 32) {
+                uint4 q[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) q[j] = c + 8 * j < c1 ? *(const uint4*)(sk + c + 8 * j) : uint4{0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const unsigned w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        if (c + 8 * j + 2 * e < c1) f(c + 8 * j + 2 * e, w[e] & 0xFFFFu);
+                        if (c + 8 * j + 2 * e + 1 < c1) f(c + 8 * j + 2 * e + 1, w[e] >> 16);
+                    }
+                }
+            }
+        } else {
+            for (int c = c0; c < c1; c++) f(c, beam_key<BITS>(to_f32(row[c])));
+        }
+    };
+
+    unsigned kmax = 0;
+    if constexpr (STAGED) {
+        beam_row_vectors4(row, V, [&](int c, float x) __attribute__((always_inline)) {
+            const unsigned k = beam_key<BITS>(x);
+            sk[c] = (unsigned short)k;
+            kmax = k > kmax ? k : kmax;
+        });
+        for (int c = V + tid; c < ((V + 7) & ~7); c += 256) sk[c] = 0;
+    } else {
+        each([&](unsigned k) __attribute__((always_inline)) { kmax = k > kmax ? k : kmax; });
+    }
+    if (tid < kBeamCand) { cs[tid] = -INFINITY; cc[tid] = tid < V ? tid : 0; }     // what a row of NaN / +inf leaves behind: in range
+    kmax = beam_block_max_uint(kmax, (unsigned*)red);                              // (its barriers also publish the key image)
+    const float xmax = beam_value<BITS>(kmax);
+
+    // rule 1: lse = max + log(sum exp(x - max)); a padding key (0 = a NaN of the lowest order) is skipped, it is no column
+    float s = 0.f;
+    if constexpr (STAGED) each([&](unsigned k) __attribute__((always_inline)) { if (k) s += expf(beam_value<BITS>(k) - xmax); });
+    else each([&](unsigned k) __attribute__((always_inline)) { s += expf(beam_value<BITS>(k) - xmax); });
+    s = block_sum<4>(s, red);
+    const float lse = xmax + logf(s);
+    const float sc = score[blockIdx.x];
+    auto f = [lse, sc](unsigned k) __attribute__((always_inline)) { return (beam_value<BITS>(k) - lse) + sc; };         // rules 2 and 3: two roundings
+
+    // the K-th largest key = the largest t with count(key >= t) >= K (V >= K: t = 0 qualifies; padding keys never count, t >= 1)
+    unsigned tk = 0;
+    for (int bit = BITS - 1; bit >= 0; bit--) {
+        const unsigned cand = tk | (1u << bit);
+        int n = 0;
+        each([&](unsigned k) __attribute__((always_inline)) { n += k >= cand ? 1 : 0; });
+        if (beam_block_sum_int(n, (int*)red) >= K) tk = cand;
+    }
+    const float fk = f(tk);
+
+    // rule 4 inside the row: scores above fk (fewer than K: they belong to logits above the K-th largest), then the lowest columns at fk
+    int gt = 0, eq = 0;
+    own([&](int, unsigned k) __attribute__((always_inline)) {
+        const float v = f(k);
+        gt += v > fk ? 1 : 0;
+        eq += v == fk ? 1 : 0;
+    });
+    n_gt[tid] = gt;
+    n_eq[tid] = eq;
+    __syncthreads();
+    int gt_before = 0, eq_before = 0, gt_all = 0;
+    for (int t = 0; t < 256; t++) {
+        const int g = n_gt[t], e = n_eq[t];
+        if (t < tid) { gt_before += g; eq_before += e; }
+        gt_all += g;
+    }
+    int ig = gt_before, ie = gt_all + eq_before;
+    own([&](int c, unsigned k) __attribute__((always_inline)) {
+        const float v = f(k);
+        const bool g = v > fk, e = v == fk;
+        const int slot = g ? ig : ie;
+        if ((g || e) && slot < K) { cs[slot] = v; cc[slot] = c; }
+        ig += g ? 1 : 0;
+        ie += e ? 1 : 0;
+    });
+    __syncthreads();
+    if (tid < K) {
+        cand_score[(long long)blockIdx.x * K + tid] = cs[tid];
+        cand_col[(long long)blockIdx.x * K + tid] = cc[tid];
+    }
+}
+
+struct BeamState {
+    int b, nb, vocab, max_len, eos, pad, early_stopping;
+    float* score; int* done; int* n_hyp; float* hyp_score; int* hyp_len; int* hyp_row;
+    long long* hist_tok; int* hist_parent; float* hist_score; long long* next_tok; long long* beam_idx;
+    const float* len_norm; const long long* cur_len;
+};
+
+// one wave per sequence: rank the nb K candidates (score descending, beam then column ascending = flat index ascending, slot last), walk
+__global__ __launch_bounds__(64) void beam_merge_kernel(BeamState st, const float* __restrict__ cand_score, const int* __restrict__ cand_col) {
+    __shared__ unsigned key[FF_BEAM_MAX * kBeamCand];
+    __shared__ int col[FF_BEAM_MAX * kBeamCand];
+    __shared__ float top_s[kBeamCand];
+    __shared__ int top_beam[kBeamCand], top_col[kBeamCand];
+    __shared__ float ns[FF_BEAM_MAX];
+    __shared__ int nt[FF_BEAM_MAX], np[FF_BEAM_MAX];
+    const int s = blockIdx.x, nb = st.nb, K = 2 * nb, n = nb * K, tid = threadIdx.x;
+    const long long r0 = (long long)s * nb;
+    for (int j = tid; j < n; j += 64) {
+        key[j] = beam_key<32>(cand_score[r0 * K + j]);
+        int c = cand_col[r0 * K + j];
+        col[j] = c < 0 ? 0 : (c >= st.vocab ? st.vocab - 1 : c);
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 64) {
+        const unsigned ki = key[i];
+        const int bi = i / K, ci = col[i];
+        int rank = 0;
+        for (int j = 0; j < n; j++) {
+            const unsigned kj = key[j];
+            const int bj = j / K, cj = col[j];
+            const bool better = kj > ki || (kj == ki && (bj < bi || (bj == bi && (cj < ci || (cj == ci && j < i)))));
+            rank += better ? 1 : 0;
+        }
+        if (rank < K) { top_s[rank] = beam_value<32>(ki); top_beam[rank] = bi; top_col[rank] = ci; }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+
+    long long cur = *st.cur_len;
+    cur = cur < 1 ? 1 : (cur > st.max_len ? st.max_len : cur);                     // (a length outside the tables: no write leaves them)
+    const float norm = st.len_norm[cur];
+    float* hs = st.hyp_score + r0;
+    int* hl = st.hyp_len + r0;
+    int* hr = st.hyp_row + r0;
+    for (int k = 0; k < nb; k++) { ns[k] = -INFINITY; nt[k] = st.pad; np[k] = k; }
+    if (!st.done[s]) {
+        int nh = st.n_hyp[s];
+        nh = nh < 0 ? 0 : (nh > nb ? nb : nh);
+        int k = 0;
+        for (int rank = 0; rank < K && k < nb; rank++) {
+            const float v = top_s[rank];
+            const int beam = top_beam[rank], tok = top_col[rank];
+            if (st.eos >= 0 && tok == st.eos) {
+                if (rank < nb) {                                                     // a finished hypothesis: kept sorted, equal scores in arrival order
+                    const float h = v / norm;
+                    int p = 0;
+                    while (p < nh && hs[p] >= h) p++;
+                    if (p < nb) {
+                        for (int j = nh < nb - 1 ? nh : nb - 1; j > p; j--) { hs[j] = hs[j - 1]; hl[j] = hl[j - 1]; hr[j] = hr[j - 1]; }
+                        hs[p] = h; hl[p] = (int)cur; hr[p] = (int)r0 + beam;
+                        nh = nh < nb ? nh + 1 : nb;
+                    }
+                }
+                continue;
+            }
+            ns[k] = v; nt[k] = tok; np[k] = beam;
+            k++;
+        }
+        st.n_hyp[s] = nh;
+        if (nh >= nb) {
+            float best = ns[0];
+            for (int j = 1; j < nb; j++) best = fmaxf(best, ns[j]);
+            if (st.early_stopping || hs[nb - 1] >= best / norm) st.done[s] = 1;
+        }
+    }
+    const long long h0 = (cur - 1) * (long long)st.b * nb + r0;
+    for (int k = 0; k < nb; k++) {
+        st.score[r0 + k] = ns[k];
+        st.next_tok[r0 + k] = nt[k];
+        st.beam_idx[r0 + k] = r0 + np[k];
+        st.hist_tok[h0 + k] = nt[k];
+        st.hist_parent[h0 + k] = (int)r0 + np[k];
+        st.hist_score[h0 + k] = ns[k];
+    }
+}
+
+template <typename T, bool STAGED>
+static int beam_rows_launch(int rows, int V, long long ld, const void* logits, int K, const float* score, float* cand_score, int* cand_col, hipStream_t st) {
+    const size_t lds = kBeamScratch + (STAGED ? (size_t)((V + 7) / 8) * 16 : 0);
+    if (STAGED) {                                                                  // beyond 64 KiB of dynamic LDS a kernel has to ask once per device
+        static bool attr_done[64] = {};
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
+            hipError_t e = hipFuncSetAttribute((const void*)beam_rows_kernel<T, STAGED>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               kBeamScratch + kBeamStageMax * 2);
+            FF_CHECK(e == hipSuccess, FF_ERR_LAUNCH, "hipFuncSetAttribute(beam_rows lds): %s", hipGetErrorString(e));
+            if (dev >= 0 && dev < 64) attr_done[dev] = true;
+        }
+    }
+    beam_rows_kernel<T, STAGED><<<dim3(rows), dim3(256), lds, st>>>(V, ld, (const T*)logits, K, score, cand_score, cand_col);
+    return check_launch("beam_rows");
+}
+
+// ---- in-place gather of cache rows --------------------------------------------------------------------------------------------------
+constexpr int kGatherTensors = 48;            // pointers one launch carries in its kernel argument; longer tables are split
+struct GatherTable {
+    void* t[kGatherTensors];
+};
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+// Tensors (rows, outer, len_max, inner) seen as units U of 16, 4 or 2 bytes, `units` per (row, o, p).  One thread owns ONE unit offset of a
+// sequence in all of its nb rows: it loads the nb units its rows will hold, then stores them, so no thread reads what another writes.
+template <typename U, int NB>
+__global__ __launch_bounds__(256) void beam_gather_kernel(GatherTable tab, long long outer, long long len_max, long long units,
+                                                          const long long* __restrict__ beam_idx, const long long* __restrict__ n_pos) {
+    long long np = *n_pos;
+    np = np < 0 ? 0 : (np > len_max ? len_max : np);
+    const long long span = np * units;                                            // live units of one (row, o)
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= outer * span) return;
+    const long long r0 = (long long)blockIdx.y * NB;
+    int src[NB];
+    bool identity = true;
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+        const long long g = beam_idx[r0 + k] - r0;
+        src[k] = g < 0 || g >= NB ? k : (int)g;                                    // (an index outside the sequence's rows: the row stays)
+        identity = identity && src[k] == k;
+    }
+    if (identity) return;
+    const long long o = idx / span;
+    const long long row_units = outer * len_max * units;
+    U* base = (U*)tab.t[blockIdx.z] + r0 * row_units + o * len_max * units + (idx - o * span);
+    U v[NB];
+#pragma unroll
+    for (int k = 0; k < NB; k++) v[k] = base[src[k] * row_units];
+#pragma unroll
+    for (int k = 0; k < NB; k++)
+        if (src[k] != k) base[k * row_units] = v[k];
+}
+
+template <typename U>
+static int gather_launches(int n_tensors, void* const* tensors, int b, int nb, long long outer, long long len_max, long long units,
+                           const long long* beam_idx, const long long* n_pos, hipStream_t st) {
+    const long long blocks = (outer * len_max * units + 255) / 256;
+    FF_CHECK(blocks <= 0x7FFFFFFFll && b <= 65535, FF_ERR_SHAPE, "ff_beam_gather: %lld blocks x %d sequences exceed a launch", blocks, b);
+    for (int t0 = 0; t0 < n_tensors; t0 += kGatherTensors) {
+        const int cnt = n_tensors - t0 < kGatherTensors ? n_tensors - t0 : kGatherTensors;
+        GatherTable tab = {};
+        for (int i = 0; i < cnt; i++) tab.t[i] = tensors[t0 + i];
+        const dim3 grid((unsigned)blocks, b, cnt);
+#define FF_GATHER_NB(NB) case NB: beam_gather_kernel<U, NB><<<grid, dim3(256), 0, st>>>(tab, outer, len_max, units, beam_idx, n_pos); break;
+        switch (nb) {
+            FF_GATHER_NB(1) FF_GATHER_NB(2) FF_GATHER_NB(3) FF_GATHER_NB(4) FF_GATHER_NB(5) FF_GATHER_NB(6) FF_GATHER_NB(7) FF_GATHER_NB(8)
+        }
+#undef FF_GATHER_NB
+        FF_TRY(check_launch("beam_gather"));
+    }
+    return FF_OK;
+}
+
+}  // namespace ff
+
+extern "C" size_t ff_beam_workspace_bytes(int b, int nb) {
+    if (b <= 0 || nb < 1 || nb > FF_BEAM_MAX) return 0;
+    return (size_t)b * nb * 2 * nb * (sizeof(float) + sizeof(int));
+}
+
+extern "C" int ff_beam_step(const ff_beam_desc* d, const void* logits, const long long* cur_len, void* workspace, size_t workspace_bytes,
+                            ff_stream_t stream) {
+    using namespace ff;
+    FF_CHECK(d && logits && cur_len && workspace, FF_ERR_SHAPE, "ff_beam_step: null descriptor, logits, cur_len or workspace");
+    FF_CHECK(d->score && d->done && d->n_hyp && d->hyp_score && d->hyp_len && d->hyp_row && d->hist_tok && d->hist_parent && d->hist_score &&
+                 d->next_tok && d->beam_idx && d->len_norm, FF_ERR_SHAPE, "ff_beam_step: null state pointer");
+    FF_CHECK(d->b > 0 && d->nb >= 1 && d->nb <= FF_BEAM_MAX, FF_ERR_SHAPE, "ff_beam_step: b %d, nb %d (need b > 0, 1 <= nb <= %d)", d->b, d->nb, FF_BEAM_MAX);
+    FF_CHECK(d->vocab >= 2 * d->nb && d->ld >= d->vocab, FF_ERR_SHAPE, "ff_beam_step: vocab %d, ld %lld (need vocab >= 2 nb = %d, ld >= vocab)", d->vocab, d->ld, 2 * d->nb);
+    FF_CHECK(d->max_len >= 1 && (long long)d->b * d->nb <= 0x7FFFFFFF / (2 * FF_BEAM_MAX), FF_ERR_SHAPE, "ff_beam_step: max_len %d, %d x %d rows", d->max_len, d->b, d->nb);
+    FF_CHECK(workspace_bytes >= ff_beam_workspace_bytes(d->b, d->nb), FF_ERR_SHAPE, "ff_beam_step: workspace %zu < %zu bytes", workspace_bytes,
+             ff_beam_workspace_bytes(d->b, d->nb));
+    FF_CHECK(d->dtype == FF_DTYPE_F32 || d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_beam_step: dtype %d", d->dtype);
+    const hipStream_t st = (hipStream_t)stream;
+    const int rows = d->b * d->nb, K = 2 * d->nb, V = d->vocab;
+    float* cand_score = (float*)workspace;
+    int* cand_col = (int*)(cand_score + (size_t)rows * K);
+    if (d->dtype == FF_DTYPE_BF16) {
+        if (V <= kBeamStageMax) FF_TRY((beam_rows_launch<bf16, true>(rows, V, d->ld, logits, K, d->score, cand_score, cand_col, st)));
+        else FF_TRY((beam_rows_launch<bf16, false>(rows, V, d->ld, logits, K, d->score, cand_score, cand_col, st)));
+    } else {
+        FF_TRY((beam_rows_launch<float, false>(rows, V, d->ld, logits, K, d->score, cand_score, cand_col, st)));
+    }
+    BeamState s = {d->b, d->nb, V, d->max_len, d->eos, d->pad, d->early_stopping, d->score, d->done, d->n_hyp, d->hyp_score, d->hyp_len, d->hyp_row,
+                   d->hist_tok, d->hist_parent, d->hist_score, d->next_tok, d->beam_idx, d->len_norm, cur_len};
+    beam_merge_kernel<<<dim3(d->b), dim3(64), 0, st>>>(s, cand_score, cand_col);
+    return check_launch("beam_merge");
+}
+
+extern "C" int ff_beam_gather(int n_tensors, void* const* tensors, int elem_size, int b, int nb, long long outer, long long len_max, long long inner,
+                              const long long* beam_idx, const long long* n_pos, ff_stream_t stream) {
+    using namespace ff;
+    FF_CHECK(tensors && beam_idx && n_pos, FF_ERR_SHAPE, "ff_beam_gather: null tensor table, beam_idx or n_pos");
+    FF_CHECK(n_tensors > 0 && b > 0 && nb >= 1 && nb <= FF_BEAM_MAX && outer > 0 && len_max > 0 && inner > 0, FF_ERR_SHAPE,
+             "ff_beam_gather: n_tensors %d, b %d, nb %d, outer %lld, len_max %lld, inner %lld", n_tensors, b, nb, outer, len_max, inner);
+    FF_CHECK(elem_size == 2 || elem_size == 4, FF_ERR_UNSUPPORTED, "ff_beam_gather: element size %d (2 or 4 bytes)", elem_size);
+    bool vec = inner * elem_size % 16 == 0;
+    for (int i = 0; i < n_tensors; i++) {
+        FF_CHECK(tensors[i], FF_ERR_SHAPE, "ff_beam_gather: tensor %d is null", i);
+        vec = vec && (uintptr_t)tensors[i] % 16 == 0;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    if (vec) return gather_launches<u32x4>(n_tensors, tensors, b, nb, outer, len_max, inner * elem_size / 16, beam_idx, n_pos, st);
+    if (elem_size == 4) return gather_launches<unsigned>(n_tensors, tensors, b, nb, outer, len_max, inner, beam_idx, n_pos, st);
+    return gather_launches<unsigned short>(n_tensors, tensors, b, nb, outer, len_max, inner, beam_idx, n_pos, st);
+}

@@ -93,6 +93,16 @@ class XattnDesc(C.Structure):
                 ("sync", C.c_void_p)]
 
 
+BEAM_MAX = 8                   # FF_BEAM_MAX
+
+
+class BeamDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("dtype", "b", "nb", "vocab")] + [("ld", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("max_len", "eos", "pad", "early_stopping")] + \
+               [(n, C.c_void_p) for n in ("score", "done", "n_hyp", "hyp_score", "hyp_len", "hyp_row", "hist_tok", "hist_parent", "hist_score",
+                                          "next_tok", "beam_idx", "len_norm")]
+
+
 _P, _SZ, _I = C.c_void_p, C.c_size_t, C.c_int
 _SIGNATURES = {
     # name: (restype, argtypes) — mirrors include/flamingo_fusion.h one to one
@@ -152,6 +162,9 @@ _SIGNATURES = {
     "ff_grad_guard": (_I, [_P, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ff_adamw_step_guarded": (_I, [C.POINTER(AdamWDesc), _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ff_sample_token": (_I, [_I, _I, _I, C.c_longlong, _P, C.c_float, _I, C.c_float, _P, _P, _P]),
+    "ff_beam_workspace_bytes": (_SZ, [_I, _I]),
+    "ff_beam_step": (_I, [C.POINTER(BeamDesc), _P, _P, _P, _SZ, _P]),
+    "ff_beam_gather": (_I, [_I, _P, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P, _P]),
     "ff_xattn_block_bwd_kv": (_I, [C.POINTER(XattnDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _SZ, _P]),
     "ff_kv_project_workspace_bytes": (_SZ, [C.POINTER(KvProjDesc), _I]),
     "ff_kv_project_fwd": (_I, [C.POINTER(KvProjDesc), _P, _P, _P, _P, _SZ, _P]),

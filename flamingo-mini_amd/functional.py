@@ -926,6 +926,110 @@ def sample_tokens(logits: torch.Tensor, u: torch.Tensor, temperature: float = 1.
     return out
 
 
+class BeamState:
+    """The device state block of ff_beam_step for b sequences x nb beams and histories of max_len positions (layout and rules:
+    include/flamingo_fusion.h).  All fields are views of ONE byte buffer, so `to_host()` is one device-to-host copy.  `storage` (uint8,
+    at least BeamState.nbytes(b, nb, max_len) bytes, 16-byte aligned) lets the caller own the memory.  reset() is the initialisation the
+    library expects: score[:, 0] = 0, every other score -inf, nothing done, no hypotheses."""
+
+    @staticmethod
+    def _layout(b: int, nb: int, max_len: int):
+        rows = b * nb
+        fields = [("score", (b, nb), torch.float32), ("done", (b,), torch.int32), ("n_hyp", (b,), torch.int32),
+                  ("hyp_score", (b, nb), torch.float32), ("hyp_len", (b, nb), torch.int32), ("hyp_row", (b, nb), torch.int32),
+                  ("hist_tok", (max_len, rows), torch.int64), ("hist_parent", (max_len, rows), torch.int32),
+                  ("hist_score", (max_len, rows), torch.float32), ("next_tok", (rows,), torch.int64), ("beam_idx", (rows,), torch.int64),
+                  ("len_norm", (max_len + 1,), torch.float32)]
+        out, off = [], 0
+        for name, shape, dt in fields:
+            n = 1
+            for s in shape:
+                n *= s
+            nbytes = n * torch.empty((), dtype=dt).element_size()
+            out.append((name, shape, dt, off, nbytes))
+            off += (nbytes + 15) // 16 * 16
+        return out, off
+
+    @staticmethod
+    def nbytes(b: int, nb: int, max_len: int) -> int:
+        return BeamState._layout(b, nb, max_len)[1]
+
+    def __init__(self, b: int, nb: int, max_len: int, device, eos: Optional[int] = None, pad: int = 0, early_stopping: bool = True,
+                 length_penalty: float = 1.0, storage: Optional[torch.Tensor] = None):
+        if not 1 <= nb <= ffi.BEAM_MAX or b <= 0 or max_len < 1:
+            raise ValueError(f"BeamState: b {b}, nb {nb} (1 .. {ffi.BEAM_MAX}), max_len {max_len}")
+        self.b, self.nb, self.max_len = b, nb, max_len
+        self.eos, self.pad, self.early_stopping, self.length_penalty = eos, pad, bool(early_stopping), float(length_penalty)
+        fields, total = self._layout(b, nb, max_len)
+        if storage is None:
+            storage = _new((total,), torch.uint8, device)
+        ffi.require_cuda(storage)
+        if storage.dtype != torch.uint8 or storage.numel() < total or not storage.is_contiguous() or storage.data_ptr() % 16:
+            raise ValueError(f"BeamState: storage must be {total} contiguous, 16-byte aligned uint8 values")
+        self.storage = storage[:total]
+        for name, shape, dt, off, nbytes in fields:
+            setattr(self, name, self.storage[off:off + nbytes].view(dt).view(shape))
+        self.workspace = _new((max(int(ffi.lib().ff_beam_workspace_bytes(b, nb)), 16),), torch.uint8, storage.device)
+        self.reset()
+
+    def reset(self) -> None:
+        import numpy as np
+        self.storage.zero_()
+        self.score.fill_(float("-inf"))
+        self.score[:, 0] = 0.0
+        self.hyp_score.fill_(float("-inf"))
+        self.next_tok.fill_(self.pad)
+        self.beam_idx.copy_(torch.arange(self.b * self.nb, device=self.storage.device))
+        norm = [0.0] + [float(t) ** self.length_penalty for t in range(1, self.max_len + 1)]           # float32(t ** length_penalty): no pow on the device
+        self.len_norm.copy_(torch.from_numpy(np.asarray(norm, np.float64).astype(np.float32)))
+
+    def to_host(self) -> dict:
+        """Every field as a numpy array, from one device-to-host copy."""
+        host = self.storage.cpu()
+        out = {name: host[off:off + nbytes].view(dt).view(shape).numpy() for name, shape, dt, off, nbytes in self._layout(self.b, self.nb, self.max_len)[0]}
+        out["eos"] = -1 if self.eos is None else int(self.eos)
+        return out
+
+
+def beam_step(logits: torch.Tensor, state: BeamState, cur_len: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One beam-search selection on `logits` (b * nb, V), float32 / bfloat16 with a contiguous last dimension (a row view such as
+    logits3d[:, -1] is read in place): ff_beam_step, two launches, everything stays on the device and nothing is allocated, so the call can be
+    captured.  `cur_len` is a one-element int64 device tensor, the length the sequences have after this step's token.  Returns
+    (state.next_tok, state.beam_idx); the rules are in include/flamingo_fusion.h."""
+    ffi.require_cuda(logits, cur_len)
+    rows = state.b * state.nb
+    if logits.ndim != 2 or logits.shape[0] != rows or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"beam_step: logits must be ({rows}, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
+    if cur_len.dtype != torch.long or cur_len.numel() != 1:
+        raise ValueError(f"beam_step: cur_len must be one int64 value on the device, got {tuple(cur_len.shape)} {cur_len.dtype}")
+    V = logits.shape[1]
+    d = ffi.BeamDesc(ffi.dtype_code(logits.dtype), state.b, state.nb, V, logits.stride(0) if rows > 1 else V, state.max_len,
+                     -1 if state.eos is None else int(state.eos), int(state.pad), int(state.early_stopping),
+                     *(getattr(state, n).data_ptr() for n in ("score", "done", "n_hyp", "hyp_score", "hyp_len", "hyp_row", "hist_tok", "hist_parent",
+                                                              "hist_score", "next_tok", "beam_idx", "len_norm")))
+    ffi.check(ffi.lib().ff_beam_step(d, logits.data_ptr(), cur_len.data_ptr(), state.workspace.data_ptr(), state.workspace.numel(),
+                                     ffi.stream_handle(logits.device)), "ff_beam_step")
+    return state.next_tok, state.beam_idx
+
+
+def beam_gather(tensors: Sequence[torch.Tensor], beam_idx: torch.Tensor, n_pos: torch.Tensor, nb: int) -> None:
+    """t[row, :, p] <- t[beam_idx[row], :, p] IN PLACE for every tensor of `tensors` - all (b * nb, outer, len_max, inner), contiguous, one
+    dtype of 2 or 4 bytes: the keys / values of a StaticCache - and every position p < n_pos (a one-element int64 device tensor); later
+    positions are not touched.  beam_idx (b * nb int64, global rows) maps inside each sequence's nb rows.  ff_beam_gather: one launch per 48
+    tensors, nothing allocated, capturable."""
+    ffi.require_cuda(beam_idx, n_pos, *tensors)
+    if not tensors:
+        raise ValueError("beam_gather: no tensors")
+    t0 = tensors[0]
+    if t0.ndim != 4 or t0.shape[0] % nb or any(t.shape != t0.shape or t.dtype != t0.dtype or not t.is_contiguous() for t in tensors):
+        raise ValueError(f"beam_gather: tensors must all be (b * {nb}, outer, len_max, inner), contiguous and of one dtype, got {[tuple(t.shape) for t in tensors[:2]]}")
+    rows, outer, len_max, inner = t0.shape
+    if beam_idx.dtype != torch.long or beam_idx.numel() != rows or not beam_idx.is_contiguous() or n_pos.dtype != torch.long or n_pos.numel() != 1:
+        raise ValueError(f"beam_gather: beam_idx must be {rows} contiguous int64 values and n_pos one int64 value")
+    ffi.check(ffi.lib().ff_beam_gather(len(tensors), ffi.ptr_array(tensors), t0.element_size(), rows // nb, nb, outer, len_max, inner,
+                                       beam_idx.data_ptr(), n_pos.data_ptr(), ffi.stream_handle(t0.device)), "ff_beam_gather")
+
+
 # ----------------------------------------------------------------------------------------------------
 # primitive wrappers (parity tests / micro-benchmarks): thin, allocation + one C call each
 # ----------------------------------------------------------------------------------------------------

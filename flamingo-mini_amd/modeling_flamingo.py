@@ -309,6 +309,41 @@ import weakref
 _DECODE_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
+def _beam_finalize(state, L0, prompt_ids, nb, pad):
+    """The result of a beam search from the state block of ff_beam_step, on the host (numpy only; `state` = BeamState.to_host(), plus
+    "length" = the sequences' length after the last step, default: the whole history): per sequence the best finished hypothesis - or, when
+    the sequence is not done (the length limit), the best of the hypotheses and the open beams, normalised in float32 by len_norm[length],
+    the earlier entry on equal scores - as in the tail of FlamingoModel._beam_search.  Tokens are read back by following hist_parent
+    downwards from the entry's row; rows are padded with `pad` to the longest.  Returns (b, width) int64 on the CPU."""
+    import numpy as np
+    hist_tok, hist_parent, len_norm = state["hist_tok"], state["hist_parent"], state["len_norm"]
+    length, eos = int(state.get("length", hist_tok.shape[0])), int(state.get("eos", -1))
+    prompt = np.asarray(prompt_ids)
+
+    def backtrack(row, last):               # the tokens at positions L0 .. last of the beam that sat in `row` after the step that wrote `last`
+        toks = []
+        for p in range(last, L0 - 1, -1):
+            toks.append(int(hist_tok[p, row]))
+            row = int(hist_parent[p, row])
+        return toks[::-1]
+
+    out = []
+    for s in range(state["score"].shape[0]):
+        hyps = [(np.float32(state["hyp_score"][s, j]), (int(state["hyp_row"][s, j]), int(state["hyp_len"][s, j]) - 2, [eos]))
+                for j in range(int(state["n_hyp"][s]))]
+        if not state["done"][s]:
+            hyps += [(np.float32(state["score"][s, k]) / np.float32(len_norm[length]), (s * nb + k, length - 1, []))
+                     for k in range(nb) if state["score"][s, k] > -np.inf]
+        best = 0
+        for j in range(1, len(hyps)):
+            if hyps[j][0] > hyps[best][0]:
+                best = j
+        row, last, tail = hyps[best][1]
+        out.append([int(t) for t in prompt[s]] + backtrack(row, last) + tail)
+    width = max(len(o) for o in out)
+    return torch.tensor([o + [pad] * (width - len(o)) for o in out], dtype=torch.long)
+
+
 class _DecodeSession:
     """Fixed-shape greedy decoding for one (batch, max_length) shape: the LM keeps a transformers StaticCache of max_length positions, the
     attention mask and the token buffer are preallocated, positions travel as a device tensor (`cache_position`), the cross-attention K / V
@@ -321,11 +356,18 @@ class _DecodeSession:
     (one launch on the logits in their own dtype, csrc/ff_sample.hip) instead of the argmax.  The random numbers of a whole call are drawn
     before the prompt step, outside any capture, into `u_all` (max_length, b): row `pos` serves the token written at position `pos` and the
     captured step picks it with a device-side index_select on `pos`, so the graph holds no random-number generation and eager and replayed
-    steps consume identical numbers."""
+    steps consume identical numbers.
+    `beams` = (nb, early_stopping, length_penalty) makes it a BEAM-SEARCH session (GPU only) for `b` sequences: every buffer and the LM cache
+    are b * nb rows wide (row s * nb + k = beam k of sequence s; the visual features are encoded once per sequence and repeated), and _append
+    is functional.beam_step (selection and all bookkeeping in a device state block, csrc/ff_beam.hip), functional.beam_gather (the static LM
+    cache reordered in place by beam index, live positions only) and tok <- next_tok.  The cross-attention K / V, the attention mask and
+    text_time are equal within a sequence's beams and are NOT reordered.  The result is read back once, after the loop (_beam_finalize)."""
 
-    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None):
+    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None):
         from transformers.cache_utils import StaticCache
         self._model_ref = weakref.ref(model)
+        self.beams, self.nb, self.n_seq = beams, (beams[0] if beams else 1), b
+        b = b * self.nb
         self.b, self.max_length, self.eos, self.graph_wanted = b, max_length, eos, graph
         self.fill = pad if pad is not None else 0
         self.lm_family = "gpt2" if isinstance(model.flamingo, FlamingoGPT2) else "opt"
@@ -341,6 +383,10 @@ class _DecodeSession:
         if sampling is not None:
             self.u_all = torch.zeros((max_length, b), dtype=torch.float32, device=device)
             self.nxt = torch.zeros((b,), dtype=torch.long, device=device)
+        if beams is not None:
+            self.state = F.BeamState(self.n_seq, self.nb, max_length, device, eos=eos, pad=self.fill, early_stopping=beams[1], length_penalty=beams[2])
+            self.cur_len = torch.zeros((1,), dtype=torch.long, device=device)  # pos + 1: the length after the token beam_step chooses
+            self.lm_tensors = None                                             # keys / values of every StaticCache layer (allocated by the first prompt step)
         self.xattn_past = None                                                 # persistent (k, v) per layer, filled by every prompt step
         self.replay = None
         self.capture_failed = False
@@ -362,6 +408,14 @@ class _DecodeSession:
         return self.param_ptrs != self._param_ptrs()
 
     def _append(self, logits):             # choose, apply the eos bookkeeping of generate(), append at `pos`
+        if self.beams is not None:
+            if self.lm_tensors is None:
+                self.lm_tensors = [t for layer in self.cache.layers for t in (layer.keys, layer.values)]
+            torch.add(self.pos, 1, out=self.cur_len)
+            nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
+            F.beam_gather(self.lm_tensors, beam_idx, self.pos, self.nb)       # positions < pos are live: the cache rows follow their beams
+            self.tok.copy_(nxt[:, None])
+            return
         if self.sampling is None:
             nxt = logits.float().argmax(-1)
         else:
@@ -397,6 +451,14 @@ class _DecodeSession:
     def run(self, ids, ml, am, pixel_values, visual_features, generator=None):
         L0 = ids.shape[1]
         dev = ids.device
+        if self.beams is not None:
+            prompt_ids = ids
+            if visual_features is None and pixel_values is not None:         # encoded once per sequence, repeated per beam
+                visual_features, pixel_values = self.model.flamingo.encode_resample_visuals(pixel_values), None
+            ids, ml, am = _repeat_leading(ids, self.nb), _repeat_leading(ml, self.nb), _repeat_leading(am, self.nb)
+            if visual_features is not None:
+                visual_features = _repeat_leading(visual_features, self.nb)
+            self.state.reset()
         if self.sampling is not None:
             self.u_all.copy_(torch.rand((self.max_length, self.b), generator=generator, device=dev, dtype=torch.float32))
         self.cache.reset()
@@ -435,11 +497,16 @@ class _DecodeSession:
                 self.capture_failed = True
         run_step = self.replay or self._step
         i = 0
+        all_done = self.finished if self.beams is None else self.state.done
         while i < remaining:
             run_step()
             i += 1
-            if self.eos is not None and i % 16 == 0 and bool(self.finished.all()):     # (a host sync: only every 16 tokens)
+            if self.eos is not None and i % 16 == 0 and bool(all_done.all()):          # (a host sync: only every 16 tokens)
                 break
+        if self.beams is not None:                                            # one device-to-host copy; steps past the last `done` only wrote padding
+            host = self.state.to_host()
+            host["length"] = self.max_length - remaining + i
+            return _beam_finalize(host, L0, prompt_ids.cpu(), self.nb, self.fill).to(dev)
         if self.eos is not None:
             return self.ids_buf[:, :L0 + int(self.n_new)].clone()
         return self.ids_buf.clone()
@@ -577,8 +644,8 @@ class FlamingoModel(PreTrainedModel):
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
         implemented here: greedy, multinomial sampling (do_sample, temperature, top_k, top_p) and beam search (num_beams, length_penalty,
         early_stopping).  Unknown generation arguments raise instead of being ignored.
-        Sampling takes the fixed-shape, graph-replayed path of greedy decoding (_DecodeSession) only when `static_decode=True` is passed
-        explicitly (GPU tensors, a GPT-2- or OPT-backed model, a prompt shorter than max_length - 1); otherwise it runs the dynamic loop
+        Sampling and beam search (num_beams <= 8) take the fixed-shape, graph-replayed path of greedy decoding (_DecodeSession) only when
+        `static_decode=True` is passed explicitly (GPU tensors, a GPT-2- or OPT-backed model, a prompt shorter than max_length - 1); otherwise it runs the dynamic loop
         below, as it always has.  The two paths draw DIFFERENT token streams from the same seed: the static path draws by inverse CDF in
         vocabulary order from one uniform number per token (functional.sample_tokens), the dynamic loop with torch.multinomial.  Both are
         reproducible per seed (`generator`)."""
@@ -594,6 +661,11 @@ class FlamingoModel(PreTrainedModel):
         if num_beams > 1:
             if do_sample:
                 raise ValueError("beam search with sampling is not implemented")
+            if static_decode:                                                 # explicit static_decode=True: the beam kernels have no CPU form
+                F.ffi.require_cuda(ids)
+                if isinstance(self.flamingo, (FlamingoGPT2, FlamingoOPT)) and ids.shape[1] + 1 < max_length and num_beams <= F.ffi.BEAM_MAX:
+                    return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
+                                               beams=(int(num_beams), bool(early_stopping), float(length_penalty)))
             return self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty)
         if do_sample and static_decode:                                       # explicit static_decode=True: the sampling kernel has no CPU form
             F.ffi.require_cuda(ids)
@@ -625,9 +697,9 @@ class FlamingoModel(PreTrainedModel):
         return ids
 
     def _static_greedy(self, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, graph: Optional[bool] = None,
-                       sampling=None, generator=None):
+                       sampling=None, generator=None, beams=None):
         """Greedy (or, with `sampling` = (temperature, top_k, top_p), sampled) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches and buffers plus, on the GPU, the captured
-        HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, eos / pad, sampling settings) and reused by later calls, so only the
+        HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, eos / pad, sampling settings, beam settings (nb, early_stopping, length_penalty)) and reused by later calls, so only the
         first caption batch of a shape pays for the capture.  a session whose model's parameters were re-allocated since (model.to(), ShardedAdamW) is rebuilt; reset_decode_sessions() drops them all."""
         b = ids.shape[0]
         if graph is None:
@@ -635,7 +707,7 @@ class FlamingoModel(PreTrainedModel):
         sessions = _DECODE_SESSIONS.setdefault(self, {})
         n_media = int(ml.sum(-1).max()) if visual_features is None and pixel_values is None else \
             (visual_features.shape[1] if visual_features is not None else (pixel_values.shape[1] if pixel_values.ndim >= 5 else pixel_values.shape[0]))
-        key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling)
+        key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams)
         sess = sessions.get(key)
         if sess is not None and sess.stale():
             sessions.pop(key)
@@ -643,7 +715,7 @@ class FlamingoModel(PreTrainedModel):
         if sess is None:
             if len(sessions) >= 4:                                            # a handful of shapes at most: each holds a KV cache and a graph
                 sessions.pop(next(iter(sessions)))
-            sess = sessions[key] = _DecodeSession(self, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling)
+            sess = sessions[key] = _DecodeSession(self, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling, beams)
         if sampling is None:
             return sess.run(ids, ml, am, pixel_values, visual_features)
         return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator)

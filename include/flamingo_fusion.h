@@ -49,7 +49,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * 5: gradient clipping: ff_grad_sumsq*, ff_grad_clip_coef, ff_scale_grads, ff_adamw_step_clipped;
                                 * 6: fp32 gradient accumulation: ff_grad_accumulate, ff_adamw_step_acc;
                                 * still 6, additions only: the non-finite gradient guard ff_grad_guard, ff_adamw_step_guarded;
-                                * still 6, addition only: token selection for sampled decoding, ff_sample_token) */
+                                * still 6, addition only: token selection for sampled decoding, ff_sample_token;
+                                * still 6, additions only: beam search on the captured decode step, ff_beam_step, ff_beam_gather) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -485,6 +486,68 @@ int ff_shifted_ce_bwd(int dtype, int batch, int seq, int vocab, const void* logi
  * ------------------------------------------------------------------------------------------------------ */
 int ff_sample_token(int dtype, int rows, int vocab, long long ld, const void* logits, float temperature, int top_k, float top_p,
                     const float* u, long long* token, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Beam search on the captured decode step (added under ABI 6): ff_beam_step selects and keeps ALL bookkeeping on the device (no host
+ * synchronisation, no allocation), ff_beam_gather reorders the static LM cache in place.  Both are capturable.
+ * logits: rows = b * nb rows of `vocab` elements of `dtype`, row r at element r * ld, ld >= vocab, element alignment only; row s * nb + k
+ * is beam k of sequence s.  cur_len: a device int64, the length the sequences have AFTER this step's token (1 <= *cur_len <= max_len).
+ * The state block belongs to the caller, who initialises it once (score[s][0] = 0, every other score -inf, done / n_hyp 0) and fills
+ * len_norm[t] = float32(t ** length_penalty), t = 0 .. max_len; after that only the library writes it:
+ *   score[b][nb] fp32 (-inf = a dead beam), done[b], n_hyp[b] int32, finished hypotheses hyp_score / hyp_len / hyp_row [b][nb] (sorted by
+ *   score, best first), histories hist_tok int64 / hist_parent int32 / hist_score fp32 [max_len][b * nb], and the step's results
+ *   next_tok[b * nb] int64 and beam_idx[b * nb] int64 (GLOBAL row indices: the argument of ff_beam_gather).
+ * Rules (FlamingoModel._beam_search, step for step), per sequence s:
+ *   1. per row  lse = max + log(sum exp(x - max))  in fp32, in a fixed summation order;
+ *   2. logp_v = x_v - lse;
+ *   3. candidate (k, v) scores  score[s][k] + logp_v,  each operation rounded once in fp32;
+ *   4. the 2 nb best candidates are taken, ordered by score descending, then by flat index k * vocab + v ascending (ties are decided);
+ *   5. a -inf candidate is taken only if fewer finite ones exist;
+ *   6. the ranks are walked in order until nb beams are filled: an eos candidate at rank < nb becomes a finished hypothesis
+ *      (score / len_norm[*cur_len] in fp32, *cur_len, parent row), at rank >= nb it is dropped; the first nb other candidates become the next
+ *      beams (missing ones: -inf, pad, the identity parent); hypotheses are kept sorted, equal scores in arrival order, the best nb stay; with
+ *      nb of them, done[s] is set if early_stopping, or if the worst kept one >= (best next score) / len_norm[*cur_len].  A sequence that was
+ *      done before the call gets -inf, pad and the identity parent and keeps its hypotheses;
+ *   7. token, parent row and score of every row go into the history tables at index *cur_len - 1 (a hypothesis or an open beam is read
+ *      back by following hist_parent downwards from its row);
+ *   8. a row holding NaN or +inf gives unspecified candidates, but every index written stays in range;
+ *   9. fixed order throughout: equal inputs give equal bits, eager or replayed.
+ * eos = -1: none.  workspace: ff_beam_workspace_bytes(b, nb) bytes (0 for arguments ff_beam_step rejects).
+ * FF_ERR_SHAPE: a null pointer, b <= 0, nb outside [1, FF_BEAM_MAX], vocab < 2 nb, ld < vocab, max_len < 1, a workspace that is too small.
+ * FF_ERR_UNSUPPORTED: other dtypes.
+ *
+ * ff_beam_gather: t[row, o, p, :] <- t[beam_idx[row], o, p, :] for every tensor of the table (host array of n_tensors device pointers, each
+ * (b * nb, outer, len_max, inner) contiguous, elements of elem_size 2 or 4 bytes) and every position p < *n_pos (a device int64, clamped to
+ * [0, len_max]); positions >= *n_pos are neither read nor written.  beam_idx[row] must lie in the nb rows of row's sequence (otherwise the
+ * row stays) and may repeat a row.  In place: one thread moves one 16-byte vector (or element, when inner * elem_size or a pointer is not a
+ * multiple of 16) of all nb rows of a sequence, loads before stores.  FF_ERR_SHAPE: null pointers, non-positive sizes, nb outside
+ * [1, FF_BEAM_MAX]; FF_ERR_UNSUPPORTED: another element size.
+ * (ff_beam_desc is declared struct-then-typedef; tests/test_beam_args.py checks its ctypes mirror against this header.)
+ * ------------------------------------------------------------------------------------------------------ */
+#define FF_BEAM_MAX 8
+struct ff_beam_desc {
+    int dtype, b, nb, vocab;
+    long long ld;
+    int max_len, eos, pad, early_stopping;
+    float* score;
+    int* done;
+    int* n_hyp;
+    float* hyp_score;
+    int* hyp_len;
+    int* hyp_row;
+    long long* hist_tok;
+    int* hist_parent;
+    float* hist_score;
+    long long* next_tok;
+    long long* beam_idx;
+    const float* len_norm;
+};
+typedef struct ff_beam_desc ff_beam_desc;
+size_t ff_beam_workspace_bytes(int b, int nb);
+int ff_beam_step(const ff_beam_desc* d, const void* logits, const long long* cur_len, void* workspace, size_t workspace_bytes,
+                 ff_stream_t stream);
+int ff_beam_gather(int n_tensors, void* const* tensors, int elem_size, int b, int nb, long long outer, long long len_max, long long inner,
+                   const long long* beam_idx, const long long* n_pos, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * QuickGELU of the CLIP vision tower, y = x * sigmoid(1.702 x) (transformers.activations.QuickGELUActivation, selected by
