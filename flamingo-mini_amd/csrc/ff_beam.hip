@@ -1,9 +1,9 @@
 // Beam search on the captured decode step: the selection with all of its bookkeeping (ff_beam_step) and the in-place reorder of the static
 // LM cache by beam index (ff_beam_gather).  The rules are in include/flamingo_fusion.h; they restate FlamingoModel._beam_search.
 // ff_beam_step is two launches:
-//   beam_rows_kernel   one 256-thread workgroup per row (= one beam of one sequence), built like sample_token_kernel: a bf16 row of up to
-//                      65536 columns is staged once in LDS as order-preserving 16-bit keys; lse = max + log(sum exp(x - max)); the 2 nb-th
-//                      largest value of the row is found by bisection on the key; then the row's best 2 nb candidates under the rule's order
+//   beam_rows_kernel   one 256-thread workgroup per row (= one beam of one sequence) on the row machinery of ff_row_keys.h, which it shares
+//                      with sample_token_kernel (keys, the staged key image, the passes and their contracts): lse = max + log(sum exp(x - max));
+//                      the 2 nb-th largest value of the row by bisection on the key; then the row's best 2 nb candidates under the rule's order
 //                      (score descending, column ascending) are collected: everything whose score  f(x) = (x - lse) + score[row]  is above
 //                      f(that value), then the lowest columns with a score equal to it.  f is monotone in x, so this is the row's top 2 nb
 //                      by SCORE even where two different logits round to one score.  A sequence's top 2 nb over nb V candidates lies in the
@@ -13,74 +13,12 @@
 // Every sum has a fixed order (thread-local in column order, xor butterfly in the wave, wave 0..3): equal inputs give equal bits.
 #include <cmath>
 
-#include "ff_common.h"
-#include "ff_internal.h"
+#include "ff_row_keys.h"
 
 namespace ff {
 
 constexpr int kBeamScratch = 2304;            // n_gt[256] ints | n_eq[256] ints | red[16] words | cand score[16] | cand column[16]: the key image starts behind them
-constexpr int kBeamStageMax = 65536;          // columns of a staged row (128 KiB of keys)
 constexpr int kBeamCand = 2 * FF_BEAM_MAX;    // candidates a row contributes at most
-
-// order-preserving key of a float: a > b  <=>  key(a) > key(b) for all non-NaN values (-0 is +0).  A bf16 value's key is the top 16 bits.
-template <int BITS> FF_DEV unsigned beam_key(float v) {
-    unsigned b = __float_as_uint(v);
-    if (b == 0x80000000u) b = 0;
-    return ((b >> 31) ? ~b : (b | 0x80000000u)) >> (32 - BITS);
-}
-template <int BITS> FF_DEV float beam_value(unsigned k) {
-    const unsigned k32 = k << (32 - BITS);
-    return __uint_as_float((k32 >> 31) ? (k32 & 0x7FFFFFFFu) : (~k32 & (0xFFFFFFFFu << (32 - BITS))));
-}
-
-// f(column, value) over a row whose start is only element-aligned: scalar head up to the next 16-byte boundary, 16-byte vectors with four
-// requests in flight (one workgroup has its CU to itself), scalar tail.  A thread sees its columns in the order of the plain loop.
-template <typename T, typename F>
-FF_DEV void beam_row_vectors4(const T* row, int V, F&& f) {
-    constexpr int N = Vec<T>::N;
-    int head = (int)(((16u - (unsigned)((unsigned long long)row & 15u)) & 15u) / sizeof(T));
-    head = head < V ? head : V;
-    const int nvec = (V - head) / N, tail0 = head + nvec * N;
-    if ((int)threadIdx.x < head) f((int)threadIdx.x, to_f32(row[threadIdx.x]));
-    for (int v = threadIdx.x; v < nvec; v += 1024) {
-        typename Vec<T>::raw q[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int vj = v + 256 * j;
-            q[j] = *(const typename Vec<T>::raw*)(row + head + (vj < nvec ? vj : v) * N);       // (out of range: the first vector again, unused)
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int vj = v + 256 * j;
-            if (vj < nvec) {
-#pragma unroll
-                for (int e = 0; e < N; e++) f(head + vj * N + e, (float)q[j][e]);
-            }
-        }
-    }
-    for (int c = tail0 + threadIdx.x; c < V; c += 256) f(c, to_f32(row[c]));
-}
-
-FF_DEV int beam_block_sum_int(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-FF_DEV unsigned beam_block_max_uint(unsigned v, unsigned* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
-        v = v > w ? v : w;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const unsigned a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
-    return a > b ? a : b;
-}
 
 // cand_score / cand_col: [rows][K], this row's best K candidates in no particular order (the merge ranks them)
 template <typename T, bool STAGED>
@@ -94,94 +32,30 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(int V, long long ld, con
     float* red = (float*)(smem_raw + 2048);
     float* cs = (float*)(smem_raw + 2112);
     int* cc = (int*)(smem_raw + 2176);
-    unsigned short* sk = (unsigned short*)(smem_raw + kBeamScratch);              // STAGED: keys of columns [0, 8 ceil(V / 8)), the padding 0
     const int tid = threadIdx.x;
-    const T* row = logits + (long long)blockIdx.x * ld;
+    const RowKeys<T, STAGED> keys(logits + (long long)blockIdx.x * ld, V, (unsigned short*)(smem_raw + kBeamScratch));
 
-    // f(key) for every column in a fixed thread / order assignment; STAGED also visits the padding keys (0: see the callers)
-    // (every lambda here is forced inline: behind a call its captured counters would live in scratch memory)
-    auto each = [&](auto&& f) __attribute__((always_inline)) {
-        if constexpr (STAGED) {
-            const int nvec = (V + 7) >> 3;
-            for (int v = tid; v < nvec; v += 1024) {
-                uint4 q[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) q[j] = v + 256 * j < nvec ? *(const uint4*)(sk + (v + 256 * j) * 8) : uint4{0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const unsigned w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-#pragma unroll
-                    for (int e = 0; e < 4; e++) { f(w[e] & 0xFFFFu); f(w[e] >> 16); }
-                }
-            }
-        } else {
-            beam_row_vectors4(row, V, [&](int, float x) __attribute__((always_inline)) { f(beam_key<BITS>(x)); });
-        }
-    };
-    // thread t's own columns [t C, (t + 1) C) in column order, C a multiple of 8: f(column, key), column < V
-    const int C = ((((V + 255) >> 8) + 7) >> 3) << 3;
-    const int c0 = tid * C < V ? tid * C : V, c1 = c0 + C < V ? c0 + C : V;
-    auto own = [&](auto&& f) __attribute__((always_inline)) {
-        if constexpr (STAGED) {
-            for (int c = c0; c < c1; c += 32) {
-                uint4 q[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) q[j] = c + 8 * j < c1 ? *(const uint4*)(sk + c + 8 * j) : uint4{0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const unsigned w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        if (c + 8 * j + 2 * e < c1) f(c + 8 * j + 2 * e, w[e] & 0xFFFFu);
-                        if (c + 8 * j + 2 * e + 1 < c1) f(c + 8 * j + 2 * e + 1, w[e] >> 16);
-                    }
-                }
-            }
-        } else {
-            for (int c = c0; c < c1; c++) f(c, beam_key<BITS>(to_f32(row[c])));
-        }
-    };
-
-    unsigned kmax = 0;
-    if constexpr (STAGED) {
-        beam_row_vectors4(row, V, [&](int c, float x) __attribute__((always_inline)) {
-            const unsigned k = beam_key<BITS>(x);
-            sk[c] = (unsigned short)k;
-            kmax = k > kmax ? k : kmax;
-        });
-        for (int c = V + tid; c < ((V + 7) & ~7); c += 256) sk[c] = 0;
-    } else {
-        each([&](unsigned k) __attribute__((always_inline)) { kmax = k > kmax ? k : kmax; });
-    }
     if (tid < kBeamCand) { cs[tid] = -INFINITY; cc[tid] = tid < V ? tid : 0; }     // what a row of NaN / +inf leaves behind: in range
-    kmax = beam_block_max_uint(kmax, (unsigned*)red);                              // (its barriers also publish the key image)
-    const float xmax = beam_value<BITS>(kmax);
+    const float xmax = ordered_value<BITS>(keys.stage((unsigned*)red));
 
     // rule 1: lse = max + log(sum exp(x - max)); a padding key (0 = a NaN of the lowest order) is skipped, it is no column
     float s = 0.f;
-    if constexpr (STAGED) each([&](unsigned k) __attribute__((always_inline)) { if (k) s += expf(beam_value<BITS>(k) - xmax); });
-    else each([&](unsigned k) __attribute__((always_inline)) { s += expf(beam_value<BITS>(k) - xmax); });
+    if constexpr (STAGED) keys.each([&](unsigned k) __attribute__((always_inline)) { if (k) s += expf(ordered_value<BITS>(k) - xmax); });
+    else keys.each([&](unsigned k) __attribute__((always_inline)) { s += expf(ordered_value<BITS>(k) - xmax); });
     s = block_sum<4>(s, red);
     const float lse = xmax + logf(s);
     const float sc = score[blockIdx.x];
-    auto f = [lse, sc](unsigned k) __attribute__((always_inline)) { return (beam_value<BITS>(k) - lse) + sc; };         // rules 2 and 3: two roundings
-
-    // the K-th largest key = the largest t with count(key >= t) >= K (V >= K: t = 0 qualifies; padding keys never count, t >= 1)
-    unsigned tk = 0;
-    for (int bit = BITS - 1; bit >= 0; bit--) {
-        const unsigned cand = tk | (1u << bit);
-        int n = 0;
-        each([&](unsigned k) __attribute__((always_inline)) { n += k >= cand ? 1 : 0; });
-        if (beam_block_sum_int(n, (int*)red) >= K) tk = cand;
-    }
-    const float fk = f(tk);
+    auto f = [lse, sc](unsigned k) __attribute__((always_inline)) { return (ordered_value<BITS>(k) - lse) + sc; };      // rules 2 and 3: two roundings
+    const float fk = f(keys.kth_largest(K, (int*)red));                            // V >= K: the K-th largest value exists
 
     // rule 4 inside the row: scores above fk (fewer than K: they belong to logits above the K-th largest), then the lowest columns at fk
+    // (own()'s padding calls have key 0: f of it is a NaN, neither above nor equal to fk, and they touch nothing)
     int gt = 0, eq = 0;
-    own([&](int, unsigned k) __attribute__((always_inline)) {
+    keys.own([&](int, unsigned k) __attribute__((always_inline)) {
         const float v = f(k);
         gt += v > fk ? 1 : 0;
         eq += v == fk ? 1 : 0;
+        return false;
     });
     n_gt[tid] = gt;
     n_eq[tid] = eq;
@@ -193,13 +67,14 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(int V, long long ld, con
         gt_all += g;
     }
     int ig = gt_before, ie = gt_all + eq_before;
-    own([&](int c, unsigned k) __attribute__((always_inline)) {
+    keys.own([&](int c, unsigned k) __attribute__((always_inline)) {
         const float v = f(k);
         const bool g = v > fk, e = v == fk;
         const int slot = g ? ig : ie;
         if ((g || e) && slot < K) { cs[slot] = v; cc[slot] = c; }
         ig += g ? 1 : 0;
         ie += e ? 1 : 0;
+        return false;
     });
     __syncthreads();
     if (tid < K) {
@@ -226,7 +101,7 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(BeamState st, const floa
     const int s = blockIdx.x, nb = st.nb, K = 2 * nb, n = nb * K, tid = threadIdx.x;
     const long long r0 = (long long)s * nb;
     for (int j = tid; j < n; j += 64) {
-        key[j] = beam_key<32>(cand_score[r0 * K + j]);
+        key[j] = ordered_key<32>(cand_score[r0 * K + j]);
         int c = cand_col[r0 * K + j];
         col[j] = c < 0 ? 0 : (c >= st.vocab ? st.vocab - 1 : c);
     }
@@ -241,7 +116,7 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(BeamState st, const floa
             const bool better = kj > ki || (kj == ki && (bj < bi || (bj == bi && (cj < ci || (cj == ci && j < i)))));
             rank += better ? 1 : 0;
         }
-        if (rank < K) { top_s[rank] = beam_value<32>(ki); top_beam[rank] = bi; top_col[rank] = ci; }
+        if (rank < K) { top_s[rank] = ordered_value<32>(ki); top_beam[rank] = bi; top_col[rank] = ci; }
     }
     __syncthreads();
     if (tid != 0) return;
@@ -296,19 +171,8 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(BeamState st, const floa
 
 template <typename T, bool STAGED>
 static int beam_rows_launch(int rows, int V, long long ld, const void* logits, int K, const float* score, float* cand_score, int* cand_col, hipStream_t st) {
-    const size_t lds = kBeamScratch + (STAGED ? (size_t)((V + 7) / 8) * 16 : 0);
-    if (STAGED) {                                                                  // beyond 64 KiB of dynamic LDS a kernel has to ask once per device
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)beam_rows_kernel<T, STAGED>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               kBeamScratch + kBeamStageMax * 2);
-            FF_CHECK(e == hipSuccess, FF_ERR_LAUNCH, "hipFuncSetAttribute(beam_rows lds): %s", hipGetErrorString(e));
-            if (dev >= 0 && dev < 64) attr_done[dev] = true;
-        }
-    }
-    beam_rows_kernel<T, STAGED><<<dim3(rows), dim3(256), lds, st>>>(V, ld, (const T*)logits, K, score, cand_score, cand_col);
+    if (STAGED) FF_TRY((allow_dynamic_lds<beam_rows_kernel<T, STAGED>>(kBeamScratch + kRowStageMax * 2, "beam_rows")));
+    beam_rows_kernel<T, STAGED><<<dim3(rows), dim3(256), row_keys_lds<STAGED>(kBeamScratch, V), st>>>(V, ld, (const T*)logits, K, score, cand_score, cand_col);
     return check_launch("beam_rows");
 }
 
@@ -393,12 +257,9 @@ extern "C" int ff_beam_step(const ff_beam_desc* d, const void* logits, const lon
     const int rows = d->b * d->nb, K = 2 * d->nb, V = d->vocab;
     float* cand_score = (float*)workspace;
     int* cand_col = (int*)(cand_score + (size_t)rows * K);
-    if (d->dtype == FF_DTYPE_BF16) {
-        if (V <= kBeamStageMax) FF_TRY((beam_rows_launch<bf16, true>(rows, V, d->ld, logits, K, d->score, cand_score, cand_col, st)));
-        else FF_TRY((beam_rows_launch<bf16, false>(rows, V, d->ld, logits, K, d->score, cand_score, cand_col, st)));
-    } else {
-        FF_TRY((beam_rows_launch<float, false>(rows, V, d->ld, logits, K, d->score, cand_score, cand_col, st)));
-    }
+    FF_TRY(row_keys_dispatch(d->dtype, V, [&](auto t, auto staged) {
+        return beam_rows_launch<decltype(t), decltype(staged)::value>(rows, V, d->ld, logits, K, d->score, cand_score, cand_col, st);
+    }));
     BeamState s = {d->b, d->nb, V, d->max_len, d->eos, d->pad, d->early_stopping, d->score, d->done, d->n_hyp, d->hyp_score, d->hyp_len, d->hyp_row,
                    d->hist_tok, d->hist_parent, d->hist_score, d->next_tok, d->beam_idx, d->len_norm, cur_len};
     beam_merge_kernel<<<dim3(d->b), dim3(64), 0, st>>>(s, cand_score, cand_col);

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.skipif(not ROWS, reason="library not built in this tree
 
 def test_every_translation_unit_reported():
     units = {r["unit"] for r in ROWS}
-    assert {"ff_gemm", "ff_attention", "ff_xattn_fused", "ff_rowwise", "ff_optim", "ff_decode", "ff_loss", "ff_elementwise"} <= units, units
+    assert {"ff_gemm", "ff_attention", "ff_xattn_fused", "ff_rowwise", "ff_optim", "ff_decode", "ff_loss", "ff_elementwise", "ff_sample", "ff_beam"} <= units, units
 
 
 def test_producer_consumer_gemm_instantiations_keep_their_planned_co_residency():
@@ -67,3 +67,16 @@ def test_optimizer_kernels_keep_their_occupancy_without_scratch():
                 assert r["occupancy"] >= floor, (r["name"], r["vgprs"], r["occupancy"], floor)
                 seen[family] += 1
     assert all(seen.values()), seen
+
+
+def test_selection_kernels_keep_their_functors_out_of_scratch():
+    """sample_token_kernel and beam_rows_kernel hand functors to the row walks of csrc/ff_row_keys.h.  A functor that is not inlined puts its
+    captured counters in scratch memory, in a kernel that runs 16 to 32 passes over the row: every instantiation (bf16 staged, bf16
+    unstaged, fp32 - three of each kernel) uses none."""
+    seen = {"sample_token_kernel": 0, "beam_rows_kernel": 0}
+    for r in ROWS:
+        for family in seen:
+            if family in r["mangled"]:
+                assert r["scratch"] == 0, (r["name"], r["scratch"])
+                seen[family] += 1
+    assert seen == {"sample_token_kernel": 3, "beam_rows_kernel": 3}, seen
