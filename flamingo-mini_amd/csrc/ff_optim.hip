@@ -8,6 +8,7 @@
 #include <type_traits>
 #include "ff_common.h"
 #include "ff_internal.h"
+#include "ff_sr.h"
 
 namespace ff {
 
@@ -89,6 +90,9 @@ struct AdamTable {
     const float* lr_dev;     // ... and so does the learning rate, when a scheduler is to stay effective under replay
     const float* grad_coef;  // CLIP kernels: device scalar multiplying every (grad_scale'd) gradient - the max-norm clip coefficient
     const float* skip;       // GUARD kernels: device scalar, != 0 = the step is not taken (ff_grad_guard found a non-finite gradient)
+    unsigned long long seed;              // SR kernels: the Philox key, ...
+    unsigned stream_id[kAdamTensors];     // ... each tensor's stream (< 2^30: the two low counter bits name the stored array) ...
+    unsigned step;                        // ... and the number of the step being taken where it is not read from *step_dev
 };
 
 // T: storage type of the parameters' compute copy and of the gradients; ST: storage type of the two moments; MASTER: the update
@@ -101,9 +105,14 @@ struct AdamTable {
 // GT: storage type of the gradients - T, or float where the gradients are the fp32 accumulators of ff_grad_accumulate (ff_adamw_step_acc).
 // GUARD (implies CLIP; ff_adamw_step_guarded): every workgroup reads *t.skip first and returns before it touches a tensor when it is set -
 // a skipped launch is a no-op (no weight decay, no moment decay, no master write).  The read and the branch are wave-uniform.
-template <typename T, typename ST, bool MASTER, bool CLIP = false, typename GT = T, bool GUARD = false>
+// SR (ff_adamw_step_sr; bf16 parameters without master copies): every bf16 store - the parameter, and the moments where ST is bf16 - is
+// rounded stochastically (ff_sr.h) instead of to nearest, with the bits of (seed, stream id, step, slot, element index); the arithmetic
+// before the store is the same.  fp32 moments are stored as they are.
+template <typename T, typename ST, bool MASTER, bool CLIP = false, typename GT = T, bool GUARD = false, bool SR = false>
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
     static_assert(!GUARD || CLIP, "GUARD implies CLIP");
+    static_assert(!SR || (std::is_same_v<T, bf16> && !MASTER), "SR rounds bf16 parameters that have no master copy");
+    constexpr bool SR_MOMENTS = SR && std::is_same_v<ST, bf16>;
     constexpr int VEC = Vec<T>::N;
     constexpr bool NT = !std::is_same_v<T, float>;
     if constexpr (GUARD) {
@@ -128,6 +137,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
         bc2_sqrt = sqrtf(1.f - powf(t.beta2, step));
     }
     const float lr = t.lr_dev ? *t.lr_dev : t.lr;
+    unsigned sr_step = 0, sr_stream = 0;
+    if constexpr (SR) {
+        sr_step = t.step_dev ? (unsigned)*t.step_dev : t.step;
+        sr_stream = t.stream_id[ti] << 2;
+    }
     // CLIP folds the coefficient into the one factor every gradient is multiplied by (the unclipped instantiations compile as before).  With
     // a coefficient of 1 the parameters and the fp32 kernel's moments are the unclipped ones bit for bit; the bf16-parameter kernels contract
     // the moments' multiply-adds differently, so those may differ in the last bit
@@ -177,6 +191,20 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
         constexpr std::true_type S{};
         constexpr std::false_type K{};
         auto store = [&](long long i, const float (&pf)[VEC], const float (&mf)[VEC], const float (&vf)[VEC]) {
+            if constexpr (SR) {                                        // (i is a multiple of 8: one vector of the counter layout)
+                unsigned r[4];
+                sr_words(t.seed, i >> 3, sr_step, sr_stream, r);
+                sr_store8<false>(p + i, pf, r);
+                if constexpr (SR_MOMENTS) {
+                    sr_words(t.seed, i >> 3, sr_step, sr_stream | 1, r);
+                    sr_store8<true>(m + i, mf, r);
+                    sr_words(t.seed, i >> 3, sr_step, sr_stream | 2, r);
+                    sr_store8<true>(v + i, vf, r);
+                } else {
+                    stv(m, i, mf, S); stv(v, i, vf, S);
+                }
+                return;
+            }
             stv(p, i, pf, K); stv(m, i, mf, S); stv(v, i, vf, S);      // the updated parameters are what the next forward reads: kept cacheable
             if (MASTER) stv(w, i, pf, S);
         };
@@ -213,6 +241,25 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
             mf[e] = ok ? to_f32(m[i + e]) : 0.f; vf[e] = ok ? to_f32(v[i + e]) : 0.f;
         }
         update(pf, gf, mf, vf);
+        if constexpr (SR) {                                            // (i is a multiple of 8 here too: the same words as on the vector path)
+            unsigned rp[4], rm[4], rv[4];
+            sr_words(t.seed, i >> 3, sr_step, sr_stream, rp);
+            if constexpr (SR_MOMENTS) {
+                sr_words(t.seed, i >> 3, sr_step, sr_stream | 1, rm);
+                sr_words(t.seed, i >> 3, sr_step, sr_stream | 2, rv);
+            }
+#pragma unroll
+            for (int e = 0; e < VEC; e++)
+                if (i + e < n) {
+                    p[i + e] = sr_bf16_value(pf[e], sr_r16(rp, e));
+                    if constexpr (SR_MOMENTS) {
+                        m[i + e] = sr_bf16_value(mf[e], sr_r16(rm, e)); v[i + e] = sr_bf16_value(vf[e], sr_r16(rv, e));
+                    } else {
+                        m[i + e] = from_f32<ST>(mf[e]); v[i + e] = from_f32<ST>(vf[e]);
+                    }
+                }
+            continue;
+        }
 #pragma unroll
         for (int e = 0; e < VEC; e++)
             if (i + e < n) {
@@ -223,34 +270,41 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t) {
 }
 
 // The one place a storage mode and a variant become an instantiation: (4 storage modes with gradients in the parameter's type + the 3
-// bf16-parameter ones with fp32 gradients) x 3 variants = 21 kernels.
+// bf16-parameter ones with fp32 gradients) x 3 variants = 21 kernels; sr (bf16 parameters without master copies: 2 moment storages x 2
+// gradient types) x 3 variants = 12 more.
 enum AdamVariant { kAdamPlain, kAdamClip, kAdamGuard };
-static void adamw_dispatch(int dtype, bool master, int state_dtype, bool grads32, AdamVariant variant, dim3 grid, hipStream_t stream,
+static void adamw_dispatch(int dtype, bool master, int state_dtype, bool grads32, AdamVariant variant, bool sr, dim3 grid, hipStream_t stream,
                            const AdamTable& t) {
-    auto run = [&](auto p, auto s, auto has_master, auto g) {      // the three variants of one (parameter, moment, master, gradient) storage
+    auto run = [&](auto p, auto s, auto has_master, auto g, auto rounding) {      // the three variants of one (parameter, moment, master, gradient) storage
         typedef decltype(p) T;
         typedef decltype(s) ST;
         typedef decltype(g) GT;
-        constexpr bool MASTER = decltype(has_master)::value;
-        if (variant == kAdamGuard) adamw_kernel<T, ST, MASTER, true, GT, true><<<grid, 256, 0, stream>>>(t);
-        else if (variant == kAdamClip) adamw_kernel<T, ST, MASTER, true, GT, false><<<grid, 256, 0, stream>>>(t);
-        else adamw_kernel<T, ST, MASTER, false, GT, false><<<grid, 256, 0, stream>>>(t);
+        constexpr bool MASTER = decltype(has_master)::value, SR = decltype(rounding)::value;
+        if (variant == kAdamGuard) adamw_kernel<T, ST, MASTER, true, GT, true, SR><<<grid, 256, 0, stream>>>(t);
+        else if (variant == kAdamClip) adamw_kernel<T, ST, MASTER, true, GT, false, SR><<<grid, 256, 0, stream>>>(t);
+        else adamw_kernel<T, ST, MASTER, false, GT, false, SR><<<grid, 256, 0, stream>>>(t);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
     const float f{};                                              // (values that only carry their types into `run`)
     const bf16 h{};
-    if (dtype == FF_DTYPE_F32) run(f, f, no, f);
-    else if (master) grads32 ? run(h, f, yes, f) : run(h, f, yes, h);
-    else if (state_dtype == FF_DTYPE_F32) grads32 ? run(h, f, no, f) : run(h, f, no, h);
-    else grads32 ? run(h, h, no, f) : run(h, h, no, h);
+    if (sr) {
+        if (state_dtype == FF_DTYPE_F32) grads32 ? run(h, f, no, f, yes) : run(h, f, no, h, yes);
+        else grads32 ? run(h, h, no, f, yes) : run(h, h, no, h, yes);
+        return;
+    }
+    if (dtype == FF_DTYPE_F32) run(f, f, no, f, no);
+    else if (master) grads32 ? run(h, f, yes, f, no) : run(h, f, yes, h, no);
+    else if (state_dtype == FF_DTYPE_F32) grads32 ? run(h, f, no, f, no) : run(h, f, no, h, no);
+    else grads32 ? run(h, h, no, f, no) : run(h, h, no, h, no);
 }
 
 // acc_grads: the gradients are fp32 whatever d->dtype is (for fp32 parameters that is what the fp32 kernels read anyway)
 // skip: the GUARD kernels (grad_coef is then given too)
 static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, void* const* exp_avg,
                         void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef, const long long* numels,
-                        hipStream_t stream, bool acc_grads = false, const float* skip = nullptr) {
+                        hipStream_t stream, bool acc_grads = false, const float* skip = nullptr, const unsigned* stream_ids = nullptr,
+                        unsigned long long seed = 0) {
     FF_CHECK(d && params && grads && exp_avg && exp_avg_sq && numels, FF_ERR_SHAPE, "ff_adamw_step: null argument");
     FF_CHECK(d->dtype == FF_DTYPE_F32 || d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_adamw_step: dtype %d", d->dtype);
     FF_CHECK(state_dtype == d->dtype || state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: moments must be stored in the parameter dtype or in fp32");
@@ -265,15 +319,18 @@ static int adamw_launch(const ff_adamw_desc* d, int state_dtype, void* const* pa
     t.bc1 = 1.f - powf(d->beta1, (float)std::max(d->step, 1));
     t.bc2_sqrt = sqrtf(1.f - powf(d->beta2, (float)std::max(d->step, 1)));
     t.grad_scale = d->grad_scale == 0.f ? 1.f : d->grad_scale;
+    t.seed = seed;
+    t.step = (unsigned)std::max(d->step, 1);
     const AdamVariant variant = skip ? kAdamGuard : grad_coef ? kAdamClip : kAdamPlain;
     return chunk_launches("ff_adamw_step", t.chunks, d->n_tensors, numels, [&](int cnt, int i) -> int {
         FF_CHECK(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && (!master || master[i]), FF_ERR_SHAPE, "ff_adamw_step: tensor %d has a null pointer", i);
         t.p[cnt] = params[i]; t.g[cnt] = grads[i]; t.m[cnt] = exp_avg[i]; t.v[cnt] = exp_avg_sq[i];
         t.w[cnt] = master ? master[i] : nullptr;
+        t.stream_id[cnt] = stream_ids ? stream_ids[i] : 0;
         return FF_OK;
     }, [&](int blocks, long long) -> int {
         if (master) FF_CHECK(state_dtype == FF_DTYPE_F32, FF_ERR_UNSUPPORTED, "ff_adamw_step: fp32 master copies go with fp32 moments");
-        adamw_dispatch(d->dtype, master != nullptr, state_dtype, acc_grads, variant, dim3(blocks), stream, t);
+        adamw_dispatch(d->dtype, master != nullptr, state_dtype, acc_grads, variant, stream_ids != nullptr, dim3(blocks), stream, t);
         return check_launch("adamw");
     });
 }
@@ -485,6 +542,32 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccTable t) 
         a[i] = fold(to_f32(g[i]), OVERWRITE ? 0.f : a[i]);
 }
 
+// ff_stochastic_round_bf16: dst = src rounded stochastically (ff_sr.h), element i with the bits the optimizer gives element i of a tensor:
+// 16-byte stores over the whole vectors where src and dst are on the 16-byte grid, the ragged tail - or, off the grid, everything - one by one
+__global__ __launch_bounds__(256) void sr_round_kernel(const float* src, bf16* dst, long long n, unsigned long long seed, unsigned step,
+                                                       unsigned stream_slot) {
+    const long long base = (long long)blockIdx.x * kAdamChunk, end = min(n, base + (long long)kAdamChunk);
+    long long tail = base;
+    if (((uintptr_t)src | (uintptr_t)dst) % 16 == 0) {             // (base is a multiple of the chunk, so every vector below is 16-byte aligned)
+        const long long vend = base + (end - base) / 8 * 8;
+        tail = vend;
+        for (long long i = base + (long long)threadIdx.x * 8; i < vend; i += 256 * 8) {
+            float lo[4], hi[4];
+            Vec<float>::load_nt(src + i, lo);
+            Vec<float>::load_nt(src + i + 4, hi);
+            const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            unsigned r[4];
+            sr_words(seed, i >> 3, step, stream_slot, r);
+            sr_store8<false>(dst + i, x, r);
+        }
+    }
+    for (long long i = tail + threadIdx.x; i < end; i += 256) {
+        unsigned r[4];
+        sr_words(seed, i >> 3, step, stream_slot, r);
+        dst[i] = sr_bf16_value(src[i], sr_r16(r, (int)(i & 7)));
+    }
+}
+
 // ff_grad_sumsq / ff_scale_grads: launch(blocks, first slot) on `t`, filled with the next tensors of the call
 template <typename F>
 static int grad_launches(const char* what, int n_tensors, void* const* grads, const long long* numels, GradTable& t, F&& launch) {
@@ -529,6 +612,29 @@ extern "C" int ff_adamw_step_guarded(const ff_adamw_desc* d, int state_dtype, vo
     FF_CHECK(grad_coef && skip, FF_ERR_SHAPE, "ff_adamw_step_guarded: %s is null", grad_coef ? "skip" : "grad_coef");
     return ff::adamw_launch(d, state_dtype, params, grads, exp_avg, exp_avg_sq, master, lr_dev, grad_coef, numels, (hipStream_t)stream,
                             grads_fp32 != 0, skip);
+}
+extern "C" int ff_adamw_step_sr(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, int grads_fp32,
+                                void* const* exp_avg, void* const* exp_avg_sq, const float* lr_dev, const float* grad_coef, const float* skip,
+                                long long seed, const unsigned* stream_ids, const long long* numels, ff_stream_t stream) {
+    FF_CHECK(d && stream_ids, FF_ERR_SHAPE, "ff_adamw_step_sr: null argument");
+    FF_CHECK(d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_adamw_step_sr: dtype %d (stochastic rounding is for bf16 parameters)", d->dtype);
+    FF_CHECK(grad_coef || !skip, FF_ERR_SHAPE, "ff_adamw_step_sr: skip is given without grad_coef");
+    for (int i = 0; i < d->n_tensors; i++)
+        FF_CHECK(stream_ids[i] < (1u << 30), FF_ERR_SHAPE, "ff_adamw_step_sr: stream id %u of tensor %d is not below 2^30", stream_ids[i], i);
+    return ff::adamw_launch(d, state_dtype, params, grads, exp_avg, exp_avg_sq, nullptr, lr_dev, grad_coef, numels, (hipStream_t)stream,
+                            grads_fp32 != 0, skip, stream_ids, (unsigned long long)seed);
+}
+extern "C" int ff_stochastic_round_bf16(const float* src, void* dst, long long n, long long seed, unsigned stream_id, unsigned step, int slot,
+                                        ff_stream_t stream) {
+    using namespace ff;
+    const char* what = "ff_stochastic_round_bf16";
+    FF_CHECK(n >= 0 && (n == 0 || (src && dst)), FF_ERR_SHAPE, "%s: null argument", what);
+    FF_CHECK(stream_id < (1u << 30) && slot >= 0 && slot <= 3, FF_ERR_SHAPE, "%s: stream_id %u (< 2^30), slot %d (0 .. 3)", what, stream_id, slot);
+    if (n == 0) return FF_OK;
+    const long long blocks = chunks_of(n);
+    FF_CHECK(blocks <= kGradMaxBlocks, FF_ERR_SHAPE, "%s: %lld elements", what, n);
+    sr_round_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(src, (bf16*)dst, n, (unsigned long long)seed, step, stream_id << 2 | (unsigned)slot);
+    return check_launch(what);
 }
 extern "C" long long ff_grad_sumsq_partials(int n_tensors, const long long* numels) {
     return n_tensors > 0 && numels ? ff::grad_slots(n_tensors, numels) : 0;

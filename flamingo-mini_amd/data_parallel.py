@@ -307,6 +307,9 @@ class ShardedAdamW(torch.optim.Optimizer):
     parameters' update, with it - every rank gets the same coefficient bit for bit.  The update no longer overlaps backward.  `grad_norm`
     is the pre-clip norm of the last step.
 
+    Stochastic rounding (FusedAdamW(stochastic_rounding=True)) is not offered here: a shard's element index is not the parameter's, so the
+    streams would depend on the world size; pure-bf16 data-parallel training with it is GradientAllReducer + FusedAdamW.
+
     xGMI arithmetic (8 GPUs, 7 links x ~153 GB/s each): reduce-scatter + all-gather move 2 * (S / 8) per link pair instead of a
     ring's 2 * (7/8) * S over one link, and the update touches 1/8 of the state per rank.
     """

@@ -853,6 +853,23 @@ def quick_gelu(x: torch.Tensor) -> torch.Tensor:
     return _QuickGeluFn.apply(x)
 
 
+def stochastic_round_bf16(x: torch.Tensor, seed: int = 0, stream_id: int = 0, step: int = 0, slot: int = 0) -> torch.Tensor:
+    """A bfloat16 copy of the contiguous float32 GPU tensor x, every element rounded to one of its two bf16 neighbours with probability
+    proportional to the distance (unbiased; a representable value is kept, a non-finite one rounds as `.to(torch.bfloat16)` does):
+    ff_stochastic_round_bf16, FusedAdamW(stochastic_rounding=True)'s rule with the random bits that optimizer gives array `slot` of
+    parameter `stream_id` at step `step` under `sr_seed=seed`.  Use: an fp32 checkpoint's weights as the bf16 parameters of a pure-bf16
+    run without the bias of round-to-nearest (give every tensor its own stream_id)."""
+    ffi.require_cuda(x)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ffi.FusionLibraryError("stochastic_round_bf16 needs a contiguous float32 tensor")
+    if not (0 <= seed < 2 ** 64 and 0 <= stream_id < 2 ** 30 and 0 <= step < 2 ** 32 and 0 <= slot < 4):
+        raise ValueError(f"stochastic_round_bf16: seed {seed} (64 bits), stream_id {stream_id} (30 bits), step {step} (32 bits), slot {slot} (0 .. 3)")
+    out = _new_like(x, torch.bfloat16)
+    ffi.check(ffi.lib().ff_stochastic_round_bf16(x.data_ptr(), out.data_ptr(), x.numel(), seed - (seed >> 63 << 64), stream_id, step, slot,
+                                                 ffi.stream_handle(x.device)), "ff_stochastic_round_bf16")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------
 # shifted cross-entropy (modeling_flamingo.py:288-298)
 # ----------------------------------------------------------------------------------------------------

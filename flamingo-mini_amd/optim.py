@@ -46,7 +46,19 @@ GradientAllReducer the averaged gradients are non-finite on every rank as soon a
 torch.amp.GradScaler (eager): a capturable FusedAdamW sets `_step_supports_amp_scaling`, so `scaler.step(opt)` hands over its device scalars
 `opt.found_inf` / `opt.grad_scale` and calls step() without a host round trip.  step() passes them to ff_grad_guard: the step is skipped on
 found_inf != 0, the gradients are unscaled as they are read (coefficient / scale) - `.grad` keeps the scaled values, `grad_norm` is the norm
-of the unscaled gradients.  The sweep runs only if skip_nonfinite or max_grad_norm asks for it.  Not with an open accumulate() cycle."""
+of the unscaled gradients.  The sweep runs only if skip_nonfinite or max_grad_norm asks for it.  Not with an open accumulate() cycle.
+
+Stochastic rounding (pure-bf16 training without master copies): at the reference's lr 1e-4 an update is below half a bf16 ulp of most weights,
+and a store that rounds to nearest drops it - a weight of 0.75 never moves, and bf16 moments stall the same way (stochastic
+rounding).  `stochastic_rounding=True` stores every bf16 result of the kernel - the parameter, and the moments unless `state_dtype=torch.float32`
+keeps them in fp32 - as one of its two bf16 neighbours with probability proportional to the distance (ff_adamw_step_sr), so every store is
+unbiased and small updates accumulate in expectation: 4 bytes of optimizer state per parameter instead of the 12 of `master_dtype=torch.float32`,
+which it excludes (a master copy already keeps the bits).  The random bits are a pure function of (`sr_seed`, the parameter's ordinal in
+`param_groups` order, the step number, which of the three arrays, the element index) - Philox4x32-7, csrc/ff_sr.h - so two optimizers built
+alike make the same decisions whatever the bucketing: on every data-parallel rank, under step(only=...) in any partition, with or without
+accumulate(), eagerly or replayed from a graph; a skipped step does not consume its step number's bits.  Both settings are optimizer-wide and
+stay out of state_dict() (`step` is in it: resuming with the same arguments continues the same streams).  fp32 parameters of the same optimizer
+are updated as without it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -60,7 +72,7 @@ from . import ffi
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  grad_scale: float = 1.0, capturable: bool = False, master_dtype=None, state_dtype=None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, stochastic_rounding: bool = False, sr_seed: int = 0):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameters")
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
@@ -75,6 +87,13 @@ class FusedAdamW(torch.optim.Optimizer):
         if master_dtype is not None:
             state_dtype = torch.float32                   # fp32 masters go with fp32 moments
         self.master_dtype, self.state_dtype = master_dtype, state_dtype
+        # optimizer-wide and out of state_dict() as well: with `step`, which is in it, they name the random bits of every store
+        self.stochastic_rounding, self.sr_seed = bool(stochastic_rounding), int(sr_seed)
+        if self.stochastic_rounding and master_dtype is not None:
+            raise ValueError("FusedAdamW(stochastic_rounding=True) is for bf16 parameters without master copies: not with master_dtype (an fp32 "
+                             "master copy already keeps the bits a rounded store would drop)")
+        if not 0 <= self.sr_seed < 2 ** 64:
+            raise ValueError(f"sr_seed must be a 64-bit unsigned integer, got {sr_seed}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, capturable=capturable))
         self._acc = {}                                    # accumulate(): parameter -> its fp32 accumulator (kept from cycle to cycle)
         self._acc_fresh = set()                           # ... the parameters folded at least once since the last step()
@@ -86,6 +105,16 @@ class FusedAdamW(torch.optim.Optimizer):
                              "count lives on the device)")
         if self.skip_nonfinite and len({p.device for g in self.param_groups for p in g["params"]}) > 1:
             raise ValueError("FusedAdamW(skip_nonfinite=True) needs every parameter on one device (the verdict is reached on it)")
+
+    def add_param_group(self, param_group) -> None:
+        """Every parameter gets its stochastic-rounding stream id here: its ordinal in param_groups order, never changed afterwards (the
+        constructor adds the groups through this method)."""
+        super().add_param_group(param_group)
+        ids = self.__dict__.setdefault("_sr_ids", {})
+        for p in self.param_groups[-1]["params"]:
+            ids.setdefault(p, len(ids))
+        if len(ids) > 2 ** 30:
+            raise ValueError("FusedAdamW: more than 2^30 parameters (the stochastic-rounding stream id has 30 bits)")
 
     @property
     def grad_norm(self) -> Optional[torch.Tensor]:
@@ -234,7 +263,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                      group["weight_decay"], group["grad_scale"], step_dev)
                 adamw_step_call(lib, desc, bucket["state_code"], (bucket["param_ptrs"], bucket["acc_ptrs"] if acc else grad_ptrs, bucket["m_ptrs"],
                                                                   bucket["v_ptrs"], bucket["w_ptrs"], bucket["numels"]),
-                                lr_dev, coef, self._clip["skip"] if guard else None, acc, ffi.stream_handle(bucket["device"]))
+                                lr_dev, coef, self._clip["skip"] if guard else None, acc, ffi.stream_handle(bucket["device"]),
+                                sr=None if bucket["sr_ids"] is None else (self.sr_seed, bucket["sr_ids"]))
         if acc:
             self.reset_accumulation()                     # the cycle is closed: the next accumulate() overwrites
         return loss
@@ -305,7 +335,7 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _buckets(self, gi, group, only=None, acc=False):
         """Parameters with a gradient, grouped by (dtype, device, step count); the pointer tables of everything that does not
-        change between steps (parameters, moments, sizes) are built once and reused while the same parameters have gradients.
+        change between steps (parameters, moments, sizes, stochastic-rounding stream ids) are built once and reused while the same parameters have gradients.
         acc: the parameters folded by accumulate() in the open cycle instead, their fp32 accumulators as `acc_ptrs` (the same cache slot,
         so the host-mode step count has one owner whichever kind of step ran last)."""
         if acc:
@@ -348,7 +378,10 @@ class FusedAdamW(torch.optim.Optimizer):
                                 acc_ptrs=ffi.ptr_array([self._acc[p] for p in params]) if acc else None,
                                 m_ptrs=ffi.ptr_array([self.state[p]["exp_avg"] for p in params]),
                                 v_ptrs=ffi.ptr_array([self.state[p]["exp_avg_sq"] for p in params]),
-                                numels=(C.c_longlong * n)(*[p.numel() for p in params])))
+                                numels=(C.c_longlong * n)(*[p.numel() for p in params]),
+                                # stochastic rounding: the bf16 parameters' stream ids (they have no master copies); None = round to nearest
+                                sr_ids=(C.c_uint * n)(*[self._sr_ids[p] for p in params])
+                                if self.stochastic_rounding and dtype == torch.bfloat16 and not has_master else None))
         cache[slot] = (key, buckets)
         return buckets
 
@@ -428,13 +461,21 @@ class FusedAdamW(torch.optim.Optimizer):
         return out
 
 
-def adamw_step_call(lib, desc, state_code, ptrs, lr_dev, coef, skip, grads_fp32, stream) -> None:
+def adamw_step_call(lib, desc, state_code, ptrs, lr_dev, coef, skip, grads_fp32, stream, sr=None) -> None:
     """The one call site of the AdamW entry points.  ptrs: the pointer tables (params, grads, exp_avg, exp_avg_sq, master or None, numels);
     coef / skip: the 0-dim device tensors of the clip coefficient and of the guard's verdict, or None; grads_fp32: the gradients are the
     fp32 accumulators of ff_grad_accumulate.  skip -> ff_adamw_step_guarded, else grads_fp32 -> ff_adamw_step_acc (coef optional), else
-    coef -> ff_adamw_step_clipped, else ff_adamw_step_mixed."""
+    coef -> ff_adamw_step_clipped, else ff_adamw_step_mixed.  sr: (seed, stream ids as a C unsigned array, one per tensor) ->
+    ff_adamw_step_sr, which takes coef, skip and grads_fp32 as they are (bf16 parameters without master copies)."""
     p, g, m, v, w, numels = ptrs
     c = None if coef is None else coef.data_ptr()
+    if sr is not None:
+        if w is not None:
+            raise ffi.FusionLibraryError("stochastic rounding is for parameters without fp32 master copies")
+        seed, ids = sr
+        ffi.check(lib.ff_adamw_step_sr(desc, state_code, p, g, int(grads_fp32), m, v, lr_dev, c, None if skip is None else skip.data_ptr(),
+                                       seed - (seed >> 63 << 64), ids, numels, stream), "ff_adamw_step_sr")
+        return
     if skip is not None:
         name, args = "ff_adamw_step_guarded", (p, g, int(grads_fp32), m, v, w, lr_dev, c, skip.data_ptr())
     elif grads_fp32:

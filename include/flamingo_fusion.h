@@ -50,7 +50,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * 6: fp32 gradient accumulation: ff_grad_accumulate, ff_adamw_step_acc;
                                 * still 6, additions only: the non-finite gradient guard ff_grad_guard, ff_adamw_step_guarded;
                                 * still 6, addition only: token selection for sampled decoding, ff_sample_token;
-                                * still 6, additions only: beam search on the captured decode step, ff_beam_step, ff_beam_gather) */
+                                * still 6, additions only: beam search on the captured decode step, ff_beam_step, ff_beam_gather;
+                                * still 6, additions only: stochastic rounding for pure-bf16 training, ff_adamw_step_sr, ff_stochastic_round_bf16) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -455,6 +456,34 @@ int ff_grad_guard(const double* sum, float max_norm, const float* ext_found_inf,
 int ff_adamw_step_guarded(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, int grads_fp32,
                           void* const* exp_avg, void* const* exp_avg_sq, float* const* master, const float* lr_dev, const float* grad_coef,
                           const float* skip, const long long* numels, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Stochastic rounding for pure-bf16 training (added under ABI 6): at lr 1e-4 an update is below half a bf16 ulp of most weights, and a
+ * store that rounds to nearest loses it every step.  Here the fp32 result x (bit pattern b) is stored as one of its two bf16 neighbours,
+ * the farther one with probability proportional to the distance, so that every store is unbiased:
+ *     r = 16 random bits;  s = b + r (32-bit add);  stored = (exponent field of s all ones ? b : s) >> 16
+ * (the exception keeps a carry past the largest finite bf16 from producing an infinity); a non-finite x is stored as round-to-nearest
+ * stores it.  A representable x is stored unchanged; exactly b & 0xFFFF of the 65536 values of r round away from zero; -0 stays -0.
+ * Random bits: Philox4x32 with 7 rounds (Random123's round function and constants), one call per 8-element vector of one stored array:
+ *     key     = (seed low 32, seed high 32)
+ *     counter = (vec low 32, vec high 32, step, stream_id << 2 | slot)      vec = element index within the tensor >> 3
+ *     slot    = 0 parameter, 1 exp_avg, 2 exp_avg_sq;   stream_id < 2^30 names the tensor;   step = the number of the step being taken
+ *     element e takes 16 bits of output word (e & 7) >> 1: the low half if e is even, the high half if it is odd
+ * so the stored bits do not depend on alignment, on how tensors are grouped into calls, or on the path (vector / element-wise) that ran.
+ *   ff_adamw_step_sr          ff_adamw_step_guarded's argument list without `master`, plus the seed (its 64 bits, signedness ignored) and
+ *                             one stream id per tensor (a HOST array).  bf16 parameters only (FF_ERR_UNSUPPORTED otherwise); the parameter
+ *                             store uses slot 0 and, where state_dtype is bf16, the moment stores slots 1 and 2 (fp32 moments are stored as
+ *                             they are).  grad_coef and skip may be NULL: both NULL = ff_adamw_step_mixed's arithmetic (grads_fp32 != 0:
+ *                             ff_adamw_step_acc's), grad_coef alone = ff_adamw_step_clipped's, both = ff_adamw_step_guarded's.  step is
+ *                             d->step, or *d->step_dev converted to unsigned.  FF_ERR_SHAPE for a null stream_ids or an id >= 2^30.
+ *   ff_stochastic_round_bf16  dst[i] (bf16) = src[i] (fp32) by the same rule with the bits of element i: n contiguous elements of any
+ *                             alignment, slot 0 .. 3.  The rule on its own (tests), and an unbiased bf16 copy of fp32 weights.
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_adamw_step_sr(const ff_adamw_desc* d, int state_dtype, void* const* params, const void* const* grads, int grads_fp32,
+                     void* const* exp_avg, void* const* exp_avg_sq, const float* lr_dev, const float* grad_coef, const float* skip,
+                     long long seed, const unsigned* stream_ids, const long long* numels, ff_stream_t stream);
+int ff_stochastic_round_bf16(const float* src, void* dst, long long n, long long seed, unsigned stream_id, unsigned step, int slot,
+                             ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Shifted next-token cross-entropy (modeling_flamingo.py:288-298): position i predicts labels[i+1].

@@ -1,0 +1,100 @@
+"""Cost of stochastic rounding in the optimizer step alone, over the trainable parameter shapes of a bench.py workload (default: config B).
+
+    python tools/adamw_sr_bench.py [--config B] [--rounds 7] [--steps 20] [--out FILE]
+
+Four FusedAdamW(capturable=True) optimizers over their own bf16 copies of the same parameter shapes (one shared set of bf16 gradients):
+    rne        bf16 moments, round to nearest                    (the default configuration)
+    sr         bf16 moments, stochastic rounding                 (three Philox calls per 8-element vector)
+    sr_f32     fp32 moments, stochastic rounding                 (one call per vector)
+    master     fp32 master copies and fp32 moments               (the remedy before stochastic rounding)
+Each step() is captured into a HIP graph after an eager warm-up step; the graphs are replayed alternately (`--rounds` rounds of `--steps`
+back-to-back replays each, device events around each block), so that clock and thermal drift fall on all arms alike.  Prints one JSON
+line: median ms per step of each arm, the bytes a step of each arm moves (computed from the shapes: reads + writes of parameters,
+gradients, moments, master copies), the rate that gives, the median per-round differences against rne and master, and the optimizer
+state each arm keeps per parameter.  The model is only built for its shapes and dropped before anything is timed."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ARMS = {   # name: (FusedAdamW arguments, bytes moved per parameter and step, bytes of optimizer state per parameter)
+    "rne": (dict(), 2 * 2 + 2 + 2 * 2 * 2, 4),
+    "sr": (dict(stochastic_rounding=True, sr_seed=1), 2 * 2 + 2 + 2 * 2 * 2, 4),
+    "sr_f32": (dict(stochastic_rounding=True, sr_seed=1, state_dtype=torch.float32), 2 * 2 + 2 + 2 * 2 * 4, 8),
+    "master": (dict(master_dtype=torch.float32), 2 + 2 + 2 * 4 + 2 * 2 * 4, 12),
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="B")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    saved, sys.argv = sys.argv, [sys.argv[0], "--config", a.config]
+    import bench
+    args = bench.parse()
+    sys.argv = saved
+    from flamingo_mini_amd import FusedAdamW, ffi
+    ffi.lib()
+    device = torch.device("cuda", 0)
+    model, _ = bench.build_model(args, device, torch.bfloat16)
+    shapes = [tuple(p.shape) for p in model.parameters_trainable()]
+    del model
+    torch.cuda.empty_cache()
+    n_params = sum(torch.Size(s).numel() for s in shapes)
+    gen = torch.Generator(device=device).manual_seed(1)
+    grads = [(torch.randn(s, generator=gen, device=device) * 1e-3).to(torch.bfloat16) for s in shapes]
+    graphs, opts = {}, {}
+    for name, (kw, _, _) in ARMS.items():
+        params = [torch.nn.Parameter((torch.randn(s, generator=gen, device=device) * 0.02).to(torch.bfloat16)) for s in shapes]
+        for p, g in zip(params, grads):
+            p.grad = g
+        opt = opts[name] = FusedAdamW(params, lr=1e-4, capturable=True, **kw)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                          # the eager step allocates the state and the device counters
+            opt.step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name]):
+            opt.step()
+    times = {k: [] for k in ARMS}
+    for _ in range(a.rounds):
+        for name, graph in graphs.items():
+            graph.replay()                                     # (one untimed replay after switching)
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(a.steps):
+                graph.replay()
+            t1.record()
+            t1.synchronize()
+            times[name].append(t0.elapsed_time(t1) / a.steps)
+    out = dict(config=a.config, tensors=len(shapes), trainable_params=n_params, rounds=a.rounds, steps_per_round=a.steps)
+    for name, (_, per_param, state) in ARMS.items():
+        ms = statistics.median(times[name])
+        out[name] = dict(ms_median=round(ms, 4), ms_all=[round(t, 4) for t in times[name]], bytes_per_step=per_param * n_params,
+                         tb_per_s=round(per_param * n_params / (ms * 1e-3) / 1e12, 3), state_bytes_per_param=state,
+                         steps_taken=int(float(opts[name].state_dict()["state"][0]["step"])))
+    for name in ("sr", "sr_f32", "master"):
+        out[f"{name}_minus_rne_ms_median"] = round(statistics.median([x - y for x, y in zip(times[name], times["rne"])]), 4)
+    for name in ("sr", "sr_f32"):
+        out[f"{name}_minus_master_ms_median"] = round(statistics.median([x - y for x, y in zip(times[name], times["master"])]), 4)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
