@@ -943,6 +943,29 @@ def sample_tokens(logits: torch.Tensor, u: torch.Tensor, temperature: float = 1.
     return out
 
 
+def process_logits(logits: torch.Tensor, hist: torch.Tensor, hist_len: torch.Tensor, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                   eos: Optional[int] = None, min_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Repetition penalty, no-repeat n-gram ban and minimum length applied IN PLACE to `logits` (rows, V), float32 / bfloat16 on the GPU, against
+    the token history `hist` (rows, cap <= 4096) int64, of which the first hist_len (a one-element int64 device tensor, one value for all rows)
+    positions count: ff_logits_process, one launch, nothing allocated, capturable; the exact rules are in include/flamingo_fusion.h.  Only the
+    last dimension of either tensor has to be contiguous (logits3d[:, -1] and ids_buf work in place).  `min_len` (a one-element int64 device
+    tensor) with `eos` bans the eos entry while hist_len < min_len.  With every processor off nothing is launched.  Returns `logits`."""
+    ffi.require_cuda(logits, hist, hist_len, min_len)
+    if logits.ndim != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"process_logits: logits must be (rows, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
+    rows, V = logits.shape
+    if hist.dtype != torch.long or hist.ndim != 2 or hist.shape[0] != rows or (hist.shape[1] > 1 and hist.stride(1) != 1):
+        raise ValueError(f"process_logits: hist must be ({rows}, cap) int64 with a contiguous last dimension, got {tuple(hist.shape)} {hist.dtype} strides {hist.stride()}")
+    if hist_len.dtype != torch.long or hist_len.numel() != 1 or (min_len is not None and (min_len.dtype != torch.long or min_len.numel() != 1)):
+        raise ValueError("process_logits: hist_len and min_len must each be one int64 value on the device")
+    cap = hist.shape[1]
+    ffi.check(ffi.lib().ff_logits_process(ffi.dtype_code(logits.dtype), rows, V, logits.stride(0) if rows > 1 else V, logits.data_ptr(),
+                                          hist.data_ptr(), hist.stride(0) if rows > 1 else cap, cap, hist_len.data_ptr(), float(repetition_penalty),
+                                          int(no_repeat_ngram_size), -1 if eos is None else int(eos), ffi.ptr(min_len), ffi.stream_handle(logits.device)),
+              "ff_logits_process")
+    return logits
+
+
 class BeamState:
     """The device state block of ff_beam_step for b sequences x nb beams and histories of max_len positions (layout and rules:
     include/flamingo_fusion.h).  All fields are views of ONE byte buffer, so `to_host()` is one device-to-host copy.  `storage` (uint8,

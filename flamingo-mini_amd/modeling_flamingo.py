@@ -361,9 +361,14 @@ class _DecodeSession:
     are b * nb rows wide (row s * nb + k = beam k of sequence s; the visual features are encoded once per sequence and repeated), and _append
     is functional.beam_step (selection and all bookkeeping in a device state block, csrc/ff_beam.hip), functional.beam_gather (the static LM
     cache reordered in place by beam index, live positions only) and tok <- next_tok.  The cross-attention K / V, the attention mask and
-    text_time are equal within a sequence's beams and are NOT reordered.  The result is read back once, after the loop (_beam_finalize)."""
+    text_time are equal within a sequence's beams and are NOT reordered.  The result is read back once, after the loop (_beam_finalize).
+    `processors` = (repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens) puts functional.process_logits (one launch,
+    csrc/ff_logits.hip) in front of the selection of every mode: it edits the step's logits in place against the token history - `ids_buf`
+    with `pos` as its length, which already is the sequence; in a beam session `seq_buf` (b * nb, max_length), which follows the beams through
+    the same in-place gather as the LM cache (viewed as two 4-byte elements per id) - and against `min_len`, a device scalar run() sets
+    outside any capture.  A session without processors issues none of this and allocates no seq_buf."""
 
-    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None):
+    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None):
         from transformers.cache_utils import StaticCache
         self._model_ref = weakref.ref(model)
         self.beams, self.nb, self.n_seq = beams, (beams[0] if beams else 1), b
@@ -387,7 +392,13 @@ class _DecodeSession:
             self.state = F.BeamState(self.n_seq, self.nb, max_length, device, eos=eos, pad=self.fill, early_stopping=beams[1], length_penalty=beams[2])
             self.cur_len = torch.zeros((1,), dtype=torch.long, device=device)  # pos + 1: the length after the token beam_step chooses
             self.lm_tensors = None                                             # keys / values of every StaticCache layer (allocated by the first prompt step)
-        self.xattn_past = None                                                 # persistent (k, v) per layer, filled by every prompt step
+        self.processors = processors
+        if processors is not None:
+            self.min_len = torch.zeros((1,), dtype=torch.long, device=device)
+            self.min_on = eos is not None and (processors[2] > 0 or processors[3] > 0)
+            if beams is not None:
+                self.seq_buf = torch.full((b, max_length), self.fill, dtype=torch.long, device=device)
+        self.xattn_past = None                                                # persistent (k, v) per layer, filled by every prompt step
         self.replay = None
         self.capture_failed = False
         self.param_ptrs = self._param_ptrs()                                   # what a captured graph reads: checked before every reuse
@@ -407,15 +418,26 @@ class _DecodeSession:
         a captured graph would replay reads of freed memory."""
         return self.param_ptrs != self._param_ptrs()
 
+    def _process(self, logits, hist):      # the logits processors, in place, against the first `pos` tokens of every row of `hist`
+        p, g = self.processors[:2]
+        F.process_logits(logits, hist, self.pos, p, g, self.eos if self.min_on else None, self.min_len if self.min_on else None)
+
     def _append(self, logits):             # choose, apply the eos bookkeeping of generate(), append at `pos`
         if self.beams is not None:
             if self.lm_tensors is None:
                 self.lm_tensors = [t for layer in self.cache.layers for t in (layer.keys, layer.values)]
+            if self.processors is not None:
+                self._process(logits, self.seq_buf)
             torch.add(self.pos, 1, out=self.cur_len)
             nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
             F.beam_gather(self.lm_tensors, beam_idx, self.pos, self.nb)       # positions < pos are live: the cache rows follow their beams
+            if self.processors is not None:                                   # ... and so do the histories: an id is two 4-byte elements
+                F.beam_gather([self.seq_buf.view(torch.int32).view(self.b, 1, self.max_length, 2)], beam_idx, self.pos, self.nb)
+                self.seq_buf.index_copy_(1, self.pos, nxt[:, None])
             self.tok.copy_(nxt[:, None])
             return
+        if self.processors is not None:
+            self._process(logits, self.ids_buf)
         if self.sampling is None:
             nxt = logits.float().argmax(-1)
         else:
@@ -478,6 +500,11 @@ class _DecodeSession:
         self.finished.zero_()
         self.n_new.zero_()
         self.pos.fill_(L0)
+        if self.processors is not None:
+            self.min_len.fill_(max(self.processors[2], L0 + self.processors[3]))
+            if self.beams is not None:
+                self.seq_buf.fill_(self.fill)
+                self.seq_buf[:, :L0] = ids
         self._append(out.logits[:, -1])
         remaining = self.max_length - L0 - 1
         if self.graph_wanted and self.replay is None and not self.capture_failed and remaining > 1:
@@ -633,12 +660,37 @@ class FlamingoModel(PreTrainedModel):
             logits = logits.masked_fill(drop.scatter(-1, idx, drop), float("-inf"))
         return logits
 
+    @staticmethod
+    def _process_logits(logits, seqs, repetition_penalty, no_repeat_ngram_size, eos, min_len):
+        """Repetition penalty, no-repeat n-gram ban and minimum length on float32 `logits` (rows, V) against the sequences so far `seqs`
+        (rows, n): the rules of ff_logits_process (include/flamingo_fusion.h) restated in torch for the dynamic loops, with the same
+        x * (1.0f / p) where transformers divides.  Returns new logits."""
+        V, n = logits.shape[-1], seqs.shape[1]
+        seqs = seqs.long()
+        valid = (seqs >= 0) & (seqs < V)
+        out = torch.cat([logits, logits.new_zeros(logits.shape[0], 1)], dim=1)          # column V takes what out-of-range ids would write
+        if repetition_penalty != 1.0 and n > 0:
+            import numpy as np
+            p = np.float32(repetition_penalty)
+            idx = torch.where(valid, seqs, torch.full_like(seqs, V))
+            x = out.gather(1, idx)
+            out.scatter_(1, idx, torch.where(x < 0, x * float(p), x * float(np.float32(1.0) / p)))
+        if 1 <= no_repeat_ngram_size <= n:
+            g = no_repeat_ngram_size
+            win = seqs.unfold(1, g, 1)                                                   # (rows, n - g + 1, g)
+            match = (win[..., :g - 1] == seqs[:, None, n - g + 1:]).all(-1)
+            out.scatter_(1, torch.where(match & valid[:, g - 1:], win[..., -1], torch.full_like(win[..., -1], V)), float("-inf"))
+        if eos is not None and min_len is not None and n < min_len:
+            out[:, eos] = float("-inf")
+        return out[:, :V].contiguous()
+
     @torch.no_grad()
     def generate(self, inputs=None, media_locations=None, attention_mask=None, pixel_values=None, visual_features=None,
                  max_length: int = 150, num_beams: int = 1, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
                  top_p: float = 1.0, eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, bos_token_id: Optional[int] = None,
                  early_stopping: bool = True, length_penalty: float = 1.0, use_cache: bool = True, generator: Optional[torch.Generator] = None,
-                 input_ids=None, static_decode: Optional[bool] = None, **unsupported):
+                 input_ids=None, static_decode: Optional[bool] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                 min_length: int = 0, min_new_tokens: int = 0, **unsupported):
         """Text generation with the cached cross-attention path: the first step runs CLIP + resampler and fills the xattn K/V and LM caches,
         every later step feeds one token (reference: HF `generate` through prepare_inputs_for_generation / _reorder_cache, :464-548).
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
@@ -648,38 +700,67 @@ class FlamingoModel(PreTrainedModel):
         `static_decode=True` is passed explicitly (GPU tensors, a GPT-2- or OPT-backed model, a prompt shorter than max_length - 1); otherwise it runs the dynamic loop
         below, as it always has.  The two paths draw DIFFERENT token streams from the same seed: the static path draws by inverse CDF in
         vocabulary order from one uniform number per token (functional.sample_tokens), the dynamic loop with torch.multinomial.  Both are
-        reproducible per seed (`generator`)."""
+        reproducible per seed (`generator`).
+        Logits processors, as in transformers: `repetition_penalty` (1 = off), `no_repeat_ngram_size` (0 = off) and `min_length` /
+        `min_new_tokens` (both need eos_token_id) act on the logits of every step BEFORE the selection of every mode, against the whole
+        sequence so far, prompt included.  On the static path they are one in-place launch inside the replayed step
+        (functional.process_logits; int64 ids, max_length <= 4096 - otherwise the dynamic loop runs), on the dynamic paths the torch
+        restatement _process_logits.  They are offered for GPU tensors only: with CPU tensors generate() raises TypeError for them, as it
+        did before they existed (the processor kernel has no CPU form; static_decode=True raises what ffi.require_cuda raises).  Deliberate deviation from transformers in beam search: the log-softmax is taken AFTER the processors, so
+        the mass of banned tokens is renormalised over the rest, where transformers penalises log-probabilities without renormalising."""
         if unsupported:
             raise TypeError(f"generate(): unsupported generation arguments {sorted(unsupported)}")
         if not use_cache:
             raise ValueError("generate() always decodes with the cross-attention / LM caches (use_cache=True)")
+        if isinstance(repetition_penalty, bool) or not isinstance(repetition_penalty, (int, float)) or not 0 < repetition_penalty < float("inf"):
+            raise ValueError(f"generate(): repetition_penalty must be a positive, finite number (1 = off), got {repetition_penalty!r}")
+        for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_length", min_length), ("min_new_tokens", min_new_tokens)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"generate(): {name} must be an integer >= 0 (0 = off), got {v!r}")
+        if (min_length > 0 or min_new_tokens > 0) and eos_token_id is None:
+            raise ValueError("generate(): min_length / min_new_tokens need eos_token_id")
+        procs = None                                                          # every processor off: exactly the paths without them
+        if repetition_penalty != 1 or no_repeat_ngram_size > 0 or min_length > 0 or min_new_tokens > 0:
+            procs = (float(repetition_penalty), int(no_repeat_ngram_size), int(min_length), int(min_new_tokens))
         ids = inputs if inputs is not None else input_ids
         assert ids is not None and media_locations is not None, "generate() needs input ids and media_locations"
         am = attention_mask if attention_mask is not None else torch.ones_like(ids)
         ml = media_locations
         pad = pad_token_id if pad_token_id is not None else eos_token_id
+        if procs is not None and not ids.is_cuda:                             # GPU tensors only: on CPU tensors they stay what they were, unsupported
+            if static_decode:
+                F.ffi.require_cuda(ids)
+            given = [n for n, v, off in (("repetition_penalty", repetition_penalty, 1), ("no_repeat_ngram_size", no_repeat_ngram_size, 0),
+                                         ("min_length", min_length, 0), ("min_new_tokens", min_new_tokens, 0)) if v != off]
+            raise TypeError(f"generate(): unsupported generation arguments {given} on CPU tensors (the logits processors run on the GPU only)")
+        static_ok = isinstance(self.flamingo, (FlamingoGPT2, FlamingoOPT)) and ids.shape[1] + 1 < max_length and \
+            (procs is None or (ids.dtype == torch.long and max_length <= F.ffi.LOGITS_HIST_MAX))
         if num_beams > 1:
             if do_sample:
                 raise ValueError("beam search with sampling is not implemented")
             if static_decode:                                                 # explicit static_decode=True: the beam kernels have no CPU form
                 F.ffi.require_cuda(ids)
-                if isinstance(self.flamingo, (FlamingoGPT2, FlamingoOPT)) and ids.shape[1] + 1 < max_length and num_beams <= F.ffi.BEAM_MAX:
+                if static_ok and num_beams <= F.ffi.BEAM_MAX:
                     return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
-                                               beams=(int(num_beams), bool(early_stopping), float(length_penalty)))
-            return self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty)
+                                               beams=(int(num_beams), bool(early_stopping), float(length_penalty)), processors=procs)
+            return self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty,
+                                     processors=procs)
         if do_sample and static_decode:                                       # explicit static_decode=True: the sampling kernel has no CPU form
             F.ffi.require_cuda(ids)
-            if isinstance(self.flamingo, (FlamingoGPT2, FlamingoOPT)) and ids.shape[1] + 1 < max_length:
+            if static_ok:
                 return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
-                                           sampling=(float(temperature), int(top_k), float(top_p)), generator=generator)
+                                           sampling=(float(temperature), int(top_k), float(top_p)), generator=generator, processors=procs)
         if static_decode is None:       # greedy decoding on the GPU (GPT-2- and OPT-backed models): fixed-shape decode steps, replayed from a HIP graph
             static_decode = ids.is_cuda and self.static_decode
-        if static_decode and not do_sample and isinstance(self.flamingo, (FlamingoGPT2, FlamingoOPT)) and ids.shape[1] + 1 < max_length:
-            return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad)
+        if static_decode and not do_sample and static_ok:
+            return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, processors=procs)
         finished = torch.zeros(ids.shape[0], dtype=torch.bool, device=ids.device)
         past, step_ids = None, ids
+        min_len = None if procs is None or eos_token_id is None else max(procs[2], ids.shape[1] + procs[3])
         while ids.shape[1] < max_length:
             logits, past = self._decode_step(step_ids, ml, am, past, pixel_values, visual_features)
+            if procs is not None:
+                logits = self._process_logits(logits, ids, procs[0], procs[1], eos_token_id, min_len)
             if do_sample:
                 probs = self._filter_logits(logits, temperature, top_k, top_p).softmax(-1)
                 nxt = torch.multinomial(probs, 1, generator=generator)[:, 0]
@@ -697,9 +778,9 @@ class FlamingoModel(PreTrainedModel):
         return ids
 
     def _static_greedy(self, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, graph: Optional[bool] = None,
-                       sampling=None, generator=None, beams=None):
+                       sampling=None, generator=None, beams=None, processors=None):
         """Greedy (or, with `sampling` = (temperature, top_k, top_p), sampled) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches and buffers plus, on the GPU, the captured
-        HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, eos / pad, sampling settings, beam settings (nb, early_stopping, length_penalty)) and reused by later calls, so only the
+        HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, eos / pad, sampling settings, beam settings (nb, early_stopping, length_penalty), logits processors) and reused by later calls, so only the
         first caption batch of a shape pays for the capture.  a session whose model's parameters were re-allocated since (model.to(), ShardedAdamW) is rebuilt; reset_decode_sessions() drops them all."""
         b = ids.shape[0]
         if graph is None:
@@ -707,7 +788,7 @@ class FlamingoModel(PreTrainedModel):
         sessions = _DECODE_SESSIONS.setdefault(self, {})
         n_media = int(ml.sum(-1).max()) if visual_features is None and pixel_values is None else \
             (visual_features.shape[1] if visual_features is not None else (pixel_values.shape[1] if pixel_values.ndim >= 5 else pixel_values.shape[0]))
-        key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams)
+        key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams, processors)
         sess = sessions.get(key)
         if sess is not None and sess.stale():
             sessions.pop(key)
@@ -715,7 +796,7 @@ class FlamingoModel(PreTrainedModel):
         if sess is None:
             if len(sessions) >= 4:                                            # a handful of shapes at most: each holds a KV cache and a graph
                 sessions.pop(next(iter(sessions)))
-            sess = sessions[key] = _DecodeSession(self, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling, beams)
+            sess = sessions[key] = _DecodeSession(self, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling, beams, processors)
         if sampling is None:
             return sess.run(ids, ml, am, pixel_values, visual_features)
         return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator)
@@ -727,13 +808,17 @@ class FlamingoModel(PreTrainedModel):
     def reset_decode_sessions(self) -> None:
         _DECODE_SESSIONS.pop(self, None)
 
-    def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty):
+    def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None):
         """Standard beam search over the cached decode path.  The prompt runs once per sequence; its caches are then replicated per beam
-        (xattn K/V: repeat_interleave; LM cache: Cache.batch_repeat_interleave) and re-ordered every step (_reorder_cache)."""
+        (xattn K/V: repeat_interleave; LM cache: Cache.batch_repeat_interleave) and re-ordered every step (_reorder_cache).
+        `processors` (see generate()) act on every step's logits before the log-softmax."""
         b, L0 = ids.shape
         dev = ids.device
+        min_len = None if processors is None or eos is None else max(processors[2], L0 + processors[3])
+        process = (lambda x, s: x) if processors is None else \
+            (lambda x, s: FlamingoModel._process_logits(x, s, processors[0], processors[1], eos, min_len))
         logits, past = self._decode_step(ids, ml, am, None, pixel_values, visual_features)
-        logp = logits.log_softmax(-1)
+        logp = process(logits, ids).log_softmax(-1)
         V = logp.shape[-1]
         xattn_past, lm_past = past
         xattn_past = tuple(tuple(_repeat_leading(t, nb) for t in kv) for kv in xattn_past)
@@ -786,7 +871,7 @@ class FlamingoModel(PreTrainedModel):
             ml = torch.cat([ml, torch.zeros_like(ml[:, :1])], dim=1)
             am = torch.cat([am, torch.ones_like(am[:, :1])], dim=1)
             logits, past = self._decode_step(seqs[:, -1:], ml, am, past, None, None)
-            logp = logits.log_softmax(-1)
+            logp = process(logits, seqs).log_softmax(-1)
         out = []
         for bi in range(b):
             hyps = list(done_hyps[bi])
@@ -802,7 +887,8 @@ class FlamingoModel(PreTrainedModel):
     def generate_captions(self, processor, pixel_values=None, images=None, prompt: str = "<image>", max_length: int = 150,
                           num_beams: int = 1, device=None, **kwargs):
         """Caption a batch of images; the prompt is replicated for every image (reference :550-605).  `kwargs` are generation
-        arguments (do_sample, temperature, top_k, top_p, length_penalty, ...) and go to generate(), which rejects unknown ones."""
+        arguments (do_sample, temperature, top_k, top_p, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length,
+        min_new_tokens, ...) and go to generate(), which rejects unknown ones."""
         if device is None:
             device = self.device
         if images is not None:

@@ -51,7 +51,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, additions only: the non-finite gradient guard ff_grad_guard, ff_adamw_step_guarded;
                                 * still 6, addition only: token selection for sampled decoding, ff_sample_token;
                                 * still 6, additions only: beam search on the captured decode step, ff_beam_step, ff_beam_gather;
-                                * still 6, additions only: stochastic rounding for pure-bf16 training, ff_adamw_step_sr, ff_stochastic_round_bf16) */
+                                * still 6, additions only: stochastic rounding for pure-bf16 training, ff_adamw_step_sr, ff_stochastic_round_bf16;
+                                * still 6, addition only: logits processors on the captured decode step, ff_logits_process) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -577,6 +578,36 @@ int ff_beam_step(const ff_beam_desc* d, const void* logits, const long long* cur
                  ff_stream_t stream);
 int ff_beam_gather(int n_tensors, void* const* tensors, int elem_size, int b, int nb, long long outer, long long len_max, long long inner,
                    const long long* beam_idx, const long long* n_pos, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Logits processors on the captured decode step (added under ABI 6): repetition penalty, no-repeat n-gram ban and minimum length, applied
+ * IN PLACE to the rows a step is about to select from (argmax, ff_sample_token, ff_beam_step).  One launch, no allocation, no host
+ * synchronisation, capturable; equal inputs give equal bits, eager or replayed.
+ * logits: `rows` rows of `vocab` elements of `dtype` (FF_DTYPE_F32 / FF_DTYPE_BF16), row r at element r * ld, ld >= vocab, element alignment
+ * only (the contract of ff_sample_token: logits[:, -1] of a (batch, seq, vocab) tensor works).  hist: int64 token ids, row r at
+ * hist + r * hist_ld, hist_ld >= hist_cap.  *hist_len: a device int64, the number of tokens the sequences already hold, one value for all
+ * rows, clamped to [0, hist_cap]: n.  Positions >= n of hist are never read.  *min_len: a device int64; min_len may be null.
+ * Rules, per row; h = the row's first n history tokens, x = the row's logits as stored:
+ *   1. repetition penalty p, applied when p != 1: once for every DISTINCT token t in h with 0 <= t < vocab - a token that occurs several
+ *      times is still penalised exactly once - x_t becomes  x_t < 0 ? x_t * p : x_t * rp,  rp = 1.0f / p computed once on the host in
+ *      fp32; the product is computed in fp32 and rounded once to the dtype, round to nearest even.  (transformers divides where this
+ *      multiplies by the reciprocal: the results differ by at most one fp32 ulp, and this one is reproducible bit for bit.)  A NaN x_t
+ *      keeps its bits.
+ *   2. no-repeat n-gram of size g, applied when g >= 1 and n >= g: for every i in [0, n - g] with h[i .. i+g-2] == h[n-g+1 .. n-1] the
+ *      token h[i+g-1] gets -inf, if it lies in [0, vocab).  With g = 1 every token of h is banned.  Tokens outside [0, vocab) still take
+ *      part in the comparisons.
+ *   3. minimum length: if eos >= 0, min_len is not null and n < *min_len, x_eos = -inf.
+ *   4. bans win over the penalty.  Every entry not named above keeps its bits; NaN stays NaN under the penalty; nothing outside
+ *      [0, vocab) of a row is written.
+ * With p == 1, g == 0 and rule 3 off (eos < 0 or min_len null) the call returns FF_OK and launches nothing.
+ * FF_ERR_SHAPE: null logits, hist or hist_len; rows <= 0, vocab <= 0, ld < vocab; hist_cap < 1, hist_ld < hist_cap; p not positive and
+ * finite; g < 0; eos outside [-1, vocab).  FF_ERR_UNSUPPORTED: another dtype, hist_cap > FF_LOGITS_HIST_MAX.
+ * ------------------------------------------------------------------------------------------------------ */
+#define FF_LOGITS_HIST_MAX 4096
+int ff_logits_process(int dtype, int rows, int vocab, long long ld, void* logits,
+                      const long long* hist, long long hist_ld, long long hist_cap, const long long* hist_len,
+                      float repetition_penalty, int no_repeat_ngram_size, int eos, const long long* min_len,
+                      ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * QuickGELU of the CLIP vision tower, y = x * sigmoid(1.702 x) (transformers.activations.QuickGELUActivation, selected by
