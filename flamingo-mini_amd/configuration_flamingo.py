@@ -8,6 +8,9 @@ Extra, optional key understood by this implementation only (stored like any othe
     backbone_overrides (dict): {'lm': {...}, 'clip': {...}} keyword overrides of those random-init backbone configs.
     backbone_op_substitutions (bool): default False = the frozen CLIP / LM stay exactly as Hugging Face builds them (stock
     PyTorch-ROCm); True swaps three ops inside them for result-identical faster forms (backbones.py).
+    label_smoothing (float in [0, 1]), z_loss (float >= 0): the regularisers of the training loss that forward(labels=...) uses when
+    its arguments of the same names are None: per scored token  lse - (1 - eps) x_t - eps mean(x) + z_loss lse^2.  Absent = 0 = the plain
+    cross-entropy.  They apply in eval() too: pass label_smoothing=0.0, z_loss=0.0 to forward() for the plain evaluation loss.
 """
 from __future__ import annotations
 

@@ -150,6 +150,8 @@ _SIGNATURES = {
     "ff_quick_gelu_bwd": (_I, [_I, C.c_longlong, _P, _P, _P, _P]),
     "ff_shifted_ce_fwd": (_I, [_I, _I, _I, _I, _P, _P, C.c_longlong, _P, _P, _P]),
     "ff_shifted_ce_bwd": (_I, [_I, _I, _I, _I, _P, _P, C.c_longlong, _P, _P, _P, _P]),
+    "ff_shifted_ce_fwd_reg": (_I, [_I, _I, _I, _I, _P, _P, C.c_longlong, _P, _P, C.c_float, C.c_float, _P]),
+    "ff_shifted_ce_bwd_reg": (_I, [_I, _I, _I, _I, _P, _P, C.c_longlong, _P, _P, _P, C.c_float, C.c_float, _P]),
     "ff_adamw_step": (_I, [C.POINTER(AdamWDesc), _P, _P, _P, _P, _P, _P]),
     "ff_adamw_step_mixed": (_I, [C.POINTER(AdamWDesc), _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ff_adamw_step_clipped": (_I, [C.POINTER(AdamWDesc), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

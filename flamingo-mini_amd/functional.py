@@ -875,16 +875,21 @@ def stochastic_round_bf16(x: torch.Tensor, seed: int = 0, stream_id: int = 0, st
 # ----------------------------------------------------------------------------------------------------
 class _ShiftedCEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, ignore_index):
+    def forward(ctx, logits, labels, ignore_index, label_smoothing=0.0, z_loss=0.0):
         lib = ffi.lib()
         logits = logits.contiguous()
         labels = labels.contiguous().to(torch.int64)
         b, L, V = logits.shape
         rows = _new(b * (L - 1), torch.float32, logits.device)
         lse = _new_like(rows)
-        ffi.check(lib.ff_shifted_ce_fwd(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ignore_index,
-                                        rows.data_ptr(), lse.data_ptr(), ffi.stream_handle(logits.device)), "ff_shifted_ce_fwd")
-        ctx.ignore_index = ignore_index
+        if label_smoothing == 0.0 and z_loss == 0.0:
+            ffi.check(lib.ff_shifted_ce_fwd(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ignore_index,
+                                            rows.data_ptr(), lse.data_ptr(), ffi.stream_handle(logits.device)), "ff_shifted_ce_fwd")
+        else:
+            ffi.check(lib.ff_shifted_ce_fwd_reg(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ignore_index,
+                                                rows.data_ptr(), lse.data_ptr(), label_smoothing, z_loss, ffi.stream_handle(logits.device)),
+                      "ff_shifted_ce_fwd_reg")
+        ctx.ignore_index, ctx.label_smoothing, ctx.z_loss = ignore_index, label_smoothing, z_loss
         ctx.save_for_backward(logits, labels, lse)
         return rows
 
@@ -901,16 +906,38 @@ class _ShiftedCEFn(torch.autograd.Function):
         else:
             dlogits = _new_like(logits)
         g = grad_rows.contiguous().float()
-        ffi.check(lib.ff_shifted_ce_bwd(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ctx.ignore_index,
-                                        lse.data_ptr(), g.data_ptr(), dlogits.data_ptr(), ffi.stream_handle(logits.device)), "ff_shifted_ce_bwd")
-        return dlogits, None, None
+        if ctx.label_smoothing == 0.0 and ctx.z_loss == 0.0:
+            ffi.check(lib.ff_shifted_ce_bwd(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ctx.ignore_index,
+                                            lse.data_ptr(), g.data_ptr(), dlogits.data_ptr(), ffi.stream_handle(logits.device)), "ff_shifted_ce_bwd")
+        else:
+            ffi.check(lib.ff_shifted_ce_bwd_reg(ffi.dtype_code(logits.dtype), b, L, V, logits.data_ptr(), labels.data_ptr(), ctx.ignore_index,
+                                                lse.data_ptr(), g.data_ptr(), dlogits.data_ptr(), ctx.label_smoothing, ctx.z_loss,
+                                                ffi.stream_handle(logits.device)), "ff_shifted_ce_bwd_reg")
+        return dlogits, None, None, None, None
 
 
-def shifted_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, reduction: str = "mean", ignore_index: int = -100) -> torch.Tensor:
+def check_loss_regularisers(label_smoothing, z_loss) -> Tuple[float, float]:
+    """(label_smoothing, z_loss) as floats; ValueError unless 0 <= label_smoothing <= 1 and z_loss >= 0 and finite (NaN is refused)"""
+    eps, zl = float(label_smoothing), float(z_loss)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1], got {label_smoothing!r}")
+    if not 0.0 <= zl < float("inf"):
+        raise ValueError(f"z_loss must be >= 0 and finite, got {z_loss!r}")
+    return eps, zl
+
+
+def shifted_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, reduction: str = "mean", ignore_index: int = -100,
+                          label_smoothing: float = 0.0, z_loss: float = 0.0) -> torch.Tensor:
     """F.cross_entropy(logits[..., :-1, :].reshape(-1, V), labels[..., 1:].reshape(-1), reduction=reduction) in two fused passes
-    (fp32 math).  logits (b, L, V) float32 / bfloat16 on the GPU, labels (b, L) integer."""
+    (fp32 math).  logits (b, L, V) float32 / bfloat16 on the GPU, labels (b, L) integer.
+    label_smoothing = eps in [0, 1] and z_loss = zeta >= 0 ride on the same two passes: per scored row
+        lse - (1 - eps) x_t - eps mean(x) + zeta lse^2
+    which with zeta = 0 is F.cross_entropy(label_smoothing=eps) and HF's LabelSmoother(epsilon=eps).  A -inf logit makes the row's loss
+    +inf when eps > 0, as in torch; its gradient stays finite.  Both are launch constants (Python floats, not tensors): a captured graph
+    keeps the values it was captured with.  With both 0 (the default) the plain kernels run and give the bits they always gave."""
+    eps, zl = check_loss_regularisers(label_smoothing, z_loss)
     ffi.require_cuda(logits, labels)
-    rows = _ShiftedCEFn.apply(logits, labels, ignore_index)
+    rows = _ShiftedCEFn.apply(logits, labels, ignore_index, eps, zl)
     if reduction == "none":
         return rows
     if reduction == "sum":

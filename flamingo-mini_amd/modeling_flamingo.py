@@ -177,8 +177,16 @@ class FlamingoBaseModel(ABC, PreTrainedModel):
     # ---- forward (reference :183-306) ----
     def forward(self, input_ids=None, attention_mask=None, media_locations=None, pixel_values=None, visual_features=None,
                 head_mask=None, inputs_embeds=None, use_cache: bool = False, past_key_values=None, return_dict: bool = True,
-                labels=None, loss_reduction: str = "mean", text_time=None, **kwargs) -> CausalLMOutputWithPast:
+                labels=None, loss_reduction: str = "mean", text_time=None, label_smoothing: Optional[float] = None,
+                z_loss: Optional[float] = None, **kwargs) -> CausalLMOutputWithPast:
+        """label_smoothing (eps in [0, 1]) and z_loss (zeta >= 0) regularise the loss, per scored token
+            lse - (1 - eps) x_t - eps mean(x) + zeta lse^2           (functional.shifted_cross_entropy)
+        None takes the optional config keys `label_smoothing` / `z_loss` (0 when absent), so loops that call model(**batch) - HF Trainer,
+        GraphedTrainStep, PiecewiseGraphedTrainStep - pick them up from the config.  They are launch constants: a captured step keeps the
+        values it was captured with.  The loss is the same in eval(): pass label_smoothing=0.0, z_loss=0.0 for the plain evaluation loss."""
         assert return_dict, "can only use return_dict=True at the moment!"
+        eps, zeta = F.check_loss_regularisers(getattr(self.config, "label_smoothing", 0.0) if label_smoothing is None else label_smoothing,
+                                              getattr(self.config, "z_loss", 0.0) if z_loss is None else z_loss)
         assert (input_ids is None) != (inputs_embeds is None), "you must pass either input_ids or inputs_embeds!"
         ref = input_ids if input_ids is not None else inputs_embeds
         batch_size, seq_length = ref.shape[:2]
@@ -248,12 +256,26 @@ class FlamingoBaseModel(ABC, PreTrainedModel):
         loss = None
         if labels is not None:   # tokens < n predict n (reference :288-298)
             if logits.is_cuda and logits.dtype in (torch.float32, torch.bfloat16) and logits.ndim == 3 and seq_length > 1:
-                loss = F.shifted_cross_entropy(logits, labels, reduction=loss_reduction)      # two fused passes over the logits
+                loss = F.shifted_cross_entropy(logits, labels, reduction=loss_reduction, label_smoothing=eps, z_loss=zeta)      # two fused passes over the logits
             else:   # host-side / exotic dtypes: the stock op (the loss is not part of the accelerated fusion path)
                 flat = logits[..., :-1, :].contiguous().view(-1, logits.size(-1))
                 if flat.dtype in (torch.bfloat16, torch.float16):
                     flat = flat.float()
-                loss = TF.cross_entropy(flat, labels[..., 1:].contiguous().view(-1), reduction=loss_reduction)
+                target = labels[..., 1:].contiguous().view(-1)
+                if eps == 0.0 and zeta == 0.0:
+                    loss = TF.cross_entropy(flat, target, reduction=loss_reduction)
+                else:   # the same definition as the fused path: the z term per scored token, under the same reduction
+                    rows = TF.cross_entropy(flat, target, reduction="none", label_smoothing=eps)
+                    if zeta != 0.0:
+                        rows = rows + torch.where(target != -100, zeta * torch.logsumexp(flat, dim=-1).square(), torch.zeros_like(rows))
+                    if loss_reduction == "none":
+                        loss = rows
+                    elif loss_reduction == "sum":
+                        loss = rows.sum()
+                    elif loss_reduction == "mean":
+                        loss = rows.sum() / (target != -100).sum()
+                    else:
+                        raise ValueError(f"unknown reduction {loss_reduction}")
 
         return CausalLMOutputWithPast(
             loss=loss, logits=logits,
@@ -598,8 +620,10 @@ class FlamingoModel(PreTrainedModel):
 
     def forward(self, input_ids=None, attention_mask=None, media_locations=None, pixel_values=None, visual_features=None,
                 head_mask=None, inputs_embeds=None, use_cache: bool = False, past_key_values=None, return_dict: bool = True,
-                labels=None, loss_reduction: str = "mean", **kwargs) -> CausalLMOutputWithPast:
-        return self.flamingo(input_ids=input_ids, attention_mask=attention_mask, media_locations=media_locations,
+                labels=None, loss_reduction: str = "mean", label_smoothing: Optional[float] = None, z_loss: Optional[float] = None,
+                **kwargs) -> CausalLMOutputWithPast:
+        """label_smoothing / z_loss: see FlamingoBaseModel.forward (None = the config's optional keys, 0 when absent)."""
+        return self.flamingo(label_smoothing=label_smoothing, z_loss=z_loss,input_ids=input_ids, attention_mask=attention_mask, media_locations=media_locations,
                              pixel_values=pixel_values, visual_features=visual_features, head_mask=head_mask,
                              inputs_embeds=inputs_embeds, use_cache=use_cache, past_key_values=past_key_values,
                              return_dict=return_dict, labels=labels, loss_reduction=loss_reduction, **kwargs)

@@ -20,6 +20,7 @@
  *   ff_text_time             media_locations.cumsum(dim=-1)               flamingo_mini/gated_cross_attention.py:97
  *   ff_quick_gelu_fwd/bwd    CLIP MLP activation (QuickGELU)               transformers CLIPMLP via modeling_flamingo.py:70-78
  *   ff_shifted_ce_fwd/bwd    shifted F.cross_entropy on the logits        flamingo_mini/modeling_flamingo.py:288-298
+ *   ff_shifted_ce_fwd/bwd_reg  the same with label smoothing and z-loss   HF Trainer --label_smoothing_factor (trainer_pt_utils.LabelSmoother)
  *   ff_adamw_step            torch AdamW over parameters_trainable()      training/train.sh:10-13, modeling_flamingo.py:132-138
  * The primitive entry points (ff_gemm, ff_layernorm_*, ff_attention_*, ff_rows_reduce, ff_gate_grad) are the
  * kernels those are built from; they are exported so each can be parity-tested on its own.
@@ -497,6 +498,20 @@ int ff_shifted_ce_fwd(int dtype, int batch, int seq, int vocab, const void* logi
                       float* loss_row, float* lse, ff_stream_t stream);
 int ff_shifted_ce_bwd(int dtype, int batch, int seq, int vocab, const void* logits, const long long* labels, long long ignore_index,
                       const float* lse, const float* grad_row, void* dlogits, ff_stream_t stream);
+/* Label smoothing and z-loss in the same two passes (added under ABI 6).  eps = label_smoothing in [0, 1], zeta = z_loss >= 0 and finite;
+ * anything else (NaN included) returns FF_ERR_UNSUPPORTED before any launch.  Per scored row, fp32 math on the logits x as stored:
+ *   fwd: lse[r] as above, unchanged;   loss_row[r] = lse - (1 - eps) x_t - eps mean_c(x_c) + zeta lse^2
+ *        (zeta = 0: F.cross_entropy(label_smoothing=eps) on the shifted logits and labels, HF LabelSmoother(epsilon=eps))
+ *   bwd: dlogits[b,i,c] = grad_row[r] * (p_c (1 + 2 zeta lse) - (1 - eps) [c == t] - eps / vocab),   p_c = exp(x_c - lse)
+ * Ignored rows (loss 0, gradient row exactly 0), the last position (gradient row exactly 0) and a label outside [0, vocab) (NaN loss, NaN
+ * row, nothing read out of bounds) are as in the plain entry points.  -inf logits are as in torch: with eps > 0 the row's loss is +inf
+ * (the mean of -log p is), its gradient stays finite, -eps / vocab * grad_row at the -inf columns; with eps = 0 everything stays finite.
+ * No atomics: the same bits on every run.  With eps = 0 and zeta = 0 the plain kernels are launched: the bits of ff_shifted_ce_fwd/bwd.
+ * The two values are launch constants: a captured graph keeps the ones it was captured with. */
+int ff_shifted_ce_fwd_reg(int dtype, int batch, int seq, int vocab, const void* logits, const long long* labels, long long ignore_index,
+                          float* loss_row, float* lse, float label_smoothing, float z_loss, ff_stream_t stream);
+int ff_shifted_ce_bwd_reg(int dtype, int batch, int seq, int vocab, const void* logits, const long long* labels, long long ignore_index,
+                          const float* lse, const float* grad_row, void* dlogits, float label_smoothing, float z_loss, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Token selection for sampled decoding (added under ABI 6): temperature, top-k and nucleus (top-p) filtering and the draw, one launch, no
