@@ -386,3 +386,76 @@ def quick_gelu_bound_ok(got, ref, terms, storage_dtype, c=None):
 
 def quick_gelu_excess(got, ref, terms, storage_dtype):
     return _excess(got, ref, terms, 0.5 * _ulp(_t64(ref).reshape(-1), storage_dtype))
+
+
+# ---- the attention core, element by element (tests/test_hip_attention_bounds.py; the checkers' own tests: tests/test_attn_cases.py) ----
+# rel() and rel_rows() at 5e-6 / 8e-3 hold a row's L2 norm: one wrong key tile of one row, an lse that is off, a zero row that holds 1e-30
+# or a stride used for the wrong tensor in one head all hide inside them.  attn_cases.attention_ref gives every output of the three kernels
+# in float64 from what they saw, with the size of the terms each rounding error is proportional to; attn_bound_ok holds every element:
+#   lse:  |lse - lse*| <= c_l 2^-24 (1 + |lse*| + sum_j p_ij a_ij)                     a_ij = sum_d |q_id| |k_jd|, the size of a score's terms
+#   o:    1/2 ulp_T(o*) + u_P sum_j p_ij |v_jd| + c_o 2^-24 (sum_j w_ij |v_jd| + |o*_id| sum_j w_ij) + 2^-126 sum_j |v_jd|
+#   dV:   1/2 ulp_T + u_P sum_i p_ij |dO_id| + c_g 2^-24 sum_i w_ij |dO_id| + 2^-126 sum_i |dO_id|
+#   dQ:   1/2 ulp_T + u_P sum_j |ds_ij| |k_jd| + (1 + u_P) u_T (sum_d |dO_id o*_id|) sum_j p_ij |k_jd| + c_g 2^-24 sum_j g_ij |k_jd|
+#         + 2^-126 sum_j (1 + |dp_ij| + |D_i|) |k_jd|
+#   dK:   the dQ bound with q for k and the sums over i
+# w_ij = p_ij (1 + a_ij + |s_ij - lse*_i|): the rounding of the score and of the exponent's argument reach p in proportion to it;
+# g_ij = p_ij (|dp_ij| + |D_i|)(1 + a_ij + |s_ij - lse*_i|) + p_ij (b_ij + sum_d |dO_id o*_id|), b_ij = sum_d |dO_id| |v_jd|: the same for
+# ds = p (dp - D), plus the rounding of dp and of D.  The sums run over the keys a row may see (over the rows that may see a key).
+# u_P: P and dS are rounded to bf16 before the second product (0 in fp32); u_T: D = rowsum(dO . O) is taken from the STORED O (2^-24 in
+# fp32), and dS is rounded after that D went in (the 1 + u_P).  Both are 2^-8 in bf16, the format's unit roundoff (8 significant bits: half
+# a spacing of 2^-7 at the bottom of a binade).  With 2^-9 the bf16 restatement itself is up to 1.15 x its bound (d v of bf16-dh32-64x130-scales:
+# error 0.119 = half an ulp of the result, 0.0625, + 0.057 from the rounded P, where 2^-9 sum p |dO| allows 0.042).
+# The 2^-126 terms: __expf is v_exp_f32, which returns 0 below 2^-126, so a probability (or a rescale factor alpha) that small is lost
+# whole - an absolute error of up to 2^-126 per key (query) of the sum, however small the sum itself is; in bf16 a dS below 2^-126 has
+# fewer than eight bits left: the "1 +".  The sharp cases put the second-best score 95 below the best, p = 5e-42: d v and d k of a key
+# no row favours are 1e-41 exactly and 0 from the kernel.  Without the terms the fp32 restatement is 85138 (d v) and 82137 (d k) roundings
+# over at f32-dh128-130x200-sharp-rows; with them no case is above 6.81.
+# Where every term is zero - a text_time = 0 row's o and dq, a uniform row's dq, the dk of an image no token looks at - the bound is 0:
+# the kernel must store an exact zero.  A zero row's lse must be the kernel's sentinel 1e30 (exp(s - 1e30) = 0 whatever the score).
+# c_l, c_o, c_g: measured, not derived (tools/attn_c.py, on the CPU): 4 x the worst excess of the float32 / bf16 restatements of the kernels
+# (attn_cases.attn_fwd_f32, attn_bwd_f32: 64-row tiles, block_range's tile skipping, the running (m, lsum) per lane with the alpha
+# rescale, acc * (1 / lsum), exp(s - L) from the stored lse, D from the rounded O) over attention_ref, at exactly the inputs of
+# tests/test_hip_attention_bounds.py; the factor 4 as for ADAMW_C: the device's __expf / __logf, the MFMA accumulation order and FMA
+# contraction cannot be shown on the CPU.  Worst excess: lse 5.77 (f32-dh128-130x200-sharp-rows: scores of 300, a_ij the whole of the
+# bound) -> c_l = 4 x 5.77; o 5.48 (f32-dh128-64x130-tied) -> c_o = 4 x 5.48; d v 6.81 (f32-dh64-media-nv72x3-sharp-rows), d k 5.35
+# (f32-dh128-64x130-offset+), d q 4.41 (f32-dh128-65x63-offset+) -> c_g = 4 x 6.81.  In bf16 the fixed terms cover everything but lse
+# (<= 3.3).
+# On the MI355X (worst error / bound per checker, the [elem] entries of an FF_TOL_REPORT run of tests/test_hip_attention_bounds.py):
+#   fp32: lse 0.26 (f32-dh128-64x130-sharp-rows), o 0.25 (f32-dh128-65x63-tied), d q 0.15, d k 0.20, d v 0.19 (the offset cases at dim_head
+#   128) - the same cases that give the restatement's worst figures, at the 1 / 4 the factor leaves;
+#   bf16: lse 0.11, o 0.81 (bf16-dh128-65x63-tied), d q 0.51, d k 0.77, d v 0.86 (the scales cases at 64x130): results beside a rounding tie,
+#   where half a storage ulp and the rounded P are nearly all of the bound.  No device figure is above 1; the kernels needed no change.
+ATTN_C_L = 23.1
+ATTN_C_O = 21.9
+ATTN_C_G = 27.2
+ATTN_U_P = {torch.bfloat16: 2.0 ** -8, torch.float32: 0.0}
+ATTN_U_T = {torch.bfloat16: 2.0 ** -8, torch.float32: 2.0 ** -24}
+_ATTN_C = {"lse": "ATTN_C_L", "o": "ATTN_C_O", "dq": "ATTN_C_G", "dk": "ATTN_C_G", "dv": "ATTN_C_G"}
+
+
+def _attn_parts(what, ref, storage_dtype):
+    """(fixed, scaled): the part of the bound that does not carry the constant and the terms one float32 rounding is proportional to;
+    both exactly 0 where no term reaches the element."""
+    r = _t64(ref[what])
+    if what == "lse":
+        return torch.zeros_like(r), _t64(ref["t_lse"])
+    t, pu, fl = _t64(ref["t_" + what]), _t64(ref["pu_" + what]), _t64(ref["fl_" + what])
+    fixed = 0.5 * _ulp(r, storage_dtype) + ATTN_U_P[storage_dtype] * pu + 2.0 ** -126 * fl
+    if what in ("dq", "dk"):
+        fixed = fixed + (1.0 + ATTN_U_P[storage_dtype]) * ATTN_U_T[storage_dtype] * _t64(ref["ut_" + what])     # dS is rounded after D went in
+    return torch.where(t + pu + fl == 0, torch.zeros_like(fixed), fixed), t
+
+
+def attn_bound_ok(what, got, ref, storage_dtype, c=None):
+    """One output (what = "lse", "o", "dq", "dk", "dv") of the attention kernels against attn_cases.attention_ref's dict, element by
+    element, nothing excluded, NaN = inf.  Returns (ok, worst error / bound, index of that element in the output's own shape)."""
+    c = globals()[_ATTN_C[what]] if c is None else c
+    fixed, t = _attn_parts(what, ref, storage_dtype)
+    worst, i = _elem_ratio(got, ref[what], fixed + c * 2.0 ** -24 * t)
+    _report("elem", worst)
+    return worst <= 1.0, worst, tuple(int(x) for x in np.unravel_index(i, tuple(np.shape(ref[what]))))
+
+
+def attn_excess(what, got, ref, storage_dtype):
+    fixed, t = _attn_parts(what, ref, storage_dtype)
+    return _excess(got, ref[what], t, fixed)
