@@ -1,0 +1,540 @@
+"""Decoding for FlamingoModel.generate(): the option tuples, the routing rule, the fixed-shape sessions (one class per strategy) and the
+dynamic loops.  Nothing here knows the model classes: a session reads `model.flamingo` (its `lm_family`, its LM config, its forward), the
+dynamic loops take the model's `_decode_step` / `_reorder_cache` as callables.  modeling_flamingo.py keeps thin methods that delegate here.
+"""
+from __future__ import annotations
+
+import weakref
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import functional as F
+from .graphs import _prepared_capture_stream
+
+
+# ---- options: NamedTuples, so they compare and hash equal to the plain tuples they replaced (session keys, tests, tools) ----
+Sampling = NamedTuple("Sampling", [("temperature", float), ("top_k", int), ("top_p", float)])
+Beams = NamedTuple("Beams", [("nb", int), ("early_stopping", bool), ("length_penalty", float)])
+
+
+class Processors(NamedTuple):
+    repetition_penalty: float
+    no_repeat_ngram_size: int
+    min_length: int
+    min_new_tokens: int
+
+    def min_len(self, L0: int) -> int:
+        """The length below which eos is banned, for a prompt of L0 tokens."""
+        return max(self.min_length, L0 + self.min_new_tokens)
+
+    def given(self):
+        """The names of the arguments that are not at their off value."""
+        return [n for n, v, off in zip(self._fields, self, (1, 0, 0, 0)) if v != off]
+
+
+def _repeat_leading(t: torch.Tensor, m: int) -> torch.Tensor:
+    """'n ... -> (n m) ...' (each row repeated m times, as beam search does with input_ids)."""
+    return t.repeat_interleave(m, dim=0)
+
+
+# ---- generate(): argument checks and the static / dynamic decision ----
+def check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos) -> Optional[Processors]:
+    """The argument checks of generate(), in its order.  Returns the logits processors, None when every one is off (exactly the paths
+    without them)."""
+    if unsupported:
+        raise TypeError(f"generate(): unsupported generation arguments {sorted(unsupported)}")
+    if not use_cache:
+        raise ValueError("generate() always decodes with the cross-attention / LM caches (use_cache=True)")
+    if isinstance(repetition_penalty, bool) or not isinstance(repetition_penalty, (int, float)) or not 0 < repetition_penalty < float("inf"):
+        raise ValueError(f"generate(): repetition_penalty must be a positive, finite number (1 = off), got {repetition_penalty!r}")
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_length", min_length), ("min_new_tokens", min_new_tokens)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"generate(): {name} must be an integer >= 0 (0 = off), got {v!r}")
+    if (min_length > 0 or min_new_tokens > 0) and eos is None:
+        raise ValueError("generate(): min_length / min_new_tokens need eos_token_id")
+    procs = Processors(float(repetition_penalty), int(no_repeat_ngram_size), int(min_length), int(min_new_tokens))
+    return procs if procs.given() else None
+
+
+def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_family, L0, max_length, ids_is_int64, procs_on, procs_given=()):
+    """Which path a generate() call takes: "static" (a _DecodeSession) or "dynamic" (dynamic_decode / beam_search), from plain values only.
+    `static_decode` is generate()'s argument (None, True, False), `model_default` the model's attribute, `procs_given` the processor
+    arguments' names for the TypeError on CPU tensors.  Greedy decoding takes the static path by default on the GPU; sampling and beam search
+    only when static_decode=True is passed, and then they need GPU tensors: their kernels have no CPU form."""
+    def need_gpu():                     # what ffi.require_cuda raises for a CPU tensor
+        if not is_cuda:
+            F.ffi.require_cuda(torch.empty(0))
+
+    if procs_on and not is_cuda:        # GPU tensors only: on CPU tensors the processors stay what they were, unsupported
+        if static_decode:
+            need_gpu()
+        raise TypeError(f"generate(): unsupported generation arguments {list(procs_given)} on CPU tensors (the logits processors run on the GPU only)")
+    if num_beams > 1 and do_sample:
+        raise ValueError("beam search with sampling is not implemented")
+    on_request = num_beams > 1 or do_sample                                   # static only when static_decode=True is passed
+    if on_request and static_decode:
+        need_gpu()
+    if static_decode is None:
+        static_decode = is_cuda and model_default and not on_request
+    static_ok = lm_family is not None and L0 + 1 < max_length and num_beams <= F.ffi.BEAM_MAX and (not procs_on or (ids_is_int64 and max_length <= F.ffi.LOGITS_HIST_MAX))
+    return "static" if static_decode and static_ok else "dynamic"
+
+
+# ---- logits rules of the dynamic loops, in torch (FlamingoModel._filter_logits / ._process_logits) ----
+def filter_logits(logits, temperature, top_k, top_p):
+    """temperature / top-k / nucleus filtering as in transformers' logits warpers."""
+    if temperature != 1.0:
+        logits = logits / temperature
+    if top_k and top_k > 0:
+        kth = logits.topk(min(top_k, logits.shape[-1]), dim=-1).values[..., -1, None]
+        logits = logits.masked_fill(logits < kth, float("-inf"))
+    if top_p < 1.0:
+        srt, idx = logits.sort(dim=-1, descending=True)
+        cum = srt.softmax(-1).cumsum(-1)
+        drop = cum - srt.softmax(-1) >= top_p               # keep the smallest prefix whose mass reaches top_p
+        logits = logits.masked_fill(drop.scatter(-1, idx, drop), float("-inf"))
+    return logits
+
+
+def process_logits(logits, seqs, repetition_penalty, no_repeat_ngram_size, eos, min_len):
+    """Repetition penalty, no-repeat n-gram ban and minimum length on float32 `logits` (rows, V) against the sequences so far `seqs`
+    (rows, n): the rules of ff_logits_process (include/flamingo_fusion.h) restated in torch for the dynamic loops, with the same
+    x * (1.0f / p) where transformers divides.  Returns new logits."""
+    V, n = logits.shape[-1], seqs.shape[1]
+    seqs = seqs.long()
+    valid = (seqs >= 0) & (seqs < V)
+    out = torch.cat([logits, logits.new_zeros(logits.shape[0], 1)], dim=1)          # column V takes what out-of-range ids would write
+    if repetition_penalty != 1.0 and n > 0:
+        import numpy as np
+        p = np.float32(repetition_penalty)
+        idx = torch.where(valid, seqs, torch.full_like(seqs, V))
+        x = out.gather(1, idx)
+        out.scatter_(1, idx, torch.where(x < 0, x * float(p), x * float(np.float32(1.0) / p)))
+    if 1 <= no_repeat_ngram_size <= n:
+        g = no_repeat_ngram_size
+        win = seqs.unfold(1, g, 1)                                                   # (rows, n - g + 1, g)
+        match = (win[..., :g - 1] == seqs[:, None, n - g + 1:]).all(-1)
+        out.scatter_(1, torch.where(match & valid[:, g - 1:], win[..., -1], torch.full_like(win[..., -1], V)), float("-inf"))
+    if eos is not None and min_len is not None and n < min_len:
+        out[:, eos] = float("-inf")
+    return out[:, :V].contiguous()
+
+
+def _dynamic_processor(processors, eos, L0):
+    """(logits, sequences so far) -> logits for the dynamic loops: process_logits with the call's settings, the identity without processors."""
+    if processors is None:
+        return lambda x, s: x
+    p = Processors(*processors)
+    return lambda x, s: process_logits(x, s, p.repetition_penalty, p.no_repeat_ngram_size, eos, p.min_len(L0))
+
+
+def _pad_finished(nxt, finished, eos, pad):
+    """The eos rule of greedy and sampled decoding: a row that has finished takes `pad`, a row that chose `eos` is finished from now on
+    (`finished` is updated in place).  Returns the tokens to append."""
+    nxt = torch.where(finished, torch.full_like(nxt, pad), nxt)
+    finished.logical_or_(nxt == eos)
+    return nxt
+
+
+# ---- the static path: fixed-shape sessions ----
+# Decode sessions hold HIP graphs and raw parameter addresses: they live in a weak side table, not in the model's __dict__, so
+# copy.deepcopy(model) / pickling (EMA or evaluation copies) neither see nor try to copy them.  The table is keyed by the model and a
+# session refers to its model only WEAKLY (a strong reference from the value would keep the key - and with it the model, its static KV
+# cache and the captured graph - alive for ever): `del model` frees all of it.
+_DECODE_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+
+
+def _beam_finalize(state, L0, prompt_ids, nb, pad):
+    """The result of a beam search from the state block of ff_beam_step, on the host (numpy only; `state` = BeamState.to_host(), plus
+    "length" = the sequences' length after the last step, default: the whole history): per sequence the best finished hypothesis - or, when
+    the sequence is not done (the length limit), the best of the hypotheses and the open beams, normalised in float32 by len_norm[length],
+    the earlier entry on equal scores - as in the tail of beam_search.  Tokens are read back by following hist_parent
+    downwards from the entry's row; rows are padded with `pad` to the longest.  Returns (b, width) int64 on the CPU."""
+    import numpy as np
+    hist_tok, hist_parent, len_norm = state["hist_tok"], state["hist_parent"], state["len_norm"]
+    length, eos = int(state.get("length", hist_tok.shape[0])), int(state.get("eos", -1))
+    prompt = np.asarray(prompt_ids)
+
+    def backtrack(row, last):               # the tokens at positions L0 .. last of the beam that sat in `row` after the step that wrote `last`
+        toks = []
+        for p in range(last, L0 - 1, -1):
+            toks.append(int(hist_tok[p, row]))
+            row = int(hist_parent[p, row])
+        return toks[::-1]
+
+    out = []
+    for s in range(state["score"].shape[0]):
+        hyps = [(np.float32(state["hyp_score"][s, j]), (int(state["hyp_row"][s, j]), int(state["hyp_len"][s, j]) - 2, [eos]))
+                for j in range(int(state["n_hyp"][s]))]
+        if not state["done"][s]:
+            hyps += [(np.float32(state["score"][s, k]) / np.float32(len_norm[length]), (s * nb + k, length - 1, []))
+                     for k in range(nb) if state["score"][s, k] > -np.inf]
+        best = 0
+        for j in range(1, len(hyps)):
+            if hyps[j][0] > hyps[best][0]:
+                best = j
+        row, last, tail = hyps[best][1]
+        out.append([int(t) for t in prompt[s]] + backtrack(row, last) + tail)
+    width = max(len(o) for o in out)
+    return torch.tensor([o + [pad] * (width - len(o)) for o in out], dtype=torch.long)
+
+
+class _DecodeSession:
+    """Fixed-shape decoding for one (batch, max_length) shape: the LM keeps a transformers StaticCache of max_length positions, the
+    attention mask and the token buffer are preallocated, positions travel as a device tensor (`cache_position`), the cross-attention K / V
+    of the prompt step are copied into persistent buffers, and the text_time of a generated token is the prompt's last value (generated
+    tokens are never media tags).  A decode step then issues exactly the same work on the same addresses every time, so on the GPU it is
+    captured once into a HIP graph and replayed (the eager step is host-bound: 72 layers, ~800 launches of a few microseconds each).
+    If the capture raises (e.g. a host synchronisation inside the stock LM) the steps run eagerly.
+    This class is what the strategies share - the caches and buffers, the step, capture and replay, the prompt step and the loop of run().
+    How a token is chosen is the subclass's: _TokenSession (greedy, sampling) and _BeamSession supply _alloc, _begin, _history, _select,
+    _all_done and _result, and override neither _append nor run.
+    `processors` (a Processors) puts functional.process_logits (one launch, csrc/ff_logits.hip) in front of the selection of every strategy:
+    _append edits the step's logits in place against the strategy's token history (_history(), with `pos` as its length) and against
+    `min_len`, a device scalar _begin sets outside any capture.  A session without processors issues none of this."""
+
+    nb = 1                                 # rows per sequence
+
+    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None):
+        from transformers.cache_utils import StaticCache
+        self._model_ref = weakref.ref(model)
+        self.sampling, self.beams, self.processors = sampling, beams, processors
+        self.n_seq = b
+        b = b * self.nb
+        self.b, self.max_length, self.eos, self.graph_wanted = b, max_length, eos, graph
+        self.fill = pad if pad is not None else 0
+        self.lm_family = model.flamingo.lm_family
+        self.cache = StaticCache(config=model.flamingo.lm.config, max_cache_len=max_length)
+        self.ids_buf = torch.empty((b, max_length), dtype=ids_dtype, device=device)
+        self.am_buf = torch.empty((b, max_length), dtype=am_dtype, device=device)
+        self.pos = torch.zeros((1,), dtype=torch.long, device=device)          # position of `tok` (the token the next step consumes)
+        self.tok = torch.zeros((b, 1), dtype=ids_dtype, device=device)
+        self.tt_step = torch.zeros((b, 1), dtype=torch.int32, device=device)
+        self._alloc()
+        self.xattn_past = None                                                # persistent (k, v) per layer, filled by every prompt step
+        self.replay = None
+        self.capture_failed = False
+        self.param_ptrs = self._param_ptrs()                                   # what a captured graph reads: checked before every reuse
+
+    @property
+    def model(self):
+        m = self._model_ref()
+        if m is None:
+            raise RuntimeError("decode session used after its model was deleted")
+        return m
+
+    def _param_ptrs(self):
+        return tuple(p.data_ptr() for p in self.model.parameters())
+
+    def stale(self) -> bool:
+        """Parameters were re-allocated since this session was built (model.to() / .half(), ShardedAdamW moving them into flat buffers):
+        a captured graph would replay reads of freed memory."""
+        return self.param_ptrs != self._param_ptrs()
+
+    def _alloc_min_len(self):              # the processors' device scalar; subclasses call it from _alloc when they have processors
+        p = self.processors
+        self.min_len = torch.zeros((1,), dtype=torch.long, device=self.pos.device)
+        self.min_on = self.eos is not None and (p.min_length > 0 or p.min_new_tokens > 0)
+
+    def _append(self, logits):
+        """The single place that receives a step's unprocessed logits: the processors, in place, against the first `pos` tokens of every
+        row of the strategy's history, then the strategy's selection."""
+        p = self.processors
+        if p is not None:
+            F.process_logits(logits, self._history(), self.pos, p.repetition_penalty, p.no_repeat_ngram_size, self.eos if self.min_on else None, self.min_len if self.min_on else None)
+        self._select(logits)
+
+    def _positions(self, L0=None):
+        """How the LM family learns where a step's tokens sit without reading anything back to the host.  GPT-2 takes absolute cache
+        positions.  OPT numbers the ATTENDED tokens (cumsum of the attention mask, padding skipped - modeling_opt's own rule), and derives
+        that by slicing with the cache's length, which for a StaticCache is a device scalar (a host synchronisation: not capturable): the
+        decode step hands it `position_ids` instead - the token at `pos` is the (number of ones in the mask so far)-th attended one."""
+        if self.lm_family == "gpt2":
+            return {"cache_position": self.pos if L0 is None else torch.arange(L0, device=self.pos.device)}
+        if L0 is None:
+            return {"position_ids": self.am_buf.sum(1, keepdim=True).long() - 1}
+        return {}                       # the prompt step: an empty cache, OPT's own cumsum applies
+
+    def _step(self):
+        self.am_buf.index_fill_(1, self.pos, 1)
+        o = self.model.flamingo(input_ids=self.tok, attention_mask=self.am_buf, use_cache=True, past_key_values=(self.xattn_past, self.cache),
+                                text_time=self.tt_step, **self._positions())
+        self.pos.add_(1)
+        self._append(o.logits[:, -1])
+
+    @torch.no_grad()
+    def run(self, ids, ml, am, pixel_values, visual_features, generator=None):
+        L0, prompt_ids = ids.shape[1], ids
+        ids, ml, am, pixel_values, visual_features = self._begin(ids, ml, am, pixel_values, visual_features, generator)
+        self.cache.reset()
+        out = self.model.flamingo(input_ids=ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=(None, self.cache),
+                                  pixel_values=pixel_values, visual_features=visual_features, **self._positions(L0))
+        fresh = out.past_key_values[0]
+        if self.xattn_past is None:
+            self.xattn_past = tuple((torch.empty_like(k, memory_format=torch.contiguous_format), torch.empty_like(v, memory_format=torch.contiguous_format))
+                                    for k, v in fresh)
+        for (kb, vb), (k, v) in zip(self.xattn_past, fresh):
+            kb.copy_(k); vb.copy_(v)
+        self.tt_step.copy_(F.text_time(ml)[:, -1:])
+        self.ids_buf.fill_(self.fill)
+        self.ids_buf[:, :L0] = ids
+        self.am_buf.zero_()
+        self.am_buf[:, :L0] = am
+        self.pos.fill_(L0)
+        self._append(out.logits[:, -1])
+        remaining = self.max_length - L0 - 1
+        if self.graph_wanted and self.replay is None and not self.capture_failed and remaining > 1:
+            self._step()                                                      # eager once: lazy initialisation, allocator pools
+            remaining -= 1
+            try:
+                # captured on a stream whose sync buffer exists before the capture: an unprepared capture would keep the separate to_out
+                # launches where the eager steps exchange inside the fused launch (> 32 rows) - replay and eager steps must be the same work
+                self.capture_stream = _prepared_capture_stream(self.model)
+                g = torch.cuda.CUDAGraph()
+                torch.cuda.synchronize()
+                with torch.cuda.graph(g, stream=self.capture_stream):
+                    self._step()
+                self.graph, self.replay = g, g.replay
+            except Exception:                                                 # the steps run eagerly from here on (and in later calls)
+                torch.cuda.synchronize()
+                self.capture_failed = True
+        run_step = self.replay or self._step
+        i = 0
+        all_done = self._all_done()
+        while i < remaining:
+            run_step()
+            i += 1
+            if self.eos is not None and i % 16 == 0 and bool(all_done.all()):          # (a host sync: only every 16 tokens)
+                break
+        return self._result(L0, prompt_ids, self.max_length - remaining + i)
+
+
+class _TokenSession(_DecodeSession):
+    """Greedy and sampled decoding: one token per row and step, the eos bookkeeping of dynamic_decode.  Token-for-token equal to the
+    growing-cache loop when greedy (tests/test_model_plumbing.py).
+    `sampling` (a Sampling) makes it a SAMPLING session (GPU only): _select draws the token with functional.sample_tokens (one launch on
+    the logits in their own dtype, csrc/ff_sample.hip) instead of the argmax.  The random numbers of a whole call are drawn before the
+    prompt step, outside any capture, into `u_all` (max_length, b): row `pos` serves the token written at position `pos` and the captured
+    step picks it with a device-side index_select on `pos`, so the graph holds no random-number generation and eager and replayed steps
+    consume identical numbers.  The processors read `ids_buf`, which already is the sequence."""
+
+    def _alloc(self):
+        dev = self.pos.device
+        self.finished = torch.zeros(self.b, dtype=torch.bool, device=dev)
+        self.n_new = torch.zeros((), dtype=torch.long, device=dev)            # tokens appended while not every sequence had finished
+        if self.sampling is not None:
+            self.u_all = torch.zeros((self.max_length, self.b), dtype=torch.float32, device=dev)
+            self.nxt = torch.zeros((self.b,), dtype=torch.long, device=dev)
+        if self.processors is not None:
+            self._alloc_min_len()
+
+    def _begin(self, ids, ml, am, pixel_values, visual_features, generator):
+        if self.sampling is not None:
+            self.u_all.copy_(torch.rand((self.max_length, self.b), generator=generator, device=ids.device, dtype=torch.float32))
+        self.finished.zero_()
+        self.n_new.zero_()
+        if self.processors is not None:
+            self.min_len.fill_(self.processors.min_len(ids.shape[1]))
+        return ids, ml, am, pixel_values, visual_features
+
+    def _history(self):
+        return self.ids_buf
+
+    def _select(self, logits):             # choose, apply the eos bookkeeping, append at `pos`
+        if self.sampling is None:
+            nxt = logits.float().argmax(-1)
+        else:
+            nxt = F.sample_tokens(logits, self.u_all.index_select(0, self.pos).view(-1), *self.sampling, out=self.nxt)
+        alive = ~self.finished.all()
+        if self.eos is not None:
+            nxt = _pad_finished(nxt, self.finished, self.eos, self.fill)
+        self.tok.copy_(nxt[:, None])
+        self.ids_buf.index_copy_(1, self.pos, self.tok)
+        self.n_new.add_(alive.to(self.n_new.dtype))
+
+    def _all_done(self):
+        return self.finished
+
+    def _result(self, L0, prompt_ids, length):
+        return self.ids_buf[:, :L0 + int(self.n_new)].clone() if self.eos is not None else self.ids_buf.clone()
+
+
+class _BeamSession(_DecodeSession):
+    """Beam search (GPU only) for `b` sequences with `beams` (a Beams): every buffer and the LM cache are b * nb rows wide (row s * nb + k =
+    beam k of sequence s; the visual features are encoded once per sequence and repeated), and _select is functional.beam_step (selection
+    and all bookkeeping in a device state block, csrc/ff_beam.hip), functional.beam_gather (the static LM cache reordered in place by beam
+    index, live positions only) and tok <- next_tok.  The cross-attention K / V, the attention mask and text_time are equal within a
+    sequence's beams and are NOT reordered.  The result is read back once, after the loop (_beam_finalize).
+    The processors read `seq_buf` (b * nb, max_length), which follows the beams through the same in-place gather as the LM cache (viewed as
+    two 4-byte elements per id); a session without processors allocates no seq_buf."""
+
+    def __init__(self, model, b, *args, beams, **kw):
+        self.nb = beams.nb
+        super().__init__(model, b, *args, beams=beams, **kw)
+
+    def _alloc(self):
+        dev = self.pos.device
+        self.state = F.BeamState(self.n_seq, self.nb, self.max_length, dev, eos=self.eos, pad=self.fill, early_stopping=self.beams.early_stopping, length_penalty=self.beams.length_penalty)
+        self.cur_len = torch.zeros((1,), dtype=torch.long, device=dev)        # pos + 1: the length after the token beam_step chooses
+        self.lm_tensors = None                                                # keys / values of every StaticCache layer (allocated by the first prompt step)
+        if self.processors is not None:
+            self._alloc_min_len()
+            self.seq_buf = torch.full((self.b, self.max_length), self.fill, dtype=torch.long, device=dev)
+
+    def _begin(self, ids, ml, am, pixel_values, visual_features, generator):
+        if visual_features is None and pixel_values is not None:             # encoded once per sequence, repeated per beam
+            visual_features, pixel_values = self.model.flamingo.encode_resample_visuals(pixel_values), None
+        ids, ml, am = _repeat_leading(ids, self.nb), _repeat_leading(ml, self.nb), _repeat_leading(am, self.nb)
+        if visual_features is not None:
+            visual_features = _repeat_leading(visual_features, self.nb)
+        self.state.reset()
+        if self.processors is not None:
+            self.min_len.fill_(self.processors.min_len(ids.shape[1]))
+            self.seq_buf.fill_(self.fill)
+            self.seq_buf[:, :ids.shape[1]] = ids
+        return ids, ml, am, pixel_values, visual_features
+
+    def _history(self):
+        return self.seq_buf
+
+    def _select(self, logits):
+        if self.lm_tensors is None:
+            self.lm_tensors = [t for layer in self.cache.layers for t in (layer.keys, layer.values)]
+        torch.add(self.pos, 1, out=self.cur_len)
+        nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
+        F.beam_gather(self.lm_tensors, beam_idx, self.pos, self.nb)           # positions < pos are live: the cache rows follow their beams
+        if self.processors is not None:                                       # ... and so do the histories: an id is two 4-byte elements
+            F.beam_gather([self.seq_buf.view(torch.int32).view(self.b, 1, self.max_length, 2)], beam_idx, self.pos, self.nb)
+            self.seq_buf.index_copy_(1, self.pos, nxt[:, None])
+        self.tok.copy_(nxt[:, None])
+
+    def _all_done(self):
+        return self.state.done
+
+    def _result(self, L0, prompt_ids, length):    # one device-to-host copy; steps past the last `done` only wrote padding
+        host = self.state.to_host()
+        host["length"] = length
+        return _beam_finalize(host, L0, prompt_ids.cpu(), self.nb, self.fill).to(prompt_ids.device)
+
+
+def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, beams=None, processors=None):
+    """Greedy, sampled (`sampling`) or beam-search (`beams`) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches
+    and buffers plus, on the GPU, the captured HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, device,
+    eos, pad, graph, sampling, beams, processors) and reused by later calls, so only the first caption batch of a shape pays for the
+    capture.  A session whose model's parameters were re-allocated since (model.to(), ShardedAdamW) is rebuilt;
+    FlamingoModel.reset_decode_sessions() drops them all."""
+    b = ids.shape[0]
+    graph = ids.is_cuda and not model.training and model.decode_graph
+    sessions = _DECODE_SESSIONS.setdefault(model, {})
+    n_media = int(ml.sum(-1).max()) if visual_features is None and pixel_values is None else \
+        (visual_features.shape[1] if visual_features is not None else (pixel_values.shape[1] if pixel_values.ndim >= 5 else pixel_values.shape[0]))
+    key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams, processors)
+    sess = sessions.get(key)
+    if sess is not None and sess.stale():
+        sessions.pop(key)
+        sess = None
+    if sess is None:
+        if len(sessions) >= 4:                                                # a handful of shapes at most: each holds a KV cache and a graph
+            sessions.pop(next(iter(sessions)))
+        cls = _TokenSession if beams is None else _BeamSession
+        sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors)
+    return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator)
+
+
+# ---- the dynamic path: growing caches, one forward per step (the only path on CPU tensors, and what the sessions are tested against) ----
+def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, processors=None):
+    """Greedy or, with `sampling`, multinomial decoding over the cached decode path; `step` is FlamingoModel._decode_step."""
+    finished = torch.zeros(ids.shape[0], dtype=torch.bool, device=ids.device)
+    past, step_ids = None, ids
+    process = _dynamic_processor(processors, eos, ids.shape[1])
+    while ids.shape[1] < max_length:
+        logits, past = step(step_ids, ml, am, past, pixel_values, visual_features)
+        logits = process(logits, ids)
+        if sampling is not None:
+            nxt = torch.multinomial(filter_logits(logits, *sampling).softmax(-1), 1, generator=generator)[:, 0]
+        else:
+            nxt = logits.argmax(-1)
+        if eos is not None:
+            nxt = _pad_finished(nxt, finished, eos, pad)
+        ids = torch.cat([ids, nxt[:, None]], dim=1)
+        ml = torch.cat([ml, torch.zeros_like(ml[:, :1])], dim=1)
+        am = torch.cat([am, torch.ones_like(am[:, :1])], dim=1)
+        step_ids = ids[:, -1:]
+        if eos is not None and bool(finished.all()):
+            break
+    return ids
+
+
+def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None):
+    """Standard beam search over the cached decode path; `step` / `reorder_cache` are FlamingoModel._decode_step / ._reorder_cache.  The
+    prompt runs once per sequence; its caches are then replicated per beam (xattn K/V: repeat_interleave; LM cache:
+    Cache.batch_repeat_interleave) and re-ordered every step.  `processors` act on every step's logits before the log-softmax."""
+    b, L0 = ids.shape
+    dev = ids.device
+    process = _dynamic_processor(processors, eos, L0)
+    logits, past = step(ids, ml, am, None, pixel_values, visual_features)
+    logp = process(logits, ids).log_softmax(-1)
+    V = logp.shape[-1]
+    xattn_past, lm_past = past
+    xattn_past = tuple(tuple(_repeat_leading(t, nb) for t in kv) for kv in xattn_past)
+    if hasattr(lm_past, "batch_repeat_interleave"):
+        lm_past.batch_repeat_interleave(nb)
+    else:
+        lm_past = tuple(tuple(_repeat_leading(t, nb) for t in layer) for layer in lm_past)
+    past = (xattn_past, lm_past)
+    seqs = _repeat_leading(ids, nb)                                   # (b * nb, L)
+    ml, am = _repeat_leading(ml, nb), _repeat_leading(am, nb)
+    scores = torch.full((b, nb), float("-inf"), device=dev)
+    scores[:, 0] = 0.0                                                # all beams of a sequence start identical: only one may branch
+    logp = _repeat_leading(logp, nb)
+    done_hyps = [[] for _ in range(b)]                                # (normalised score, token list) per sequence
+    is_done = [False] * b
+    while True:
+        cand = (scores.reshape(-1, 1) + logp).reshape(b, nb * V)
+        top_s, top_i = cand.topk(2 * nb, dim=-1)
+        cur_len = seqs.shape[1] + 1
+        next_scores = torch.full((b, nb), float("-inf"), device=dev)
+        next_tok = torch.full((b, nb), pad if pad is not None else 0, dtype=torch.long, device=dev)
+        next_src = torch.arange(nb, device=dev).repeat(b, 1)
+        top_s_c, top_i_c = top_s.cpu(), top_i.cpu()
+        for bi in range(b):
+            if is_done[bi]:
+                continue
+            k = 0
+            for rank in range(2 * nb):
+                s_, i_ = float(top_s_c[bi, rank]), int(top_i_c[bi, rank])
+                beam, tok = i_ // V, i_ % V
+                if eos is not None and tok == eos:
+                    if rank < nb:
+                        done_hyps[bi].append((s_ / (cur_len ** length_penalty), seqs[bi * nb + beam].tolist() + [tok]))
+                    continue
+                next_scores[bi, k], next_tok[bi, k], next_src[bi, k] = s_, tok, beam
+                k += 1
+                if k == nb:
+                    break
+            if len(done_hyps[bi]) >= nb:
+                done_hyps[bi] = sorted(done_hyps[bi], key=lambda t: -t[0])[:nb]
+                best_open = float(next_scores[bi].max()) / (cur_len ** length_penalty)
+                if early_stopping or done_hyps[bi][-1][0] >= best_open:
+                    is_done[bi] = True
+        beam_idx = (next_src + torch.arange(b, device=dev)[:, None] * nb).reshape(-1)
+        seqs = torch.cat([seqs.index_select(0, beam_idx), next_tok.reshape(-1, 1)], dim=1)
+        scores = next_scores
+        if all(is_done) or seqs.shape[1] >= max_length:
+            break
+        past = reorder_cache(past, beam_idx)
+        ml = torch.cat([ml, torch.zeros_like(ml[:, :1])], dim=1)
+        am = torch.cat([am, torch.ones_like(am[:, :1])], dim=1)
+        logits, past = step(seqs[:, -1:], ml, am, past, None, None)
+        logp = process(logits, seqs).log_softmax(-1)
+    out = []
+    for bi in range(b):
+        hyps = list(done_hyps[bi])
+        if not is_done[bi]:                                           # length limit: the open beams count as hypotheses too
+            hyps += [(float(scores[bi, k]) / (seqs.shape[1] ** length_penalty), seqs[bi * nb + k].tolist()) for k in range(nb)
+                     if float(scores[bi, k]) > float("-inf")]
+        out.append(max(hyps, key=lambda t: t[0])[1])
+    width = max(len(o) for o in out)
+    fill = pad if pad is not None else 0
+    return torch.tensor([o + [fill] * (width - len(o)) for o in out], dtype=torch.long, device=dev)

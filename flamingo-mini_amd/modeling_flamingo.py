@@ -19,11 +19,12 @@ import torch.nn.functional as TF
 from transformers import PreTrainedModel
 from transformers.modeling_outputs import CausalLMOutputWithPast
 
+from . import decoding as D
 from . import functional as F
 from .backbones import load_language_model, load_vision_encoder
 from .configuration_flamingo import FlamingoConfig
+from .decoding import _DecodeSession, _beam_finalize, _repeat_leading      # noqa: F401  (importable from here, as before decoding.py)
 from .gated_cross_attention import ModifiedLMBlock
-from .graphs import _prepared_capture_stream
 from .perceiver_resampler import PerceiverResampler
 from .utils import get_common_prefix_length
 
@@ -40,11 +41,6 @@ def suppress_model_loading_warnings(suppress: bool = True):
         logger.setLevel(level)
 
 
-def _repeat_leading(t: torch.Tensor, m: int) -> torch.Tensor:
-    """'n ... -> (n m) ...' (each row repeated m times, as beam search does with input_ids)."""
-    return t.repeat_interleave(m, dim=0)
-
-
 def _add_eoc_row(base_lm) -> None:
     """One extra embedding row for <EOC> (reference :315, :343: resize_token_embeddings(vocab_size + 1)).  from_pretrained builds the model
     on the meta device first (transformers >= 5); the mean / covariance initialisation of the new row cannot run there and is pointless
@@ -58,6 +54,7 @@ class FlamingoBaseModel(ABC, PreTrainedModel):
 
     config_class = FlamingoConfig
     _supports_sdpa = True
+    lm_family: Optional[str] = None       # "gpt2" / "opt" on the subclasses the fixed-shape decode sessions know (decoding.py)
 
     def __init__(self, config: FlamingoConfig, suppress_warnings: bool = True):
         assert isinstance(config, FlamingoConfig)
@@ -287,6 +284,7 @@ class FlamingoGPT2(FlamingoBaseModel):
     # GPT2LMHeadModel ties lm_head to the token embedding; declared here so that save_pretrained (safetensors: no aliased tensors) writes the
     # embedding once and from_pretrained re-ties it (transformers >= 5 refuses to save undeclared shared tensors)
     _tied_weights_keys = {"lm_head.weight": "lm.wte.weight"}
+    lm_family = "gpt2"
 
     def __init__(self, config: FlamingoConfig):
         assert config.lm.startswith("gpt")
@@ -306,6 +304,7 @@ class FlamingoGPT2(FlamingoBaseModel):
 
 class FlamingoOPT(FlamingoBaseModel):
     _tied_weights_keys = {"lm_head.weight": "lm.decoder.embed_tokens.weight"}
+    lm_family = "opt"
 
     def __init__(self, config: FlamingoConfig):
         assert config.lm.startswith("facebook/opt")
@@ -321,244 +320,6 @@ class FlamingoOPT(FlamingoBaseModel):
 
     def get_modified_layers(self):
         return [layer for layer in self.lm.decoder.layers if isinstance(layer, ModifiedLMBlock)]
-
-
-# Decode sessions hold HIP graphs and raw parameter addresses: they live in a weak side table, not in the model's __dict__, so
-# copy.deepcopy(model) / pickling (EMA or evaluation copies) neither see nor try to copy them.  The table is keyed by the model and a
-# session refers to its model only WEAKLY (a strong reference from the value would keep the key - and with it the model, its static KV
-# cache and the captured graph - alive for ever): `del model` frees all of it.
-import weakref
-_DECODE_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-
-
-def _beam_finalize(state, L0, prompt_ids, nb, pad):
-    """The result of a beam search from the state block of ff_beam_step, on the host (numpy only; `state` = BeamState.to_host(), plus
-    "length" = the sequences' length after the last step, default: the whole history): per sequence the best finished hypothesis - or, when
-    the sequence is not done (the length limit), the best of the hypotheses and the open beams, normalised in float32 by len_norm[length],
-    the earlier entry on equal scores - as in the tail of FlamingoModel._beam_search.  Tokens are read back by following hist_parent
-    downwards from the entry's row; rows are padded with `pad` to the longest.  Returns (b, width) int64 on the CPU."""
-    import numpy as np
-    hist_tok, hist_parent, len_norm = state["hist_tok"], state["hist_parent"], state["len_norm"]
-    length, eos = int(state.get("length", hist_tok.shape[0])), int(state.get("eos", -1))
-    prompt = np.asarray(prompt_ids)
-
-    def backtrack(row, last):               # the tokens at positions L0 .. last of the beam that sat in `row` after the step that wrote `last`
-        toks = []
-        for p in range(last, L0 - 1, -1):
-            toks.append(int(hist_tok[p, row]))
-            row = int(hist_parent[p, row])
-        return toks[::-1]
-
-    out = []
-    for s in range(state["score"].shape[0]):
-        hyps = [(np.float32(state["hyp_score"][s, j]), (int(state["hyp_row"][s, j]), int(state["hyp_len"][s, j]) - 2, [eos]))
-                for j in range(int(state["n_hyp"][s]))]
-        if not state["done"][s]:
-            hyps += [(np.float32(state["score"][s, k]) / np.float32(len_norm[length]), (s * nb + k, length - 1, []))
-                     for k in range(nb) if state["score"][s, k] > -np.inf]
-        best = 0
-        for j in range(1, len(hyps)):
-            if hyps[j][0] > hyps[best][0]:
-                best = j
-        row, last, tail = hyps[best][1]
-        out.append([int(t) for t in prompt[s]] + backtrack(row, last) + tail)
-    width = max(len(o) for o in out)
-    return torch.tensor([o + [pad] * (width - len(o)) for o in out], dtype=torch.long)
-
-
-class _DecodeSession:
-    """Fixed-shape greedy decoding for one (batch, max_length) shape: the LM keeps a transformers StaticCache of max_length positions, the
-    attention mask and the token buffer are preallocated, positions travel as a device tensor (`cache_position`), the cross-attention K / V
-    of the prompt step are copied into persistent buffers, and the text_time of a generated token is the prompt's last value (generated
-    tokens are never media tags).  A decode step then issues exactly the same work on the same addresses every time, so on the GPU it is
-    captured once into a HIP graph and replayed (the eager step is host-bound: 72 layers, ~800 launches of a few microseconds each).
-    If the capture raises (e.g. a host synchronisation inside the stock LM) the steps run eagerly.  Token-for-token equal to the
-    growing-cache loop of FlamingoModel.generate (tests/test_model_plumbing.py).
-    `sampling` = (temperature, top_k, top_p) makes it a SAMPLING session (GPU only): _append draws the token with functional.sample_tokens
-    (one launch on the logits in their own dtype, csrc/ff_sample.hip) instead of the argmax.  The random numbers of a whole call are drawn
-    before the prompt step, outside any capture, into `u_all` (max_length, b): row `pos` serves the token written at position `pos` and the
-    captured step picks it with a device-side index_select on `pos`, so the graph holds no random-number generation and eager and replayed
-    steps consume identical numbers.
-    `beams` = (nb, early_stopping, length_penalty) makes it a BEAM-SEARCH session (GPU only) for `b` sequences: every buffer and the LM cache
-    are b * nb rows wide (row s * nb + k = beam k of sequence s; the visual features are encoded once per sequence and repeated), and _append
-    is functional.beam_step (selection and all bookkeeping in a device state block, csrc/ff_beam.hip), functional.beam_gather (the static LM
-    cache reordered in place by beam index, live positions only) and tok <- next_tok.  The cross-attention K / V, the attention mask and
-    text_time are equal within a sequence's beams and are NOT reordered.  The result is read back once, after the loop (_beam_finalize).
-    `processors` = (repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens) puts functional.process_logits (one launch,
-    csrc/ff_logits.hip) in front of the selection of every mode: it edits the step's logits in place against the token history - `ids_buf`
-    with `pos` as its length, which already is the sequence; in a beam session `seq_buf` (b * nb, max_length), which follows the beams through
-    the same in-place gather as the LM cache (viewed as two 4-byte elements per id) - and against `min_len`, a device scalar run() sets
-    outside any capture.  A session without processors issues none of this and allocates no seq_buf."""
-
-    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None):
-        from transformers.cache_utils import StaticCache
-        self._model_ref = weakref.ref(model)
-        self.beams, self.nb, self.n_seq = beams, (beams[0] if beams else 1), b
-        b = b * self.nb
-        self.b, self.max_length, self.eos, self.graph_wanted = b, max_length, eos, graph
-        self.fill = pad if pad is not None else 0
-        self.lm_family = "gpt2" if isinstance(model.flamingo, FlamingoGPT2) else "opt"
-        self.cache = StaticCache(config=model.flamingo.lm.config, max_cache_len=max_length)
-        self.ids_buf = torch.empty((b, max_length), dtype=ids_dtype, device=device)
-        self.am_buf = torch.empty((b, max_length), dtype=am_dtype, device=device)
-        self.finished = torch.zeros(b, dtype=torch.bool, device=device)
-        self.n_new = torch.zeros((), dtype=torch.long, device=device)          # tokens appended while not every sequence had finished
-        self.pos = torch.zeros((1,), dtype=torch.long, device=device)          # position of `tok` (the token the next step consumes)
-        self.tok = torch.zeros((b, 1), dtype=ids_dtype, device=device)
-        self.tt_step = torch.zeros((b, 1), dtype=torch.int32, device=device)
-        self.sampling = sampling
-        if sampling is not None:
-            self.u_all = torch.zeros((max_length, b), dtype=torch.float32, device=device)
-            self.nxt = torch.zeros((b,), dtype=torch.long, device=device)
-        if beams is not None:
-            self.state = F.BeamState(self.n_seq, self.nb, max_length, device, eos=eos, pad=self.fill, early_stopping=beams[1], length_penalty=beams[2])
-            self.cur_len = torch.zeros((1,), dtype=torch.long, device=device)  # pos + 1: the length after the token beam_step chooses
-            self.lm_tensors = None                                             # keys / values of every StaticCache layer (allocated by the first prompt step)
-        self.processors = processors
-        if processors is not None:
-            self.min_len = torch.zeros((1,), dtype=torch.long, device=device)
-            self.min_on = eos is not None and (processors[2] > 0 or processors[3] > 0)
-            if beams is not None:
-                self.seq_buf = torch.full((b, max_length), self.fill, dtype=torch.long, device=device)
-        self.xattn_past = None                                                # persistent (k, v) per layer, filled by every prompt step
-        self.replay = None
-        self.capture_failed = False
-        self.param_ptrs = self._param_ptrs()                                   # what a captured graph reads: checked before every reuse
-
-    @property
-    def model(self):
-        m = self._model_ref()
-        if m is None:
-            raise RuntimeError("decode session used after its model was deleted")
-        return m
-
-    def _param_ptrs(self):
-        return tuple(p.data_ptr() for p in self.model.parameters())
-
-    def stale(self) -> bool:
-        """Parameters were re-allocated since this session was built (model.to() / .half(), ShardedAdamW moving them into flat buffers):
-        a captured graph would replay reads of freed memory."""
-        return self.param_ptrs != self._param_ptrs()
-
-    def _process(self, logits, hist):      # the logits processors, in place, against the first `pos` tokens of every row of `hist`
-        p, g = self.processors[:2]
-        F.process_logits(logits, hist, self.pos, p, g, self.eos if self.min_on else None, self.min_len if self.min_on else None)
-
-    def _append(self, logits):             # choose, apply the eos bookkeeping of generate(), append at `pos`
-        if self.beams is not None:
-            if self.lm_tensors is None:
-                self.lm_tensors = [t for layer in self.cache.layers for t in (layer.keys, layer.values)]
-            if self.processors is not None:
-                self._process(logits, self.seq_buf)
-            torch.add(self.pos, 1, out=self.cur_len)
-            nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
-            F.beam_gather(self.lm_tensors, beam_idx, self.pos, self.nb)       # positions < pos are live: the cache rows follow their beams
-            if self.processors is not None:                                   # ... and so do the histories: an id is two 4-byte elements
-                F.beam_gather([self.seq_buf.view(torch.int32).view(self.b, 1, self.max_length, 2)], beam_idx, self.pos, self.nb)
-                self.seq_buf.index_copy_(1, self.pos, nxt[:, None])
-            self.tok.copy_(nxt[:, None])
-            return
-        if self.processors is not None:
-            self._process(logits, self.ids_buf)
-        if self.sampling is None:
-            nxt = logits.float().argmax(-1)
-        else:
-            temperature, top_k, top_p = self.sampling
-            nxt = F.sample_tokens(logits, self.u_all.index_select(0, self.pos).view(-1), temperature, top_k, top_p, out=self.nxt)
-        alive = ~self.finished.all()
-        if self.eos is not None:
-            nxt = torch.where(self.finished, torch.full_like(nxt, self.fill), nxt)
-            self.finished.logical_or_(nxt == self.eos)
-        self.tok.copy_(nxt[:, None])
-        self.ids_buf.index_copy_(1, self.pos, self.tok)
-        self.n_new.add_(alive.to(self.n_new.dtype))
-
-    def _positions(self, L0=None):
-        """How the LM family learns where a step's tokens sit without reading anything back to the host.  GPT-2 takes absolute cache
-        positions.  OPT numbers the ATTENDED tokens (cumsum of the attention mask, padding skipped - modeling_opt's own rule), and derives
-        that by slicing with the cache's length, which for a StaticCache is a device scalar (a host synchronisation: not capturable): the
-        decode step hands it `position_ids` instead - the token at `pos` is the (number of ones in the mask so far)-th attended one."""
-        if self.lm_family == "gpt2":
-            return {"cache_position": self.pos if L0 is None else torch.arange(L0, device=self.pos.device)}
-        if L0 is None:
-            return {"position_ids": self.am_buf.sum(1, keepdim=True).long() - 1}
-        return {}                       # the prompt step: an empty cache, OPT's own cumsum applies
-
-    def _step(self):
-        self.am_buf.index_fill_(1, self.pos, 1)
-        o = self.model.flamingo(input_ids=self.tok, attention_mask=self.am_buf, use_cache=True, past_key_values=(self.xattn_past, self.cache),
-                                text_time=self.tt_step, **self._positions())
-        self.pos.add_(1)
-        self._append(o.logits[:, -1])
-
-    @torch.no_grad()
-    def run(self, ids, ml, am, pixel_values, visual_features, generator=None):
-        L0 = ids.shape[1]
-        dev = ids.device
-        if self.beams is not None:
-            prompt_ids = ids
-            if visual_features is None and pixel_values is not None:         # encoded once per sequence, repeated per beam
-                visual_features, pixel_values = self.model.flamingo.encode_resample_visuals(pixel_values), None
-            ids, ml, am = _repeat_leading(ids, self.nb), _repeat_leading(ml, self.nb), _repeat_leading(am, self.nb)
-            if visual_features is not None:
-                visual_features = _repeat_leading(visual_features, self.nb)
-            self.state.reset()
-        if self.sampling is not None:
-            self.u_all.copy_(torch.rand((self.max_length, self.b), generator=generator, device=dev, dtype=torch.float32))
-        self.cache.reset()
-        out = self.model.flamingo(input_ids=ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=(None, self.cache),
-                                  pixel_values=pixel_values, visual_features=visual_features, **self._positions(L0))
-        fresh = out.past_key_values[0]
-        if self.xattn_past is None:
-            self.xattn_past = tuple((torch.empty_like(k, memory_format=torch.contiguous_format), torch.empty_like(v, memory_format=torch.contiguous_format))
-                                    for k, v in fresh)
-        for (kb, vb), (k, v) in zip(self.xattn_past, fresh):
-            kb.copy_(k); vb.copy_(v)
-        self.tt_step.copy_(F.text_time(ml)[:, -1:])
-        self.ids_buf.fill_(self.fill)
-        self.ids_buf[:, :L0] = ids
-        self.am_buf.zero_()
-        self.am_buf[:, :L0] = am
-        self.finished.zero_()
-        self.n_new.zero_()
-        self.pos.fill_(L0)
-        if self.processors is not None:
-            self.min_len.fill_(max(self.processors[2], L0 + self.processors[3]))
-            if self.beams is not None:
-                self.seq_buf.fill_(self.fill)
-                self.seq_buf[:, :L0] = ids
-        self._append(out.logits[:, -1])
-        remaining = self.max_length - L0 - 1
-        if self.graph_wanted and self.replay is None and not self.capture_failed and remaining > 1:
-            self._step()                                                      # eager once: lazy initialisation, allocator pools
-            remaining -= 1
-            try:
-                # captured on a stream whose sync buffer exists before the capture: an unprepared capture would keep the separate to_out
-                # launches where the eager steps exchange inside the fused launch (> 32 rows) - replay and eager steps must be the same work
-                self.capture_stream = _prepared_capture_stream(self.model)
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                with torch.cuda.graph(g, stream=self.capture_stream):
-                    self._step()
-                self.graph, self.replay = g, g.replay
-            except Exception:                                                 # the steps run eagerly from here on (and in later calls)
-                torch.cuda.synchronize()
-                self.capture_failed = True
-        run_step = self.replay or self._step
-        i = 0
-        all_done = self.finished if self.beams is None else self.state.done
-        while i < remaining:
-            run_step()
-            i += 1
-            if self.eos is not None and i % 16 == 0 and bool(all_done.all()):          # (a host sync: only every 16 tokens)
-                break
-        if self.beams is not None:                                            # one device-to-host copy; steps past the last `done` only wrote padding
-            host = self.state.to_host()
-            host["length"] = self.max_length - remaining + i
-            return _beam_finalize(host, L0, prompt_ids.cpu(), self.nb, self.fill).to(dev)
-        if self.eos is not None:
-            return self.ids_buf[:, :L0 + int(self.n_new)].clone()
-        return self.ids_buf.clone()
 
 
 class FlamingoModel(PreTrainedModel):
@@ -669,44 +430,8 @@ class FlamingoModel(PreTrainedModel):
                             pixel_values=pixel_values if past is None else None, visual_features=visual_features if past is None else None)
         return out.logits[:, -1].float(), out.past_key_values
 
-    @staticmethod
-    def _filter_logits(logits, temperature, top_k, top_p):
-        """temperature / top-k / nucleus filtering as in transformers' logits warpers."""
-        if temperature != 1.0:
-            logits = logits / temperature
-        if top_k and top_k > 0:
-            kth = logits.topk(min(top_k, logits.shape[-1]), dim=-1).values[..., -1, None]
-            logits = logits.masked_fill(logits < kth, float("-inf"))
-        if top_p < 1.0:
-            srt, idx = logits.sort(dim=-1, descending=True)
-            cum = srt.softmax(-1).cumsum(-1)
-            drop = cum - srt.softmax(-1) >= top_p               # keep the smallest prefix whose mass reaches top_p
-            logits = logits.masked_fill(drop.scatter(-1, idx, drop), float("-inf"))
-        return logits
-
-    @staticmethod
-    def _process_logits(logits, seqs, repetition_penalty, no_repeat_ngram_size, eos, min_len):
-        """Repetition penalty, no-repeat n-gram ban and minimum length on float32 `logits` (rows, V) against the sequences so far `seqs`
-        (rows, n): the rules of ff_logits_process (include/flamingo_fusion.h) restated in torch for the dynamic loops, with the same
-        x * (1.0f / p) where transformers divides.  Returns new logits."""
-        V, n = logits.shape[-1], seqs.shape[1]
-        seqs = seqs.long()
-        valid = (seqs >= 0) & (seqs < V)
-        out = torch.cat([logits, logits.new_zeros(logits.shape[0], 1)], dim=1)          # column V takes what out-of-range ids would write
-        if repetition_penalty != 1.0 and n > 0:
-            import numpy as np
-            p = np.float32(repetition_penalty)
-            idx = torch.where(valid, seqs, torch.full_like(seqs, V))
-            x = out.gather(1, idx)
-            out.scatter_(1, idx, torch.where(x < 0, x * float(p), x * float(np.float32(1.0) / p)))
-        if 1 <= no_repeat_ngram_size <= n:
-            g = no_repeat_ngram_size
-            win = seqs.unfold(1, g, 1)                                                   # (rows, n - g + 1, g)
-            match = (win[..., :g - 1] == seqs[:, None, n - g + 1:]).all(-1)
-            out.scatter_(1, torch.where(match & valid[:, g - 1:], win[..., -1], torch.full_like(win[..., -1], V)), float("-inf"))
-        if eos is not None and min_len is not None and n < min_len:
-            out[:, eos] = float("-inf")
-        return out[:, :V].contiguous()
+    _filter_logits = staticmethod(D.filter_logits)         # the torch restatements the dynamic loops use
+    _process_logits = staticmethod(D.process_logits)
 
     @torch.no_grad()
     def generate(self, inputs=None, media_locations=None, attention_mask=None, pixel_values=None, visual_features=None,
@@ -720,9 +445,10 @@ class FlamingoModel(PreTrainedModel):
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
         implemented here: greedy, multinomial sampling (do_sample, temperature, top_k, top_p) and beam search (num_beams, length_penalty,
         early_stopping).  Unknown generation arguments raise instead of being ignored.
-        Sampling and beam search (num_beams <= 8) take the fixed-shape, graph-replayed path of greedy decoding (_DecodeSession) only when
-        `static_decode=True` is passed explicitly (GPU tensors, a GPT-2- or OPT-backed model, a prompt shorter than max_length - 1); otherwise it runs the dynamic loop
-        below, as it always has.  The two paths draw DIFFERENT token streams from the same seed: the static path draws by inverse CDF in
+        The three steps are the argument checks, decoding.route - the one statement of which path a call takes - and the call itself.
+        Sampling and beam search (num_beams <= 8) take the fixed-shape, graph-replayed path of greedy decoding (decoding._DecodeSession) only
+        when `static_decode=True` is passed explicitly (GPU tensors, a GPT-2- or OPT-backed model, a prompt shorter than max_length - 1);
+        otherwise they run the dynamic loops (decoding.dynamic_decode / beam_search), as they always have.  The two paths draw DIFFERENT token streams from the same seed: the static path draws by inverse CDF in
         vocabulary order from one uniform number per token (functional.sample_tokens), the dynamic loop with torch.multinomial.  Both are
         reproducible per seed (`generator`).
         Logits processors, as in transformers: `repetition_penalty` (1 = off), `no_repeat_ngram_size` (0 = off) and `min_length` /
@@ -732,180 +458,33 @@ class FlamingoModel(PreTrainedModel):
         restatement _process_logits.  They are offered for GPU tensors only: with CPU tensors generate() raises TypeError for them, as it
         did before they existed (the processor kernel has no CPU form; static_decode=True raises what ffi.require_cuda raises).  Deliberate deviation from transformers in beam search: the log-softmax is taken AFTER the processors, so
         the mass of banned tokens is renormalised over the rest, where transformers penalises log-probabilities without renormalising."""
-        if unsupported:
-            raise TypeError(f"generate(): unsupported generation arguments {sorted(unsupported)}")
-        if not use_cache:
-            raise ValueError("generate() always decodes with the cross-attention / LM caches (use_cache=True)")
-        if isinstance(repetition_penalty, bool) or not isinstance(repetition_penalty, (int, float)) or not 0 < repetition_penalty < float("inf"):
-            raise ValueError(f"generate(): repetition_penalty must be a positive, finite number (1 = off), got {repetition_penalty!r}")
-        for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_length", min_length), ("min_new_tokens", min_new_tokens)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-                raise ValueError(f"generate(): {name} must be an integer >= 0 (0 = off), got {v!r}")
-        if (min_length > 0 or min_new_tokens > 0) and eos_token_id is None:
-            raise ValueError("generate(): min_length / min_new_tokens need eos_token_id")
-        procs = None                                                          # every processor off: exactly the paths without them
-        if repetition_penalty != 1 or no_repeat_ngram_size > 0 or min_length > 0 or min_new_tokens > 0:
-            procs = (float(repetition_penalty), int(no_repeat_ngram_size), int(min_length), int(min_new_tokens))
+        procs = D.check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos_token_id)
         ids = inputs if inputs is not None else input_ids
         assert ids is not None and media_locations is not None, "generate() needs input ids and media_locations"
         am = attention_mask if attention_mask is not None else torch.ones_like(ids)
         ml = media_locations
         pad = pad_token_id if pad_token_id is not None else eos_token_id
-        if procs is not None and not ids.is_cuda:                             # GPU tensors only: on CPU tensors they stay what they were, unsupported
-            if static_decode:
-                F.ffi.require_cuda(ids)
-            given = [n for n, v, off in (("repetition_penalty", repetition_penalty, 1), ("no_repeat_ngram_size", no_repeat_ngram_size, 0),
-                                         ("min_length", min_length, 0), ("min_new_tokens", min_new_tokens, 0)) if v != off]
-            raise TypeError(f"generate(): unsupported generation arguments {given} on CPU tensors (the logits processors run on the GPU only)")
-        static_ok = isinstance(self.flamingo, (FlamingoGPT2, FlamingoOPT)) and ids.shape[1] + 1 < max_length and \
-            (procs is None or (ids.dtype == torch.long and max_length <= F.ffi.LOGITS_HIST_MAX))
+        path = D.route(is_cuda=ids.is_cuda, num_beams=num_beams, do_sample=do_sample, static_decode=static_decode, model_default=self.static_decode, lm_family=self.flamingo.lm_family,
+                       L0=ids.shape[1], max_length=max_length, ids_is_int64=ids.dtype == torch.long, procs_on=procs is not None, procs_given=procs.given() if procs is not None else ())
+        if path == "static":
+            return D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, generator=generator, processors=procs,
+                                    sampling=D.Sampling(float(temperature), int(top_k), float(top_p)) if do_sample else None,
+                                    beams=D.Beams(int(num_beams), bool(early_stopping), float(length_penalty)) if num_beams > 1 else None)
         if num_beams > 1:
-            if do_sample:
-                raise ValueError("beam search with sampling is not implemented")
-            if static_decode:                                                 # explicit static_decode=True: the beam kernels have no CPU form
-                F.ffi.require_cuda(ids)
-                if static_ok and num_beams <= F.ffi.BEAM_MAX:
-                    return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
-                                               beams=(int(num_beams), bool(early_stopping), float(length_penalty)), processors=procs)
-            return self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty,
-                                     processors=procs)
-        if do_sample and static_decode:                                       # explicit static_decode=True: the sampling kernel has no CPU form
-            F.ffi.require_cuda(ids)
-            if static_ok:
-                return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
-                                           sampling=(float(temperature), int(top_k), float(top_p)), generator=generator, processors=procs)
-        if static_decode is None:       # greedy decoding on the GPU (GPT-2- and OPT-backed models): fixed-shape decode steps, replayed from a HIP graph
-            static_decode = ids.is_cuda and self.static_decode
-        if static_decode and not do_sample and static_ok:
-            return self._static_greedy(ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, processors=procs)
-        finished = torch.zeros(ids.shape[0], dtype=torch.bool, device=ids.device)
-        past, step_ids = None, ids
-        min_len = None if procs is None or eos_token_id is None else max(procs[2], ids.shape[1] + procs[3])
-        while ids.shape[1] < max_length:
-            logits, past = self._decode_step(step_ids, ml, am, past, pixel_values, visual_features)
-            if procs is not None:
-                logits = self._process_logits(logits, ids, procs[0], procs[1], eos_token_id, min_len)
-            if do_sample:
-                probs = self._filter_logits(logits, temperature, top_k, top_p).softmax(-1)
-                nxt = torch.multinomial(probs, 1, generator=generator)[:, 0]
-            else:
-                nxt = logits.argmax(-1)
-            if eos_token_id is not None:
-                nxt = torch.where(finished, torch.full_like(nxt, pad), nxt)
-                finished = finished | (nxt == eos_token_id)
-            ids = torch.cat([ids, nxt[:, None]], dim=1)
-            ml = torch.cat([ml, torch.zeros_like(ml[:, :1])], dim=1)
-            am = torch.cat([am, torch.ones_like(am[:, :1])], dim=1)
-            step_ids = ids[:, -1:]
-            if eos_token_id is not None and bool(finished.all()):
-                break
-        return ids
-
-    def _static_greedy(self, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, graph: Optional[bool] = None,
-                       sampling=None, generator=None, beams=None, processors=None):
-        """Greedy (or, with `sampling` = (temperature, top_k, top_p), sampled) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches and buffers plus, on the GPU, the captured
-        HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, eos / pad, sampling settings, beam settings (nb, early_stopping, length_penalty), logits processors) and reused by later calls, so only the
-        first caption batch of a shape pays for the capture.  a session whose model's parameters were re-allocated since (model.to(), ShardedAdamW) is rebuilt; reset_decode_sessions() drops them all."""
-        b = ids.shape[0]
-        if graph is None:
-            graph = ids.is_cuda and not self.training and self.decode_graph
-        sessions = _DECODE_SESSIONS.setdefault(self, {})
-        n_media = int(ml.sum(-1).max()) if visual_features is None and pixel_values is None else \
-            (visual_features.shape[1] if visual_features is not None else (pixel_values.shape[1] if pixel_values.ndim >= 5 else pixel_values.shape[0]))
-        key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams, processors)
-        sess = sessions.get(key)
-        if sess is not None and sess.stale():
-            sessions.pop(key)
-            sess = None
-        if sess is None:
-            if len(sessions) >= 4:                                            # a handful of shapes at most: each holds a KV cache and a graph
-                sessions.pop(next(iter(sessions)))
-            sess = sessions[key] = _DecodeSession(self, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling, beams, processors)
-        if sampling is None:
-            return sess.run(ids, ml, am, pixel_values, visual_features)
-        return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator)
+            return self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty, processors=procs)
+        return D.dynamic_decode(self._decode_step, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
+                                sampling=D.Sampling(temperature, top_k, top_p) if do_sample else None, generator=generator, processors=procs)
 
     @property
     def _decode_sessions(self) -> dict:
-        return _DECODE_SESSIONS.get(self, {})
+        return D._DECODE_SESSIONS.get(self, {})
 
     def reset_decode_sessions(self) -> None:
-        _DECODE_SESSIONS.pop(self, None)
+        D._DECODE_SESSIONS.pop(self, None)
 
     def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None):
-        """Standard beam search over the cached decode path.  The prompt runs once per sequence; its caches are then replicated per beam
-        (xattn K/V: repeat_interleave; LM cache: Cache.batch_repeat_interleave) and re-ordered every step (_reorder_cache).
-        `processors` (see generate()) act on every step's logits before the log-softmax."""
-        b, L0 = ids.shape
-        dev = ids.device
-        min_len = None if processors is None or eos is None else max(processors[2], L0 + processors[3])
-        process = (lambda x, s: x) if processors is None else \
-            (lambda x, s: FlamingoModel._process_logits(x, s, processors[0], processors[1], eos, min_len))
-        logits, past = self._decode_step(ids, ml, am, None, pixel_values, visual_features)
-        logp = process(logits, ids).log_softmax(-1)
-        V = logp.shape[-1]
-        xattn_past, lm_past = past
-        xattn_past = tuple(tuple(_repeat_leading(t, nb) for t in kv) for kv in xattn_past)
-        if hasattr(lm_past, "batch_repeat_interleave"):
-            lm_past.batch_repeat_interleave(nb)
-        else:
-            lm_past = tuple(tuple(_repeat_leading(t, nb) for t in layer) for layer in lm_past)
-        past = (xattn_past, lm_past)
-        seqs = _repeat_leading(ids, nb)                                   # (b * nb, L)
-        ml, am = _repeat_leading(ml, nb), _repeat_leading(am, nb)
-        scores = torch.full((b, nb), float("-inf"), device=dev)
-        scores[:, 0] = 0.0                                                # all beams of a sequence start identical: only one may branch
-        logp = _repeat_leading(logp, nb)
-        done_hyps = [[] for _ in range(b)]                                # (normalised score, token list) per sequence
-        is_done = [False] * b
-        while True:
-            cand = (scores.reshape(-1, 1) + logp).reshape(b, nb * V)
-            top_s, top_i = cand.topk(2 * nb, dim=-1)
-            cur_len = seqs.shape[1] + 1
-            next_scores = torch.full((b, nb), float("-inf"), device=dev)
-            next_tok = torch.full((b, nb), pad if pad is not None else 0, dtype=torch.long, device=dev)
-            next_src = torch.arange(nb, device=dev).repeat(b, 1)
-            top_s_c, top_i_c = top_s.cpu(), top_i.cpu()
-            for bi in range(b):
-                if is_done[bi]:
-                    continue
-                k = 0
-                for rank in range(2 * nb):
-                    s_, i_ = float(top_s_c[bi, rank]), int(top_i_c[bi, rank])
-                    beam, tok = i_ // V, i_ % V
-                    if eos is not None and tok == eos:
-                        if rank < nb:
-                            done_hyps[bi].append((s_ / (cur_len ** length_penalty), seqs[bi * nb + beam].tolist() + [tok]))
-                        continue
-                    next_scores[bi, k], next_tok[bi, k], next_src[bi, k] = s_, tok, beam
-                    k += 1
-                    if k == nb:
-                        break
-                if len(done_hyps[bi]) >= nb:
-                    done_hyps[bi] = sorted(done_hyps[bi], key=lambda t: -t[0])[:nb]
-                    best_open = float(next_scores[bi].max()) / (cur_len ** length_penalty)
-                    if early_stopping or done_hyps[bi][-1][0] >= best_open:
-                        is_done[bi] = True
-            beam_idx = (next_src + torch.arange(b, device=dev)[:, None] * nb).reshape(-1)
-            seqs = torch.cat([seqs.index_select(0, beam_idx), next_tok.reshape(-1, 1)], dim=1)
-            scores = next_scores
-            if all(is_done) or seqs.shape[1] >= max_length:
-                break
-            past = self._reorder_cache(past, beam_idx)
-            ml = torch.cat([ml, torch.zeros_like(ml[:, :1])], dim=1)
-            am = torch.cat([am, torch.ones_like(am[:, :1])], dim=1)
-            logits, past = self._decode_step(seqs[:, -1:], ml, am, past, None, None)
-            logp = process(logits, seqs).log_softmax(-1)
-        out = []
-        for bi in range(b):
-            hyps = list(done_hyps[bi])
-            if not is_done[bi]:                                           # length limit: the open beams count as hypotheses too
-                hyps += [(float(scores[bi, k]) / (seqs.shape[1] ** length_penalty), seqs[bi * nb + k].tolist()) for k in range(nb)
-                         if float(scores[bi, k]) > float("-inf")]
-            out.append(max(hyps, key=lambda t: t[0])[1])
-        width = max(len(o) for o in out)
-        fill = pad if pad is not None else 0
-        return torch.tensor([o + [fill] * (width - len(o)) for o in out], dtype=torch.long, device=dev)
+        """The dynamic beam search (decoding.beam_search) over this model's _decode_step / _reorder_cache."""
+        return D.beam_search(self._decode_step, self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors)
 
     @torch.no_grad()
     def generate_captions(self, processor, pixel_values=None, images=None, prompt: str = "<image>", max_length: int = 150,

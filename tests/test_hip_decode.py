@@ -511,6 +511,42 @@ def test_beam_search_on_gpu():
     assert bool((lb64.sum(1) >= lg64.sum(1) - slack).all()), (lb64.sum(1), lg64.sum(1), slack)
 
 
+FALLBACKS = {   # calls the static path cannot serve: more beams than ff_beam_step has, or a prompt within one token of max_length
+    "beams-9": dict(num_beams=9, static_decode=True, max_length=10),
+    "beams-3-short": dict(num_beams=3, static_decode=True, max_length=5),
+    "sample-short": dict(do_sample=True, static_decode=True, max_length=5),
+    "greedy-short": dict(max_length=5),
+}
+
+
+@pytest.fixture(scope="module", params=["gpt2", "opt"])
+def tiny_on_gpu(request):
+    from test_model_plumbing import build
+    model, z = build(torch.float32, "cuda", request.param)
+    model.eval()
+    ids, ml = torch.from_numpy(z["ids"])[:, :4].cuda(), torch.from_numpy(z["ml"])[:, :4].cuda()
+    return model, ids, dict(media_locations=ml, attention_mask=torch.ones_like(ids), pixel_values=torch.from_numpy(z["px"]).float().cuda())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(FALLBACKS))
+def test_static_requests_the_sessions_cannot_serve_run_the_dynamic_path(tiny_on_gpu, case):
+    """The tiny fp32 models on the device, b = 2, L0 = 4: each call returns exactly what the same call with static_decode=False returns
+    (the same seed where it samples) and builds no session."""
+    model, ids, kw = tiny_on_gpu
+    args = FALLBACKS[case]
+    assert ids.shape == (2, 4) and len(model._decode_sessions) == 0
+
+    def call(**over):
+        g = torch.Generator(device="cuda").manual_seed(1234) if args.get("do_sample") else None
+        return model.generate(ids, **kw, **dict(args, **over), generator=g)
+
+    got, want = call(), call(static_decode=False)
+    assert got.shape == want.shape and torch.equal(got, want), (got.tolist(), want.tolist())
+    assert got.shape[0] == 2 and 4 < got.shape[1] <= args["max_length"]
+    assert len(model._decode_sessions) == 0
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # CPU: the harness itself
 # ---------------------------------------------------------------------------------------------------------------------------------------

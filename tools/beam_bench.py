@@ -2,7 +2,7 @@
 """Beam-search caption decoding at the benchmark's geometry (config B: gpt2-large + CLIP ViT-L/14, random-init backbones, batch 32, bf16,
 a 4-token prompt with the media tag first - bench.py's caption leg), 3 beams, no eos (every call runs to the length limit).  One JSON line:
 
-    dynamic_beam   generate(num_beams=3): the growing-cache loop (_beam_search: log_softmax + topk, a host copy and a Python walk per step,
+    dynamic_beam   generate(num_beams=3): the growing-cache loop (decoding.beam_search: log_softmax + topk, a host copy and a Python walk per step,
                    torch.cat, index_select of every cache tensor)
     static_beam    generate(num_beams=3, static_decode=True): the fixed-shape session, one decode step replayed from a HIP graph with
                    ff_beam_step and ff_beam_gather inside it

@@ -2,7 +2,7 @@
 """Sampled caption decoding at the benchmark's geometry (config B: gpt2-large + CLIP ViT-L/14, random-init backbones, batch 32, bf16, a
 4-token prompt with the media tag first - bench.py's caption leg), temperature 0.8, top_k 50, top_p 0.9.  Four numbers, one JSON line:
 
-    dynamic_sampling   tokens/s of generate(do_sample=True): the growing-cache loop (_filter_logits: topk + sort + 2 softmax + cumsum + scatter,
+    dynamic_sampling   tokens/s of generate(do_sample=True): the growing-cache loop (decoding.dynamic_decode; filter_logits: topk + sort + 2 softmax + cumsum + scatter,
                        torch.multinomial, torch.cat of ids / masks, a host synchronisation per token)
     static_sampling    tokens/s of generate(do_sample=True, static_decode=True): the fixed-shape session, one decode step replayed from a
                        HIP graph with ff_sample_token inside it

@@ -5,7 +5,7 @@ ViT-L/14, random-init backbones, batch 32, bf16, a 4-token prompt with the media
     process_logits_us   ff_logits_process alone on 32 rows x 50 258 columns bf16 with histories of 32, 150 and 1024 tokens (device events
                         around --launches back-to-back calls; the logits are not restored between calls: a later call penalises the
                         penalised values again, with the same loads and stores)
-    torch_chain_us      FlamingoModel._process_logits, the torch restatement the dynamic loops use, on the same GPU and inputs: the op chain
+    torch_chain_us      FlamingoModel._process_logits (decoding.process_logits), the torch restatement the dynamic loops use, on the same GPU and inputs: the op chain
                         the kernel replaces (cat, gather, where, scatter, unfold, compare, all, scatter)
     greedy_off / greedy_on   generate() on the static path without and with the processors: tokens/s and ms per replayed decode step
 
