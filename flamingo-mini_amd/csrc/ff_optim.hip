@@ -542,6 +542,88 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccTable t) 
         a[i] = fold(to_f32(g[i]), OVERWRITE ? 0.f : a[i]);
 }
 
+// ---- exponential moving average of the weights (FusedAdamW(ema_decay=...); include/flamingo_fusion.h has the rule) -------------------------
+// ema += a (th - ema) in the AdamW table's chunks, right after the AdamW launch that wrote th: th = the weights in T (the parameters in bf16 or
+// fp32, or their fp32 master copies) is read once, the fp32 shadow is read and written once.  All accesses are plain ones: the parameters are
+// what the next forward reads and stay cacheable, as in adamw_kernel's store, and for the shadow - touched once per step like the moments -
+// nontemporal loads and stores were measured and lost: the pass over config B's 684 M bf16 parameters takes 1.37 ms with plain shadow accesses
+// (5.0 TB/s) and 1.60 - 1.64 ms with nontemporal ones (4.2 - 4.3 TB/s); DESIGN.md, weight averaging.  Four independent 16-byte weight loads
+// (and their shadow loads: two per weight load for bf16) per thread in flight before the first subtraction.
+// Its own kernel and not one more flag of adamw_kernel: fusing would save the 2-byte re-read of the parameter out of 10 bytes per element
+// and double the 33 instantiations.  *t.skip and the `every` rule are wave-uniform and decided before any tensor access: a launch that does
+// not average is a no-op, as a GUARD launch of adamw_kernel is.
+struct EmaTable {
+    const void* th[kAdamTensors];
+    float* ema[kAdamTensors];
+    ChunkTable chunks;
+    float decay, step;       // step: the number of the step just taken where it is not read from *step_dev
+    int warmup, every;
+    const float* step_dev;
+    const float* skip;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void ema_update_kernel(const EmaTable t) {
+    constexpr int VEC = Vec<T>::N, PIECES = 4;
+    const float step = t.step_dev ? *t.step_dev : t.step;
+    if (t.skip && *t.skip != 0.f) return;
+    if (t.every > 1 && fmodf(step, (float)t.every) != 0.f) return;
+    // (the intrinsics keep every operation a separately rounded one, so that `a` is the host restatement's bit for bit)
+    const float d = t.warmup ? fminf(t.decay, __fdiv_rn(__fadd_rn(1.f, step), __fadd_rn(10.f, step))) : t.decay;
+    const float a = __fsub_rn(1.f, d);
+    const auto [ti, n, base, end] = my_chunk(t.chunks);
+    const T* th = (const T*)t.th[ti];
+    float* ema = t.ema[ti];
+    auto lde = [&](long long i, float (&o)[VEC]) {                  // VEC shadow elements: one (fp32 weights) or two 16-byte loads
+#pragma unroll
+        for (int c = 0; c < VEC / 4; c++) {
+            float part[4];
+            Vec<float>::load(ema + i + c * 4, part);
+#pragma unroll
+            for (int e = 0; e < 4; e++) o[c * 4 + e] = part[e];
+        }
+    };
+    auto ste = [&](long long i, const float (&o)[VEC]) {
+#pragma unroll
+        for (int c = 0; c < VEC / 4; c++) {
+            float part[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) part[e] = o[c * 4 + e];
+            Vec<float>::store(ema + i + c * 4, part);
+        }
+    };
+    auto avg = [&](float w, float s) { return fmaf(a, __fsub_rn(w, s), s); };      // one subtraction, one fused multiply-add
+    long long tail = base;                          // elements from here to `end` go one by one
+    if (((uintptr_t)th | (uintptr_t)ema) % 16 == 0) {  // (base is a multiple of the chunk, so every vector below is 16-byte aligned)
+        const long long vend = base + (end - base) / VEC * VEC;
+        tail = vend;
+        long long i = base + (long long)threadIdx.x * VEC;
+        for (; i + (PIECES - 1) * 256 * VEC < vend; i += PIECES * 256 * VEC) {
+            float wf[PIECES][VEC], sf[PIECES][VEC];
+#pragma unroll
+            for (int k = 0; k < PIECES; k++) Vec<T>::load(th + i + k * 256 * VEC, wf[k]);
+#pragma unroll
+            for (int k = 0; k < PIECES; k++) lde(i + k * 256 * VEC, sf[k]);
+#pragma unroll
+            for (int k = 0; k < PIECES; k++) {
+#pragma unroll
+                for (int e = 0; e < VEC; e++) sf[k][e] = avg(wf[k][e], sf[k][e]);
+                ste(i + k * 256 * VEC, sf[k]);
+            }
+        }
+        for (; i < vend; i += 256 * VEC) {          // (a tensor's last, partial chunk)
+            float wf[VEC], sf[VEC];
+            Vec<T>::load(th + i, wf);
+            lde(i, sf);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) sf[e] = avg(wf[e], sf[e]);
+            ste(i, sf);
+        }
+    }
+    for (long long i = tail + threadIdx.x; i < end; i += 256)       // ragged tail (< VEC elements), or an unaligned tensor's whole chunk
+        ema[i] = avg(to_f32(th[i]), ema[i]);
+}
+
 // ff_stochastic_round_bf16: dst = src rounded stochastically (ff_sr.h), element i with the bits the optimizer gives element i of a tensor:
 // 16-byte stores over the whole vectors where src and dst are on the 16-byte grid, the ragged tail - or, off the grid, everything - one by one
 __global__ __launch_bounds__(256) void sr_round_kernel(const float* src, bf16* dst, long long n, unsigned long long seed, unsigned step,
@@ -635,6 +717,32 @@ extern "C" int ff_stochastic_round_bf16(const float* src, void* dst, long long n
     FF_CHECK(blocks <= kGradMaxBlocks, FF_ERR_SHAPE, "%s: %lld elements", what, n);
     sr_round_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(src, (bf16*)dst, n, (unsigned long long)seed, step, stream_id << 2 | (unsigned)slot);
     return check_launch(what);
+}
+extern "C" int ff_ema_update(int dtype, int n_tensors, const void* const* params, const float* const* master, float* const* ema,
+                             const long long* numels, float decay, int warmup, int every, int step, const float* step_dev, const float* skip,
+                             ff_stream_t stream) {
+    using namespace ff;
+    const char* what = "ff_ema_update";
+    FF_CHECK(dtype == FF_DTYPE_F32 || dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "%s: dtype %d", what, dtype);
+    FF_CHECK(decay > 0.f && decay < 1.f, FF_ERR_SHAPE, "%s: decay %g is not in (0, 1)", what, (double)decay);
+    FF_CHECK(every >= 1, FF_ERR_SHAPE, "%s: every=%d", what, every);
+    FF_CHECK(step >= 1 || step_dev, FF_ERR_SHAPE, "%s: step=%d without step_dev", what, step);
+    FF_CHECK(n_tensors >= 0 && (n_tensors == 0 || ((params || master) && ema && numels)), FF_ERR_SHAPE, "%s: null argument", what);
+    EmaTable t;
+    t.decay = decay; t.step = (float)std::max(step, 1);
+    t.warmup = warmup != 0; t.every = every;
+    t.step_dev = step_dev; t.skip = skip;
+    const bool f32 = master || dtype == FF_DTYPE_F32;            // the weights are read in fp32: master copies, or fp32 parameters
+    return chunk_launches(what, t.chunks, n_tensors, numels, [&](int cnt, int i) -> int {
+        const void* th = master ? (const void*)master[i] : params[i];
+        FF_CHECK(th && ema[i], FF_ERR_SHAPE, "%s: tensor %d has a null pointer", what, i);
+        t.th[cnt] = th; t.ema[cnt] = ema[i];
+        return FF_OK;
+    }, [&](int blocks, long long) -> int {
+        if (f32) ema_update_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(t);
+        else ema_update_kernel<bf16><<<blocks, 256, 0, (hipStream_t)stream>>>(t);
+        return check_launch(what);
+    });
 }
 extern "C" long long ff_grad_sumsq_partials(int n_tensors, const long long* numels) {
     return n_tensors > 0 && numels ? ff::grad_slots(n_tensors, numels) : 0;

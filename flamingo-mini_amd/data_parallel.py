@@ -309,6 +309,7 @@ class ShardedAdamW(torch.optim.Optimizer):
 
     Stochastic rounding (FusedAdamW(stochastic_rounding=True)) is not offered here: a shard's element index is not the parameter's, so the
     streams would depend on the world size; pure-bf16 data-parallel training with it is GradientAllReducer + FusedAdamW.
+    The exponential moving average of the weights (FusedAdamW(ema_decay=...)) is not offered here either.
 
     xGMI arithmetic (8 GPUs, 7 links x ~153 GB/s each): reduce-scatter + all-gather move 2 * (S / 8) per link pair instead of a
     ring's 2 * (7/8) * S over one link, and the update touches 1/8 of the state per rank.

@@ -166,6 +166,7 @@ _SIGNATURES = {
     "ff_adamw_step_guarded": (_I, [C.POINTER(AdamWDesc), _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ff_adamw_step_sr": (_I, [C.POINTER(AdamWDesc), _I, _P, _P, _I, _P, _P, _P, _P, _P, C.c_longlong, _P, _P, _P]),
     "ff_stochastic_round_bf16": (_I, [_P, _P, C.c_longlong, C.c_longlong, C.c_uint, C.c_uint, _I, _P]),
+    "ff_ema_update": (_I, [_I, _I, _P, _P, _P, _P, C.c_float, _I, _I, _I, _P, _P, _P]),
     "ff_sample_token": (_I, [_I, _I, _I, C.c_longlong, _P, C.c_float, _I, C.c_float, _P, _P, _P]),
     "ff_beam_workspace_bytes": (_SZ, [_I, _I]),
     "ff_beam_step": (_I, [C.POINTER(BeamDesc), _P, _P, _P, _SZ, _P]),

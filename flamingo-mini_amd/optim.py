@@ -58,9 +58,24 @@ which it excludes (a master copy already keeps the bits).  The random bits are a
 alike make the same decisions whatever the bucketing: on every data-parallel rank, under step(only=...) in any partition, with or without
 accumulate(), eagerly or replayed from a graph; a skipped step does not consume its step number's bits.  Both settings are optimizer-wide and
 stay out of state_dict() (`step` is in it: resuming with the same arguments continues the same streams).  fp32 parameters of the same optimizer
-are updated as without it."""
+are updated as without it.
+
+Exponential moving average of the weights (evaluating the Polyak average gives a better and steadier checkpoint than the last iterate):
+`ema_decay=d` keeps an fp32 shadow of every parameter in the optimizer state (`state["ema"]`, created with the state as a copy of the weight
+before its first update) and averages it on the device, one ff_ema_update after each bucket's AdamW launch on the same stream:
+ema += (1 - d_t) (theta - ema), theta = the fp32 master copy where there is one, else the parameter; `ema_warmup=True` uses
+d_t = min(d, (1 + t) / (10 + t)), `ema_every=k` averages on every k-th step only.  The launch reads the step count where the AdamW launch
+reads it and the guard's verdict, so a captured step contains the averaging, and a step skipped on the device leaves every shadow bit for bit
+and does not consume a warmup step.  step(only=...) averages exactly the parameters it updates.  DEVIATION from the textbook rule: a
+parameter without a gradient in a step is not updated by this optimizer and is not averaged in that step either.  The shadow is always
+fp32 (weight averaging: a bf16 shadow either never moves or carries the rounding noise of 1 / (1 - d) stores); with
+`stochastic_rounding=True` it averages the rounding noise of the stored weights away, for 4 bytes per parameter.  The three settings are
+optimizer-wide and stay out of state_dict(); the shadows are in it.  `ema_parameters()` yields (parameter, shadow) pairs;
+`with opt.swap_ema():` puts the averages into the parameters IN PLACE (rounded to nearest in the parameter's dtype, the same storage: cached
+decode sessions and captured graphs stay valid) and restores the weights bit for bit on exit."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Iterable, Optional
 
@@ -72,9 +87,20 @@ from . import ffi
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  grad_scale: float = 1.0, capturable: bool = False, master_dtype=None, state_dtype=None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False, stochastic_rounding: bool = False, sr_seed: int = 0):
+                 skip_nonfinite: bool = False, stochastic_rounding: bool = False, sr_seed: int = 0, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = False, ema_every: int = 1):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameters")
+        if ema_decay is not None and not 0 < float(ema_decay) < 1:
+            raise ValueError(f"ema_decay must be in (0, 1) (None: no averaging), got {ema_decay}")
+        if int(ema_every) != ema_every or ema_every < 1:
+            raise ValueError(f"ema_every must be an integer >= 1, got {ema_every}")
+        if ema_decay is None and (ema_warmup or ema_every != 1):
+            raise ValueError("ema_warmup / ema_every are settings of the weight average: they need ema_decay")
+        # optimizer-wide and out of state_dict() as well; the shadows (state[p]["ema"]) are state
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup, self.ema_every = bool(ema_warmup), int(ema_every)
+        self._ema_swapped = False                         # inside `with swap_ema()`: the parameters hold the averages
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError(f"max_grad_norm must be > 0 (None: no clipping), got {max_grad_norm}")
         # an optimizer-wide setting (the norm spans every group), so it is no group hyper-parameter and stays out of state_dict()
@@ -148,6 +174,8 @@ class FusedAdamW(torch.optim.Optimizer):
         set `.grad = None` (one ff_grad_accumulate call per gradient dtype and device).  Opens an accumulation cycle: the next step() reads
         the accumulators.  Enqueues on the current stream only - no allocation after the first cycle, no synchronisation (capturable)."""
         from . import functional as _F
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.accumulate() inside `with swap_ema()`: the parameters hold the averaged weights")
         lib = ffi.lib()
         calls = {}
         for group in self.param_groups:
@@ -193,6 +221,8 @@ class FusedAdamW(torch.optim.Optimizer):
         the gradients of every rank); only without max_grad_norm.
         skip_nonfinite, or `found_inf` / `grad_scale` set by torch.amp.GradScaler.step(): the guarded step (module docstring); neither
         only= (the verdict needs every gradient before the first update) nor grad_coef= (it says nothing about finiteness) goes with it."""
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.step() inside `with swap_ema()`: the parameters hold the averaged weights")
         ext_found, ext_scale = getattr(self, "found_inf", None), getattr(self, "grad_scale", None)
         amp = ext_found is not None or ext_scale is not None
         guard = self.skip_nonfinite or amp
@@ -265,6 +295,13 @@ class FusedAdamW(torch.optim.Optimizer):
                                                                   bucket["v_ptrs"], bucket["w_ptrs"], bucket["numels"]),
                                 lr_dev, coef, self._clip["skip"] if guard else None, acc, ffi.stream_handle(bucket["device"]),
                                 sr=None if bucket["sr_ids"] is None else (self.sr_seed, bucket["sr_ids"]))
+                # the weights were just written: the average follows per bucket, so that the caches get a chance to serve them (host
+                # mode knows the step count, so a step that ema_every leaves out issues no launch)
+                if self.ema_decay is not None and (capturable or step % self.ema_every == 0):
+                    ffi.check(lib.ff_ema_update(bucket["dtype_code"], n, bucket["param_ptrs"], bucket["w_ptrs"], bucket["ema_ptrs"], bucket["numels"],
+                                                self.ema_decay, int(self.ema_warmup), self.ema_every, step, step_dev,
+                                                self._clip["skip"].data_ptr() if guard else None, ffi.stream_handle(bucket["device"])),
+                              "ff_ema_update")
         if acc:
             self.reset_accumulation()                     # the cycle is closed: the next accumulate() overwrites
         return loss
@@ -325,6 +362,39 @@ class FusedAdamW(torch.optim.Optimizer):
                       "ff_grad_clip_coef")
         return clip["coef"]
 
+    # ------------------------------------------------------------------ the averaged weights
+    def ema_parameters(self):
+        """(parameter, its fp32 shadow) for every parameter that has one, in param_groups order (none before the first step)."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                shadow = self.state.get(p, {}).get("ema")
+                if shadow is not None:
+                    yield p, shadow
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Evaluate with the averaged weights: inside the block every parameter that has a shadow holds the shadow's value rounded to nearest
+        in the parameter's dtype - written IN PLACE, so data_ptr() stays, cached decode sessions are not stale and captured graphs replay on
+        the averages.  The weights' own bits wait in a stash of the parameter's dtype and are put back on exit, after an exception too;
+        master copies, moments and shadows are not touched.  step(), accumulate() and a nested swap_ema() raise RuntimeError inside the block;
+        entering it while a stream is capturing raises as well.  Plain torch copies: this is no hot path."""
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.swap_ema() is not reentrant: the parameters already hold the averaged weights")
+        pairs = list(self.ema_parameters())
+        if any(p.is_cuda for p, _ in pairs) and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW.swap_ema() cannot be entered while a stream is capturing a graph (swap first, then capture or replay)")
+        live = [p.detach() for p, _ in pairs]             # (detached views of the same storage: the copies are no autograd operations)
+        stash = [t.clone() for t in live]
+        self._ema_swapped = True
+        try:
+            if live:
+                torch._foreach_copy_(live, [s for _, s in pairs])
+            yield self
+        finally:
+            if live:
+                torch._foreach_copy_(live, stash)
+            self._ema_swapped = False
+
     def sync_device_hyperparams(self) -> None:
         """capturable mode: copy `group["lr"]` into the device scalar the captured kernels read (call before replaying a graph)."""
         for group in self.param_groups:
@@ -368,6 +438,9 @@ class FusedAdamW(torch.optim.Optimizer):
             if mixed and self.master_dtype is not None and "master" not in st:
                 st["master"] = p.detach().to(torch.float32)
             has_master = "master" in st
+            if self.ema_decay is not None and "ema" not in st:      # the weight as it is before its first (or, after a checkpoint without shadows, next) update
+                st["ema"] = _F._new_like(p, dtype=torch.float32)
+                st["ema"].copy_(st["master"] if has_master else p.detach())
             table.setdefault((p.dtype, p.device, int(st["step"]), st["exp_avg"].dtype, has_master), []).append(p)
         buckets = []
         for (dtype, device, step, sdt, has_master), params in table.items():
@@ -378,6 +451,7 @@ class FusedAdamW(torch.optim.Optimizer):
                                 acc_ptrs=ffi.ptr_array([self._acc[p] for p in params]) if acc else None,
                                 m_ptrs=ffi.ptr_array([self.state[p]["exp_avg"] for p in params]),
                                 v_ptrs=ffi.ptr_array([self.state[p]["exp_avg_sq"] for p in params]),
+                                ema_ptrs=ffi.ptr_array([self.state[p]["ema"] for p in params]) if self.ema_decay is not None else None,
                                 numels=(C.c_longlong * n)(*[p.numel() for p in params]),
                                 # stochastic rounding: the bf16 parameters' stream ids (they have no master copies); None = round to nearest
                                 sr_ids=(C.c_uint * n)(*[self._sr_ids[p] for p in params])
@@ -430,10 +504,10 @@ class FusedAdamW(torch.optim.Optimizer):
             if src is None or st is None:
                 continue
             mixed = p.dtype == torch.bfloat16
-            for key in ("exp_avg", "exp_avg_sq", "master"):
+            for key in ("exp_avg", "exp_avg_sq", "master", "ema"):
                 if key not in src or not torch.is_tensor(src[key]):
                     continue
-                want = torch.float32 if key == "master" else (self.state_dtype if (mixed and self.state_dtype is not None) else
+                want = torch.float32 if key in ("master", "ema") else (self.state_dtype if (mixed and self.state_dtype is not None) else
                                                               (src[key].dtype if mixed else p.dtype))
                 if st[key].dtype != want or st[key].dtype != src[key].dtype:
                     st[key] = src[key].detach().to(device=p.device, dtype=want).clone(memory_format=torch.preserve_format)
@@ -441,6 +515,8 @@ class FusedAdamW(torch.optim.Optimizer):
                 st["step"] = st["step"].detach().to("cpu", torch.float32)
             if mixed and self.master_dtype is None and "master" in st:
                 del st["master"]                       # this optimizer keeps no master copies: the parameter itself is the weight
+            if self.ema_decay is None and "ema" in st:
+                del st["ema"]                          # ... and this one no average (one that does and finds none starts it at the next step)
         for group in self.param_groups:                # device-side counters of the capturable mode restart from the loaded step counts
             for k in ("_step_dev", "_lr_dev", "_lr_on_dev"):
                 group.pop(k, None)

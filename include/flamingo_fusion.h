@@ -53,7 +53,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, addition only: token selection for sampled decoding, ff_sample_token;
                                 * still 6, additions only: beam search on the captured decode step, ff_beam_step, ff_beam_gather;
                                 * still 6, additions only: stochastic rounding for pure-bf16 training, ff_adamw_step_sr, ff_stochastic_round_bf16;
-                                * still 6, addition only: logits processors on the captured decode step, ff_logits_process) */
+                                * still 6, addition only: logits processors on the captured decode step, ff_logits_process;
+                                * still 6, addition only: exponential moving average of the weights, ff_ema_update) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -486,6 +487,29 @@ int ff_adamw_step_sr(const ff_adamw_desc* d, int state_dtype, void* const* param
                      long long seed, const unsigned* stream_ids, const long long* numels, ff_stream_t stream);
 int ff_stochastic_round_bf16(const float* src, void* dst, long long n, long long seed, unsigned stream_id, unsigned step, int slot,
                              ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Exponential moving average (Polyak average) of the weights (added under ABI 6): an fp32 shadow of every parameter, averaged on the
+ * device right after the AdamW launch that wrote the weights, so that a captured step contains it and a step skipped on the device
+ * (ff_grad_guard's *skip) leaves it alone.  The rule, in fp32, each operation rounded once, the same code whether the step count comes
+ * from the host or from the device:
+ *     t    = step_dev ? *step_dev : (float)step                 // number of the step just taken, >= 1
+ *     if (skip && *skip != 0) return;                           // wave-uniform, before any tensor access (as GUARD)
+ *     if (every > 1 && fmodf(t, (float)every) != 0) return;     // wave-uniform
+ *     d_t  = warmup ? fminf(decay, (1.0f + t) / (10.0f + t)) : decay
+ *     a    = 1.0f - d_t
+ *     th   = master ? master[i][e] : (float)params[i][e]        // bf16 widened exactly
+ *     ema[i][e] = fmaf(a, th - ema[i][e], ema[i][e])
+ *   ff_ema_update   n_tensors contiguous tensors of any alignment, zero-element tensors skipped, in launches of up to 32 tensors.  dtype:
+ *                   the parameters' type (FF_DTYPE_F32 / FF_DTYPE_BF16).  master: fp32 master copies or NULL; where it is given, params is
+ *                   not read and may be NULL.  ema: the fp32 shadows (always fp32: a bf16 shadow rounded to nearest never moves at decay
+ *                   0.9999, a stochastically rounded one carries a standing error of about 29 ulps - DESIGN.md).  step_dev and skip are
+ *                   device scalars or NULL.  FF_ERR_SHAPE before any HIP call: decay outside (0, 1), every < 1, step < 1 without
+ *                   step_dev, a null table with n_tensors > 0.  n_tensors == 0 is FF_OK.
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_ema_update(int dtype, int n_tensors, const void* const* params, const float* const* master, float* const* ema,
+                  const long long* numels, float decay, int warmup, int every, int step, const float* step_dev,
+                  const float* skip, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Shifted next-token cross-entropy (modeling_flamingo.py:288-298): position i predicts labels[i+1].
