@@ -4,6 +4,7 @@ dynamic loops take the model's `_decode_step` / `_reorder_cache` as callables.  
 """
 from __future__ import annotations
 
+import dataclasses
 import weakref
 from typing import NamedTuple, Optional
 
@@ -33,6 +34,19 @@ class Processors(NamedTuple):
         return [n for n, v, off in zip(self._fields, self, (1, 0, 0, 0)) if v != off]
 
 
+@dataclasses.dataclass
+class GenerateOutput:
+    """What generate(return_dict_in_generate=True) returns.  `sequences` (rows, width) are the ids generate() returns without the flag.
+    `token_logprobs` (rows, width - L0), greedy and sampling with output_logprobs=True: the log-softmax, at the chosen token, of the step's
+    logits as the selection sees them (after the logits processors, before temperature / top-k / top-p); 0 at the pad positions of a row
+    that had finished, the eos token carries its own.  `sequences_scores` (rows,): beam search - the normalised score the search ranked by;
+    greedy and sampling with output_logprobs=True - sum(token_logprobs) / float32(len ** length_penalty), len = the prompt's length plus
+    the generated tokens up to and including eos.  A field that was not computed is None."""
+    sequences: torch.Tensor
+    sequences_scores: Optional[torch.Tensor] = None
+    token_logprobs: Optional[torch.Tensor] = None
+
+
 def _repeat_leading(t: torch.Tensor, m: int) -> torch.Tensor:
     """'n ... -> (n m) ...' (each row repeated m times, as beam search does with input_ids)."""
     return t.repeat_interleave(m, dim=0)
@@ -57,11 +71,43 @@ def check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ng
     return procs if procs.given() else None
 
 
-def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_family, L0, max_length, ids_is_int64, procs_on, procs_given=()):
+def check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample) -> int:
+    """The checks of generate()'s output arguments.  Returns num_return_sequences."""
+    n = num_return_sequences
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"generate(): num_return_sequences must be an integer >= 1, got {n!r}")
+    if output_logprobs and not return_dict_in_generate:
+        raise ValueError("generate(): output_logprobs=True needs return_dict_in_generate=True")
+    if output_logprobs and num_beams > 1:
+        raise ValueError("generate(): output_logprobs=True is not offered with beam search (per-token values would be differences of rounded "
+                         "running sums); sequences_scores holds the score the search ranked by")
+    if n > 1 and num_beams > 1 and n > num_beams:
+        raise ValueError(f"generate(): num_return_sequences {n} exceeds num_beams {num_beams}")
+    if n > 1 and num_beams <= 1 and not do_sample:
+        raise ValueError("generate(): num_return_sequences > 1 needs do_sample=True or num_beams > 1 (greedy decoding has one result)")
+    return n
+
+
+def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
+    """sum(token_logprobs) / float32(len ** length_penalty) per row, len = L0 + the generated tokens up to and including eos: beam search's
+    normalisation (BeamState.len_norm) applied to greedy and sampled sequences."""
+    gen = sequences[:, L0:]
+    n_gen = torch.full((gen.shape[0],), gen.shape[1], dtype=torch.long, device=gen.device)
+    if eos is not None and gen.shape[1] > 0:
+        hit = gen == eos
+        n_gen = torch.where(hit.any(1), hit.long().argmax(1) + 1, n_gen)
+    norm = torch.tensor([float(L0 + int(k)) ** length_penalty for k in n_gen.tolist()], dtype=torch.float32, device=gen.device)
+    return token_logprobs.sum(1) / norm.to(token_logprobs.dtype)
+
+
+def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_family, L0, max_length, ids_is_int64, procs_on, procs_given=(),
+          logprobs_on=False):
     """Which path a generate() call takes: "static" (a _DecodeSession) or "dynamic" (dynamic_decode / beam_search), from plain values only.
     `static_decode` is generate()'s argument (None, True, False), `model_default` the model's attribute, `procs_given` the processor
     arguments' names for the TypeError on CPU tensors.  Greedy decoding takes the static path by default on the GPU; sampling and beam search
-    only when static_decode=True is passed, and then they need GPU tensors: their kernels have no CPU form."""
+    only when static_decode=True is passed, and then they need GPU tensors: their kernels have no CPU form.  Neither has the log-probability
+    kernel (`logprobs_on`): a static session that records them needs GPU tensors, CPU tensors take the dynamic loop unless static_decode=True
+    asks for what cannot be had."""
     def need_gpu():                     # what ffi.require_cuda raises for a CPU tensor
         if not is_cuda:
             F.ffi.require_cuda(torch.empty(0))
@@ -73,7 +119,7 @@ def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_fam
     if num_beams > 1 and do_sample:
         raise ValueError("beam search with sampling is not implemented")
     on_request = num_beams > 1 or do_sample                                   # static only when static_decode=True is passed
-    if on_request and static_decode:
+    if (on_request or logprobs_on) and static_decode:
         need_gpu()
     if static_decode is None:
         static_decode = is_cuda and model_default and not on_request
@@ -145,12 +191,15 @@ def _pad_finished(nxt, finished, eos, pad):
 _DECODE_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
-def _beam_finalize(state, L0, prompt_ids, nb, pad):
+def _beam_finalize(state, L0, prompt_ids, nb, pad, *, n_return=None):
     """The result of a beam search from the state block of ff_beam_step, on the host (numpy only; `state` = BeamState.to_host(), plus
     "length" = the sequences' length after the last step, default: the whole history): per sequence the best finished hypothesis - or, when
     the sequence is not done (the length limit), the best of the hypotheses and the open beams, normalised in float32 by len_norm[length],
     the earlier entry on equal scores - as in the tail of beam_search.  Tokens are read back by following hist_parent
-    downwards from the entry's row; rows are padded with `pad` to the longest.  Returns (b, width) int64 on the CPU."""
+    downwards from the entry's row; rows are padded with `pad` to the longest.  Returns (b, width) int64 on the CPU.
+    With `n_return` = n it returns (ids (b * n, width), scores (b * n,) float32): per sequence the n best of the same entries, best first,
+    the earlier entry on equal scores, each with the normalised score it was ranked by; where fewer than n entries exist the missing rows
+    are all `pad` with score -inf."""
     import numpy as np
     hist_tok, hist_parent, len_norm = state["hist_tok"], state["hist_parent"], state["len_norm"]
     length, eos = int(state.get("length", hist_tok.shape[0])), int(state.get("eos", -1))
@@ -163,21 +212,25 @@ def _beam_finalize(state, L0, prompt_ids, nb, pad):
             row = int(hist_parent[p, row])
         return toks[::-1]
 
-    out = []
+    out, scores = [], []
     for s in range(state["score"].shape[0]):
         hyps = [(np.float32(state["hyp_score"][s, j]), (int(state["hyp_row"][s, j]), int(state["hyp_len"][s, j]) - 2, [eos]))
                 for j in range(int(state["n_hyp"][s]))]
         if not state["done"][s]:
             hyps += [(np.float32(state["score"][s, k]) / np.float32(len_norm[length]), (s * nb + k, length - 1, []))
                      for k in range(nb) if state["score"][s, k] > -np.inf]
-        best = 0
-        for j in range(1, len(hyps)):
-            if hyps[j][0] > hyps[best][0]:
-                best = j
-        row, last, tail = hyps[best][1]
-        out.append([int(t) for t in prompt[s]] + backtrack(row, last) + tail)
+        order = sorted(range(len(hyps)), key=lambda j: -hyps[j][0])            # (a stable sort: the earlier entry on equal scores)
+        for j in range(1 if n_return is None else n_return):
+            if j < len(order):
+                row, last, tail = hyps[order[j]][1]
+                out.append([int(t) for t in prompt[s]] + backtrack(row, last) + tail)
+                scores.append(hyps[order[j]][0])
+            else:
+                out.append([])
+                scores.append(np.float32(-np.inf))
     width = max(len(o) for o in out)
-    return torch.tensor([o + [pad] * (width - len(o)) for o in out], dtype=torch.long)
+    ids = torch.tensor([o + [pad] * (width - len(o)) for o in out], dtype=torch.long)
+    return ids if n_return is None else (ids, torch.from_numpy(np.asarray(scores, np.float32)))
 
 
 class _DecodeSession:
@@ -196,10 +249,10 @@ class _DecodeSession:
 
     nb = 1                                 # rows per sequence
 
-    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None):
+    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None, logprobs=False):
         from transformers.cache_utils import StaticCache
         self._model_ref = weakref.ref(model)
-        self.sampling, self.beams, self.processors = sampling, beams, processors
+        self.sampling, self.beams, self.processors, self.logprobs = sampling, beams, processors, logprobs
         self.n_seq = b
         b = b * self.nb
         self.b, self.max_length, self.eos, self.graph_wanted = b, max_length, eos, graph
@@ -264,7 +317,7 @@ class _DecodeSession:
         self._append(o.logits[:, -1])
 
     @torch.no_grad()
-    def run(self, ids, ml, am, pixel_values, visual_features, generator=None):
+    def run(self, ids, ml, am, pixel_values, visual_features, generator=None, n_return=None):
         L0, prompt_ids = ids.shape[1], ids
         ids, ml, am, pixel_values, visual_features = self._begin(ids, ml, am, pixel_values, visual_features, generator)
         self.cache.reset()
@@ -307,7 +360,7 @@ class _DecodeSession:
             i += 1
             if self.eos is not None and i % 16 == 0 and bool(all_done.all()):          # (a host sync: only every 16 tokens)
                 break
-        return self._result(L0, prompt_ids, self.max_length - remaining + i)
+        return self._result(L0, prompt_ids, self.max_length - remaining + i, n_return)
 
 
 class _TokenSession(_DecodeSession):
@@ -317,7 +370,10 @@ class _TokenSession(_DecodeSession):
     the logits in their own dtype, csrc/ff_sample.hip) instead of the argmax.  The random numbers of a whole call are drawn before the
     prompt step, outside any capture, into `u_all` (max_length, b): row `pos` serves the token written at position `pos` and the captured
     step picks it with a device-side index_select on `pos`, so the graph holds no random-number generation and eager and replayed steps
-    consume identical numbers.  The processors read `ids_buf`, which already is the sequence."""
+    consume identical numbers.  The processors read `ids_buf`, which already is the sequence.
+    `logprobs` makes _select record the chosen token's log-probability (functional.token_logprobs on the processed logits, one launch inside
+    the captured step) into column `pos` of `lp_buf` (b, max_length) float32; a session without it allocates neither buffer and never
+    calls the function."""
 
     def _alloc(self):
         dev = self.pos.device
@@ -328,6 +384,9 @@ class _TokenSession(_DecodeSession):
             self.nxt = torch.zeros((self.b,), dtype=torch.long, device=dev)
         if self.processors is not None:
             self._alloc_min_len()
+        if self.logprobs:
+            self.lp_step = torch.zeros((self.b,), dtype=torch.float32, device=dev)
+            self.lp_buf = torch.zeros((self.b, self.max_length), dtype=torch.float32, device=dev)
 
     def _begin(self, ids, ml, am, pixel_values, visual_features, generator):
         if self.sampling is not None:
@@ -336,6 +395,8 @@ class _TokenSession(_DecodeSession):
         self.n_new.zero_()
         if self.processors is not None:
             self.min_len.fill_(self.processors.min_len(ids.shape[1]))
+        if self.logprobs:
+            self.lp_buf.zero_()
         return ids, ml, am, pixel_values, visual_features
 
     def _history(self):
@@ -346,6 +407,10 @@ class _TokenSession(_DecodeSession):
             nxt = logits.float().argmax(-1)
         else:
             nxt = F.sample_tokens(logits, self.u_all.index_select(0, self.pos).view(-1), *self.sampling, out=self.nxt)
+        if self.logprobs:                  # the chosen token's log-softmax, 0 for a row that had finished (one launch, csrc/ff_logprob.hip);
+            # `finished` still is what it was before this step: _pad_finished below updates it after the launch, in stream order
+            F.token_logprobs(logits, nxt, skip=self.finished, out=self.lp_step)
+            self.lp_buf.index_copy_(1, self.pos, self.lp_step[:, None])
         alive = ~self.finished.all()
         if self.eos is not None:
             nxt = _pad_finished(nxt, self.finished, self.eos, self.fill)
@@ -356,8 +421,9 @@ class _TokenSession(_DecodeSession):
     def _all_done(self):
         return self.finished
 
-    def _result(self, L0, prompt_ids, length):
-        return self.ids_buf[:, :L0 + int(self.n_new)].clone() if self.eos is not None else self.ids_buf.clone()
+    def _result(self, L0, prompt_ids, length, n_return=None):
+        ids = self.ids_buf[:, :L0 + int(self.n_new)].clone() if self.eos is not None else self.ids_buf.clone()
+        return (ids, self.lp_buf[:, L0:ids.shape[1]].clone()) if self.logprobs else ids
 
 
 class _BeamSession(_DecodeSession):
@@ -412,24 +478,29 @@ class _BeamSession(_DecodeSession):
     def _all_done(self):
         return self.state.done
 
-    def _result(self, L0, prompt_ids, length):    # one device-to-host copy; steps past the last `done` only wrote padding
+    def _result(self, L0, prompt_ids, length, n_return=None):    # one device-to-host copy; steps past the last `done` only wrote padding
         host = self.state.to_host()
         host["length"] = length
-        return _beam_finalize(host, L0, prompt_ids.cpu(), self.nb, self.fill).to(prompt_ids.device)
+        res = _beam_finalize(host, L0, prompt_ids.cpu(), self.nb, self.fill, n_return=n_return)
+        return res.to(prompt_ids.device) if n_return is None else tuple(t.to(prompt_ids.device) for t in res)
 
 
-def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, beams=None, processors=None):
+def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, beams=None, processors=None,
+                   logprobs=False, n_return=None):
     """Greedy, sampled (`sampling`) or beam-search (`beams`) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches
     and buffers plus, on the GPU, the captured HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, device,
     eos, pad, graph, sampling, beams, processors) and reused by later calls, so only the first caption batch of a shape pays for the
     capture.  A session whose model's parameters were re-allocated since (model.to(), ShardedAdamW) is rebuilt;
-    FlamingoModel.reset_decode_sessions() drops them all."""
+    FlamingoModel.reset_decode_sessions() drops them all.
+    `logprobs` (greedy and sampling) selects a session that records the chosen tokens' log-probabilities: its key is the same ten elements
+    followed by "logprobs", and the call returns (ids, token_logprobs).  `n_return` (beam search) returns (ids, scores) with the n best
+    entries per sequence (_beam_finalize); it changes nothing in the session."""
     b = ids.shape[0]
     graph = ids.is_cuda and not model.training and model.decode_graph
     sessions = _DECODE_SESSIONS.setdefault(model, {})
     n_media = int(ml.sum(-1).max()) if visual_features is None and pixel_values is None else \
         (visual_features.shape[1] if visual_features is not None else (pixel_values.shape[1] if pixel_values.ndim >= 5 else pixel_values.shape[0]))
-    key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams, processors)
+    key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams, processors) + (("logprobs",) if logprobs else ())
     sess = sessions.get(key)
     if sess is not None and sess.stale():
         sessions.pop(key)
@@ -438,14 +509,18 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
         if len(sessions) >= 4:                                                # a handful of shapes at most: each holds a KV cache and a graph
             sessions.pop(next(iter(sessions)))
         cls = _TokenSession if beams is None else _BeamSession
-        sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors)
-    return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator)
+        sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors, logprobs=logprobs)
+    return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator, n_return=n_return)
 
 
 # ---- the dynamic path: growing caches, one forward per step (the only path on CPU tensors, and what the sessions are tested against) ----
-def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, processors=None):
-    """Greedy or, with `sampling`, multinomial decoding over the cached decode path; `step` is FlamingoModel._decode_step."""
+def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, processors=None,
+                   logprob_dtype=None):
+    """Greedy or, with `sampling`, multinomial decoding over the cached decode path; `step` is FlamingoModel._decode_step.
+    With `logprob_dtype` (torch.float32, or torch.float64 for a model that computes in float64) it returns (ids, token_logprobs): the
+    log-softmax of the processed logits at the chosen token, taken in that dtype, 0 for a row that had finished before the step."""
     finished = torch.zeros(ids.shape[0], dtype=torch.bool, device=ids.device)
+    lps = []
     past, step_ids = None, ids
     process = _dynamic_processor(processors, eos, ids.shape[1])
     while ids.shape[1] < max_length:
@@ -455,6 +530,9 @@ def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length,
             nxt = torch.multinomial(filter_logits(logits, *sampling).softmax(-1), 1, generator=generator)[:, 0]
         else:
             nxt = logits.argmax(-1)
+        if logprob_dtype is not None:
+            lp = logits.to(logprob_dtype).log_softmax(-1).gather(1, nxt[:, None])[:, 0]
+            lps.append(torch.where(finished, torch.zeros_like(lp), lp))
         if eos is not None:
             nxt = _pad_finished(nxt, finished, eos, pad)
         ids = torch.cat([ids, nxt[:, None]], dim=1)
@@ -463,13 +541,18 @@ def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length,
         step_ids = ids[:, -1:]
         if eos is not None and bool(finished.all()):
             break
+    if logprob_dtype is not None:
+        return ids, (torch.stack(lps, dim=1) if lps else torch.zeros((ids.shape[0], 0), dtype=logprob_dtype, device=ids.device))
     return ids
 
 
-def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None):
+def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None,
+                n_return=None):
     """Standard beam search over the cached decode path; `step` / `reorder_cache` are FlamingoModel._decode_step / ._reorder_cache.  The
     prompt runs once per sequence; its caches are then replicated per beam (xattn K/V: repeat_interleave; LM cache:
-    Cache.batch_repeat_interleave) and re-ordered every step.  `processors` act on every step's logits before the log-softmax."""
+    Cache.batch_repeat_interleave) and re-ordered every step.  `processors` act on every step's logits before the log-softmax.
+    With `n_return` = n it returns (ids (b * n, width), scores (b * n,) float32): per sequence the n best of what the tail ranks, best first,
+    the earlier entry on equal scores, with their normalised scores; missing rows are all pad with score -inf (as _beam_finalize)."""
     b, L0 = ids.shape
     dev = ids.device
     process = _dynamic_processor(processors, eos, L0)
@@ -528,13 +611,20 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
         am = torch.cat([am, torch.ones_like(am[:, :1])], dim=1)
         logits, past = step(seqs[:, -1:], ml, am, past, None, None)
         logp = process(logits, seqs).log_softmax(-1)
-    out = []
+    out, out_scores = [], []
     for bi in range(b):
         hyps = list(done_hyps[bi])
         if not is_done[bi]:                                           # length limit: the open beams count as hypotheses too
             hyps += [(float(scores[bi, k]) / (seqs.shape[1] ** length_penalty), seqs[bi * nb + k].tolist()) for k in range(nb)
                      if float(scores[bi, k]) > float("-inf")]
-        out.append(max(hyps, key=lambda t: t[0])[1])
+        if n_return is None:
+            out.append(max(hyps, key=lambda t: t[0])[1])
+            continue
+        ranked = sorted(hyps, key=lambda t: -t[0])[:n_return]         # (a stable sort: the earlier entry on equal scores)
+        ranked += [(float("-inf"), [])] * (n_return - len(ranked))
+        out += [h[1] for h in ranked]
+        out_scores += [h[0] for h in ranked]
     width = max(len(o) for o in out)
     fill = pad if pad is not None else 0
-    return torch.tensor([o + [fill] * (width - len(o)) for o in out], dtype=torch.long, device=dev)
+    ids = torch.tensor([o + [fill] * (width - len(o)) for o in out], dtype=torch.long, device=dev)
+    return ids if n_return is None else (ids, torch.tensor(out_scores, dtype=torch.float32, device=dev))

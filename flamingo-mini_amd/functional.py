@@ -993,6 +993,32 @@ def process_logits(logits: torch.Tensor, hist: torch.Tensor, hist_len: torch.Ten
     return logits
 
 
+def token_logprobs(logits: torch.Tensor, token: torch.Tensor, skip: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   lse: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """log_softmax(logits[r])[token[r]] per row of `logits` (rows, V), float32 / bfloat16 on the GPU, in float32: ff_token_logprob, one launch
+    that reads each row once and never writes it; the exact rules are in include/flamingo_fusion.h.  Only the last dimension has to be
+    contiguous (logits3d[:, -1] is read in place through its row stride).  `token`: rows int64.  `skip` (rows, bool / uint8): a row whose flag
+    is set gives exactly 0 and is not read.  `lse` (rows, float32) receives the row's logsumexp.  A token outside [0, V) gives NaN.  With
+    `out` (float32, rows, contiguous) nothing is allocated, so the call can be captured into a graph."""
+    ffi.require_cuda(logits, token, skip, out, lse)
+    if logits.ndim != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"token_logprobs: logits must be (rows, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
+    rows, V = logits.shape
+    if token.dtype != torch.long or token.numel() != rows or not token.is_contiguous():
+        raise ValueError(f"token_logprobs: token must be {rows} contiguous int64 values, got {tuple(token.shape)} {token.dtype}")
+    if skip is not None and (skip.dtype not in (torch.bool, torch.uint8) or skip.numel() != rows or not skip.is_contiguous()):
+        raise ValueError(f"token_logprobs: skip must be {rows} contiguous bool / uint8 values, got {tuple(skip.shape)} {skip.dtype}")
+    if out is None:
+        out = _new((rows,), torch.float32, logits.device)
+    for name, t in (("out", out), ("lse", lse)):
+        if t is not None and (t.dtype != torch.float32 or t.shape != (rows,) or not t.is_contiguous()):
+            raise ValueError(f"token_logprobs: {name} must be {rows} contiguous float32 values, got {tuple(t.shape)} {t.dtype}")
+    ld = logits.stride(0) if rows > 1 else V
+    ffi.check(ffi.lib().ff_token_logprob(ffi.dtype_code(logits.dtype), rows, V, ld, logits.data_ptr(), token.data_ptr(), ffi.ptr(skip), out.data_ptr(),
+                                         ffi.ptr(lse), ffi.stream_handle(logits.device)), "ff_token_logprob")
+    return out
+
+
 class BeamState:
     """The device state block of ff_beam_step for b sequences x nb beams and histories of max_len positions (layout and rules:
     include/flamingo_fusion.h).  All fields are views of ONE byte buffer, so `to_host()` is one device-to-host copy.  `storage` (uint8,

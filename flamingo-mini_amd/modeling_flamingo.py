@@ -439,7 +439,8 @@ class FlamingoModel(PreTrainedModel):
                  top_p: float = 1.0, eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, bos_token_id: Optional[int] = None,
                  early_stopping: bool = True, length_penalty: float = 1.0, use_cache: bool = True, generator: Optional[torch.Generator] = None,
                  input_ids=None, static_decode: Optional[bool] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
-                 min_length: int = 0, min_new_tokens: int = 0, **unsupported):
+                 min_length: int = 0, min_new_tokens: int = 0, return_dict_in_generate: bool = False, output_logprobs: bool = False,
+                 num_return_sequences: int = 1, **unsupported):
         """Text generation with the cached cross-attention path: the first step runs CLIP + resampler and fills the xattn K/V and LM caches,
         every later step feeds one token (reference: HF `generate` through prepare_inputs_for_generation / _reorder_cache, :464-548).
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
@@ -457,23 +458,58 @@ class FlamingoModel(PreTrainedModel):
         (functional.process_logits; int64 ids, max_length <= 4096 - otherwise the dynamic loop runs), on the dynamic paths the torch
         restatement _process_logits.  They are offered for GPU tensors only: with CPU tensors generate() raises TypeError for them, as it
         did before they existed (the processor kernel has no CPU form; static_decode=True raises what ffi.require_cuda raises).  Deliberate deviation from transformers in beam search: the log-softmax is taken AFTER the processors, so
-        the mass of banned tokens is renormalised over the rest, where transformers penalises log-probabilities without renormalising."""
+        the mass of banned tokens is renormalised over the rest, where transformers penalises log-probabilities without renormalising.
+        Outputs: `return_dict_in_generate=True` returns a decoding.GenerateOutput (sequences, sequences_scores, token_logprobs) instead of
+        the ids.  `output_logprobs=True` (greedy and sampling; needs return_dict_in_generate) fills token_logprobs, aligned with
+        sequences[:, L0:]: the log-softmax, at the chosen token, of the step's logits as the selection sees them - after the logits
+        processors, before temperature / top-k / top-p -, 0 at the pad positions of a row that had finished; and sequences_scores =
+        sum(token_logprobs) / float32(len ** length_penalty), len counting the prompt and the generated tokens up to and including eos.
+        On the static path they are float32 from one launch inside the replayed step (functional.token_logprobs, GPU tensors only; with
+        static_decode=None CPU tensors take the dynamic loop); the dynamic loop takes torch's log_softmax in float32 (float64 for a float64
+        model).  With beam search sequences_scores is the normalised score the search ranked by, and output_logprobs raises ValueError.
+        `num_return_sequences=n`: sampling repeats every sequence n times (the visuals are encoded once per sequence), beam search (n <=
+        num_beams) returns the n best of the hypotheses and open beams its tail ranks, best first, missing ones all pad with score -inf;
+        output rows s * n + j.  Greedy decoding has one result: n > 1 raises ValueError."""
         procs = D.check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos_token_id)
+        n_ret = D.check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample)
         ids = inputs if inputs is not None else input_ids
         assert ids is not None and media_locations is not None, "generate() needs input ids and media_locations"
         am = attention_mask if attention_mask is not None else torch.ones_like(ids)
         ml = media_locations
         pad = pad_token_id if pad_token_id is not None else eos_token_id
         path = D.route(is_cuda=ids.is_cuda, num_beams=num_beams, do_sample=do_sample, static_decode=static_decode, model_default=self.static_decode, lm_family=self.flamingo.lm_family,
-                       L0=ids.shape[1], max_length=max_length, ids_is_int64=ids.dtype == torch.long, procs_on=procs is not None, procs_given=procs.given() if procs is not None else ())
+                       L0=ids.shape[1], max_length=max_length, ids_is_int64=ids.dtype == torch.long, procs_on=procs is not None, procs_given=procs.given() if procs is not None else (),
+                       logprobs_on=bool(output_logprobs))
+        if n_ret > 1 and num_beams <= 1:                                     # sampling: every sequence n times, its visuals encoded once
+            if visual_features is None and pixel_values is not None:
+                visual_features, pixel_values = self.flamingo.encode_resample_visuals(pixel_values), None
+            ids, ml, am = _repeat_leading(ids, n_ret), _repeat_leading(ml, n_ret), _repeat_leading(am, n_ret)
+            if visual_features is not None:
+                visual_features = _repeat_leading(visual_features, n_ret)
+        n_beams_out = n_ret if num_beams > 1 and (return_dict_in_generate or n_ret > 1) else None      # None: the search's single result, as ever
         if path == "static":
-            return D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, generator=generator, processors=procs,
-                                    sampling=D.Sampling(float(temperature), int(top_k), float(top_p)) if do_sample else None,
-                                    beams=D.Beams(int(num_beams), bool(early_stopping), float(length_penalty)) if num_beams > 1 else None)
-        if num_beams > 1:
-            return self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty, processors=procs)
-        return D.dynamic_decode(self._decode_step, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
-                                sampling=D.Sampling(temperature, top_k, top_p) if do_sample else None, generator=generator, processors=procs)
+            res = D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, generator=generator, processors=procs,
+                                   sampling=D.Sampling(float(temperature), int(top_k), float(top_p)) if do_sample else None,
+                                   beams=D.Beams(int(num_beams), bool(early_stopping), float(length_penalty)) if num_beams > 1 else None,
+                                   logprobs=bool(output_logprobs), n_return=n_beams_out)
+        elif num_beams > 1:
+            res = self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty, processors=procs,
+                                    n_return=n_beams_out)
+        else:
+            # the log-softmax is taken in float32, the dtype of the logits _decode_step hands the loop; a model that computes in float64 keeps
+            # its precision (a float32 log-softmax would throw away what a float64 evaluation on the host is run for)
+            lp_dtype = (torch.float64 if next(self.parameters()).dtype == torch.float64 else torch.float32) if output_logprobs else None
+            res = D.dynamic_decode(self._decode_step, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
+                                   sampling=D.Sampling(temperature, top_k, top_p) if do_sample else None, generator=generator, processors=procs,
+                                   logprob_dtype=lp_dtype)
+        if not return_dict_in_generate:
+            return res[0] if n_beams_out else res
+        if n_beams_out:
+            return D.GenerateOutput(sequences=res[0], sequences_scores=res[1])
+        if output_logprobs:
+            seqs, lps = res
+            return D.GenerateOutput(sequences=seqs, token_logprobs=lps, sequences_scores=D.sequence_scores(seqs, lps, ids.shape[1], eos_token_id, float(length_penalty)))
+        return D.GenerateOutput(sequences=res)
 
     @property
     def _decode_sessions(self) -> dict:
@@ -482,16 +518,20 @@ class FlamingoModel(PreTrainedModel):
     def reset_decode_sessions(self) -> None:
         D._DECODE_SESSIONS.pop(self, None)
 
-    def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None):
+    def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None, n_return=None):
         """The dynamic beam search (decoding.beam_search) over this model's _decode_step / _reorder_cache."""
-        return D.beam_search(self._decode_step, self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors)
+        return D.beam_search(self._decode_step, self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors,
+                             n_return=n_return)
 
     @torch.no_grad()
     def generate_captions(self, processor, pixel_values=None, images=None, prompt: str = "<image>", max_length: int = 150,
-                          num_beams: int = 1, device=None, **kwargs):
+                          num_beams: int = 1, device=None, return_scores: bool = False, **kwargs):
         """Caption a batch of images; the prompt is replicated for every image (reference :550-605).  `kwargs` are generation
         arguments (do_sample, temperature, top_k, top_p, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length,
-        min_new_tokens, ...) and go to generate(), which rejects unknown ones."""
+        min_new_tokens, num_return_sequences, output_logprobs, return_dict_in_generate, ...) and go to generate(), which rejects unknown ones.
+        `return_scores=True` returns (captions, scores), the scores floats from GenerateOutput.sequences_scores (beam search: the score the
+        search ranked by; greedy and sampling: the length-normalised sum of the token log-probabilities).  With num_return_sequences = n > 1
+        the captions (and the scores) are a list of one list of n per image."""
         if device is None:
             device = self.device
         if images is not None:
@@ -508,11 +548,18 @@ class FlamingoModel(PreTrainedModel):
         lm_cfg = self.flamingo.lm.config
         if pixel_values.ndim == 4:
             pixel_values = pixel_values[:, None]       # (b c h w) -> one image per sequence
-        out_ids = self.generate(inputs=input_ids, media_locations=media_locations, attention_mask=attention_mask, pixel_values=pixel_values,
-                                num_beams=num_beams, early_stopping=True, use_cache=True, bos_token_id=lm_cfg.bos_token_id,
-                                eos_token_id=lm_cfg.eos_token_id, pad_token_id=lm_cfg.eos_token_id, max_length=max_length, **kwargs)
-        captions = processor.tokenizer.batch_decode(out_ids, skip_special_tokens=True)
-        return [processor.remove_tags(t) for t in captions]
+        if return_scores:                              # the scores come with the output object; sampling and greedy need the token values for them
+            kwargs = dict(kwargs, return_dict_in_generate=True, output_logprobs=num_beams <= 1)
+        out = self.generate(inputs=input_ids, media_locations=media_locations, attention_mask=attention_mask, pixel_values=pixel_values,
+                            num_beams=num_beams, early_stopping=True, use_cache=True, bos_token_id=lm_cfg.bos_token_id,
+                            eos_token_id=lm_cfg.eos_token_id, pad_token_id=lm_cfg.eos_token_id, max_length=max_length, **kwargs)
+        out_ids = out.sequences if isinstance(out, D.GenerateOutput) else out
+        captions = [processor.remove_tags(t) for t in processor.tokenizer.batch_decode(out_ids, skip_special_tokens=True)]
+        n = kwargs.get("num_return_sequences", 1)
+        group = (lambda v: [v[i:i + n] for i in range(0, len(v), n)]) if n > 1 else (lambda v: v)
+        if return_scores:
+            return group(captions), group([float(s) for s in out.sequences_scores.tolist()])
+        return group(captions)
 
     @torch.no_grad()
     def score_sequences(self, input_ids, media_locations, attention_mask, pixel_values=None, visual_features=None,

@@ -54,7 +54,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, additions only: beam search on the captured decode step, ff_beam_step, ff_beam_gather;
                                 * still 6, additions only: stochastic rounding for pure-bf16 training, ff_adamw_step_sr, ff_stochastic_round_bf16;
                                 * still 6, addition only: logits processors on the captured decode step, ff_logits_process;
-                                * still 6, addition only: exponential moving average of the weights, ff_ema_update) */
+                                * still 6, addition only: exponential moving average of the weights, ff_ema_update;
+                                * still 6, addition only: log-probability of the chosen token on the captured decode step, ff_token_logprob) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -647,6 +648,24 @@ int ff_logits_process(int dtype, int rows, int vocab, long long ld, void* logits
                       const long long* hist, long long hist_ld, long long hist_cap, const long long* hist_len,
                       float repetition_penalty, int no_repeat_ngram_size, int eos, const long long* min_len,
                       ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Log-probability of a chosen token (added under ABI 6): logprob[r] = x_tok - logsumexp(x) for the rows a decode step just selected
+ * from.  One launch, no atomics, no allocation, no host synchronisation, capturable; equal inputs give equal bits, eager or replayed.
+ * logits: `rows` rows of `vocab` elements of `dtype` (FF_DTYPE_F32 / FF_DTYPE_BF16), row r at element r * ld, ld >= vocab, element alignment
+ * only (the contract of ff_sample_token: logits[:, -1] of a (batch, seq, vocab) tensor works in place); never written.  token: rows int64.
+ * skip: rows bytes, or null.  logprob: rows fp32.  lse: rows fp32, or null.
+ * Per row, fp32 math in the order of ff_shifted_ce_fwd (one 256-thread workgroup, (max, sum) pairs, a fixed wave and block combine,
+ * lse = M + logf(S)): for a row at the same address lse has the bits ff_shifted_ce_fwd stores, and logprob == -loss_row bit for bit.
+ *   logprob[r] = x_tok - lse, and lse[r] = lse when lse is not null;
+ *   token[r] outside [0, vocab): logprob[r] = NaN, nothing is read out of bounds;
+ *   x_tok == -inf: -inf; -inf at other columns contributes 0; a row holding NaN or +inf: NaN;
+ *   skip[r] != 0: logprob[r] = 0 and lse[r] = 0 exactly, the row is not read.
+ * FF_ERR_SHAPE: null logits, token or logprob; rows <= 0, vocab <= 0, ld < vocab.  FF_ERR_UNSUPPORTED: another dtype.  Both before any
+ * launch.
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_token_logprob(int dtype, int rows, int vocab, long long ld, const void* logits, const long long* token, const unsigned char* skip,
+                     float* logprob, float* lse, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * QuickGELU of the CLIP vision tower, y = x * sigmoid(1.702 x) (transformers.activations.QuickGELUActivation, selected by
