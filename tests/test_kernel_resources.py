@@ -80,3 +80,55 @@ def test_selection_kernels_keep_their_functors_out_of_scratch():
                 assert r["scratch"] == 0, (r["name"], r["scratch"])
                 seen[family] += 1
     assert seen == {"sample_token_kernel": 3, "beam_rows_kernel": 3}, seen
+
+
+@pytest.mark.parametrize("unit, kernel, others", [
+    ("ff_logits", "logits_process_kernel", ("sample_token_kernel", "beam_rows_kernel")),
+    ("ff_logprob", "token_logprob_kernel", ("sample_token_kernel", "beam_rows_kernel", "logits_process_kernel", "shifted_ce_")),
+], ids=["ff_logits", "ff_logprob"])
+def test_the_unit_is_reported_and_its_kernels_use_no_scratch(unit, kernel, others):
+    """ff_logits sits in front of every replayed decode step's selection, ff_logprob inside every step of a session that records
+    log-probabilities (at the occupancy of the loss forward whose row pass it restates): a spill would put a memory round trip into a
+    launch that does a handful of loads and stores.  Both instantiations are there, and their names stay clear of the kernels other
+    resource tests count by name."""
+    mine = [r for r in ROWS if r["unit"] == unit]
+    assert len(mine) == 2 and all(kernel in r["mangled"] for r in mine), [r["name"] for r in mine]
+    assert len({r["mangled"] for r in mine}) == 2
+    for r in mine:
+        assert r["scratch"] == 0 and r["occupancy"] >= 8, (r["name"], r["scratch"], r["vgprs"], r["occupancy"])
+        for other in others:
+            assert other not in r["mangled"], r["mangled"]
+
+
+def test_the_regularised_loss_kernels_are_reported_without_scratch_at_the_plain_occupancy():
+    """The regularised instantiations of the two loss kernels - the ones with the trailing (float, float) pack - ride on passes that stream
+    the logits: a spill or a lost wave against the plain instantiation of the same kernel and type would cost those passes their bandwidth."""
+    mine = [r for r in ROWS if r["unit"] == "ff_loss"]
+    assert len(mine) == 8 and all("shifted_ce_" in r["mangled"] for r in mine), [r["name"] for r in mine]
+    for kernel in ("shifted_ce_fwd_kernel", "shifted_ce_bwd_kernel"):
+        for dtype in ("DF16b", "f"):                                     # the Itanium codes of __bf16 and float
+            plain = [r for r in mine if f"{kernel}I{dtype}JEE" in r["mangled"]]
+            reg = [r for r in mine if f"{kernel}I{dtype}JffEE" in r["mangled"]]
+            assert len(plain) == 1 and len(reg) == 1, (kernel, dtype, [r["mangled"] for r in mine])
+            for r in plain + reg:
+                assert r["scratch"] == 0, (r["name"], r["scratch"])
+            assert reg[0]["occupancy"] >= plain[0]["occupancy"] >= 8, (kernel, dtype, reg[0]["vgprs"], reg[0]["occupancy"], plain[0]["occupancy"])
+
+
+def test_the_ema_kernel_is_reported_without_scratch_at_the_accumulate_kernels_occupancy():
+    """ema_update_kernel, for bf16 and for fp32 weights, is held to the floor of grad_accumulate_kernel, its nearest relative (one stream
+    in, one fp32 read-modify-write stream): 7 waves per SIMD, no scratch, no LDS."""
+    unit = [r for r in ROWS if r["unit"] == "ff_optim"]
+    mine = [r for r in unit if "ema_update_kernel" in r["mangled"]]
+    assert len(mine) == 2 and not any("adamw_kernel" in r["mangled"] for r in mine), [r["mangled"] for r in mine]
+    for dtype in ("DF16b", "f"):                                         # the Itanium codes of __bf16 and float
+        row = [r for r in mine if f"ema_update_kernelI{dtype}E" in r["mangled"]]
+        assert len(row) == 1, (dtype, [r["mangled"] for r in mine])
+        assert row[0]["scratch"] == 0 and row[0].get("lds", 0) == 0, row[0]
+        assert row[0]["occupancy"] >= 7, (row[0]["name"], row[0]["vgprs"], row[0]["occupancy"])
+
+
+def test_the_adamw_instantiations_are_the_33_there_were():
+    """The weight average came as a kernel of its own: the unit keeps its 33 adamw_kernel instantiations (21 round-to-nearest, 12
+    stochastic-rounding)."""
+    assert sum("adamw_kernel" in r["mangled"] for r in ROWS if r["unit"] == "ff_optim") == 33

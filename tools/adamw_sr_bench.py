@@ -14,14 +14,11 @@ gradients, moments, master copies), the rate that gives, the median per-round di
 state each arm keeps per parameter.  The model is only built for its shapes and dropped before anything is timed."""
 import argparse
 import json
-import os
 import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
 ARMS = {   # name: (FusedAdamW arguments, bytes moved per parameter and step, bytes of optimizer state per parameter)
     "rne": (dict(), 2 * 2 + 2 + 2 * 2 * 2, 4),
@@ -38,62 +35,23 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    saved, sys.argv = sys.argv, [sys.argv[0], "--config", a.config]
-    import bench
-    args = bench.parse()
-    sys.argv = saved
-    from flamingo_mini_amd import FusedAdamW, ffi
-    ffi.lib()
     device = torch.device("cuda", 0)
-    model, _ = bench.build_model(args, device, torch.bfloat16)
-    shapes = [tuple(p.shape) for p in model.parameters_trainable()]
-    del model
-    torch.cuda.empty_cache()
+    shapes = benchlib.trainable_shapes(a.config, device)
     n_params = sum(torch.Size(s).numel() for s in shapes)
-    gen = torch.Generator(device=device).manual_seed(1)
-    grads = [(torch.randn(s, generator=gen, device=device) * 1e-3).to(torch.bfloat16) for s in shapes]
-    graphs, opts = {}, {}
-    for name, (kw, _, _) in ARMS.items():
-        params = [torch.nn.Parameter((torch.randn(s, generator=gen, device=device) * 0.02).to(torch.bfloat16)) for s in shapes]
-        for p, g in zip(params, grads):
-            p.grad = g
-        opt = opts[name] = FusedAdamW(params, lr=1e-4, capturable=True, **kw)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                          # the eager step allocates the state and the device counters
-            opt.step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graphs[name] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[name]):
-            opt.step()
-    times = {k: [] for k in ARMS}
-    for _ in range(a.rounds):
-        for name, graph in graphs.items():
-            graph.replay()                                     # (one untimed replay after switching)
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(a.steps):
-                graph.replay()
-            t1.record()
-            t1.synchronize()
-            times[name].append(t0.elapsed_time(t1) / a.steps)
+    graphs, opts = benchlib.capture_arms(shapes, {name: kw for name, (kw, _, _) in ARMS.items()}, device)
+    times = benchlib.replay_rounds({name: graph.replay for name, graph in graphs.items()}, a.rounds, a.steps)
     out = dict(config=a.config, tensors=len(shapes), trainable_params=n_params, rounds=a.rounds, steps_per_round=a.steps)
     for name, (_, per_param, state) in ARMS.items():
         ms = statistics.median(times[name])
-        out[name] = dict(ms_median=round(ms, 4), ms_all=[round(t, 4) for t in times[name]], bytes_per_step=per_param * n_params,
+        ms_median, ms_all = benchlib.ms_summary(times[name])
+        out[name] = dict(ms_median=ms_median, ms_all=ms_all, bytes_per_step=per_param * n_params,
                          tb_per_s=round(per_param * n_params / (ms * 1e-3) / 1e12, 3), state_bytes_per_param=state,
                          steps_taken=int(float(opts[name].state_dict()["state"][0]["step"])))
     for name in ("sr", "sr_f32", "master"):
-        out[f"{name}_minus_rne_ms_median"] = round(statistics.median([x - y for x, y in zip(times[name], times["rne"])]), 4)
+        out[f"{name}_minus_rne_ms_median"] = benchlib.median_diff(times, name, "rne")
     for name in ("sr", "sr_f32"):
-        out[f"{name}_minus_master_ms_median"] = round(statistics.median([x - y for x, y in zip(times[name], times["master"])]), 4)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+        out[f"{name}_minus_master_ms_median"] = benchlib.median_diff(times, name, "master")
+    benchlib.emit(json.dumps(out), a.out)
 
 
 if __name__ == "__main__":

@@ -17,14 +17,11 @@ average over 8 steps), the rate that gives, the per-round differences against pl
 pass alone (10 bytes per parameter over ema - plain).  The model is only built for its shapes and dropped before anything is timed."""
 import argparse
 import json
-import os
 import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
 ADAMW_BYTES = 2 * 2 + 2 + 2 * 2 * 2      # parameter read + write, gradient read, two moments read + write (all bf16)
 EMA_BYTES = 2 + 2 * 4                    # parameter read, fp32 shadow read + write
@@ -45,56 +42,23 @@ def main():
     a = ap.parse_args()
     if a.steps % 8:
         ap.error("--steps must be a multiple of 8 (ema8 averages on every 8th step)")
-    saved, sys.argv = sys.argv, [sys.argv[0], "--config", a.config]
-    import bench
-    args = bench.parse()
-    sys.argv = saved
-    from flamingo_mini_amd import FusedAdamW, ffi
-    ffi.lib()
     device = torch.device("cuda", 0)
-    model, _ = bench.build_model(args, device, torch.bfloat16)
-    shapes = [tuple(p.shape) for p in model.parameters_trainable()]
-    del model
-    torch.cuda.empty_cache()
+    shapes = benchlib.trainable_shapes(a.config, device)
     n_params = sum(torch.Size(s).numel() for s in shapes)
-    gen = torch.Generator(device=device).manual_seed(1)
-    grads = [(torch.randn(s, generator=gen, device=device) * 1e-3).to(torch.bfloat16) for s in shapes]
-    graphs, opts = {}, {}
-    for name, (kw, _, _) in ARMS.items():
-        params = [torch.nn.Parameter((torch.randn(s, generator=gen, device=device) * 0.02).to(torch.bfloat16)) for s in shapes]
-        for p, g in zip(params, grads):
-            p.grad = g
-        opt = opts[name] = FusedAdamW(params, lr=1e-4, capturable=True, **kw)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                          # the eager step allocates the state, the shadows and the device counters
-            opt.step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graphs[name] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graphs[name]):
-            opt.step()
-    times = {k: [] for k in ARMS}
-    for _ in range(a.rounds):
-        for name, graph in graphs.items():
-            graph.replay()                                     # (one untimed replay after switching)
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(a.steps):
-                graph.replay()
-            t1.record()
-            t1.synchronize()
-            times[name].append(t0.elapsed_time(t1) / a.steps)
+    graphs, opts = benchlib.capture_arms(shapes, {name: kw for name, (kw, _, _) in ARMS.items()}, device)
+    times = benchlib.replay_rounds({name: graph.replay for name, graph in graphs.items()}, a.rounds, a.steps)
     out = dict(config=a.config, tensors=len(shapes), trainable_params=n_params, rounds=a.rounds, steps_per_round=a.steps)
     for name, (_, per_param, state) in ARMS.items():
         ms = statistics.median(times[name])
-        out[name] = dict(ms_median=round(ms, 4), ms_all=[round(t, 4) for t in times[name]], bytes_per_param=per_param,
+        ms_median, ms_all = benchlib.ms_summary(times[name])
+        out[name] = dict(ms_median=ms_median, ms_all=ms_all, bytes_per_param=per_param,
                          tb_per_s=round(per_param * n_params / (ms * 1e-3) / 1e12, 3), state_bytes_per_param=state,
                          steps_taken=int(float(opts[name].state_dict()["state"][0]["step"])))
-    diffs = {name: [x - y for x, y in zip(times[name], times["plain"])] for name in ("plain2", "ema", "ema8")}
+    diffs = {name: benchlib.round_diffs(times, name, "plain") for name in ("plain2", "ema", "ema8")}
     for name, d in diffs.items():
-        out[f"{name}_minus_plain_ms"] = dict(median=round(statistics.median(d), 4), all=[round(x, 4) for x in d])
-    out["aa_spread_ms"] = round(max(abs(x) for x in diffs["plain2"]), 4)
+        median, every = benchlib.ms_summary(d)
+        out[f"{name}_minus_plain_ms"] = dict(median=median, all=every)
+    out["aa_spread_ms"] = round(benchlib.aa_spread(diffs["plain2"]), 4)
     ema_ms = statistics.median(diffs["ema"])
     out["ema_pass"] = dict(ms=round(ema_ms, 4), bytes_per_param=EMA_BYTES, tb_per_s=round(EMA_BYTES * n_params / (ema_ms * 1e-3) / 1e12, 3))
     lines = [f"{'arm':8s}{'ms / step':>11s}{'bytes / parameter':>20s}{'TB/s':>8s}{'state bytes / parameter':>26s}    per-round difference against plain, ms"]
@@ -105,12 +69,7 @@ def main():
     lines.append(f"A/A spread (largest |plain2 - plain| of a round): {out['aa_spread_ms']:.4f} ms")
     lines.append(f"the averaging pass alone (ema - plain, median of the rounds): {ema_ms:.4f} ms for {EMA_BYTES} bytes per parameter = "
                  f"{out['ema_pass']['tb_per_s']:.2f} TB/s; the plain AdamW arm of this run: {out['plain']['tb_per_s']:.2f} TB/s")
-    text = "\n".join(lines) + "\n" + json.dumps(out)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    benchlib.emit("\n".join(lines) + "\n" + json.dumps(out), a.out)
 
 
 if __name__ == "__main__":

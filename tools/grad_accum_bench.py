@@ -13,14 +13,10 @@ drift fall on all alike.  Prints one JSON line: median ms per step of each, the 
 one AdamW sweep over the trainable list move.  `--only NAME` replays just one of them (for a rocprofv3 --kernel-trace --stats run)."""
 import argparse
 import json
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
 KINDS = ["full", "autograd", "accumulate"]
 
@@ -34,21 +30,8 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=0.0)
     ap.add_argument("--only", default="", choices=[""] + KINDS)
     a = ap.parse_args()
-    saved, sys.argv = sys.argv, [sys.argv[0], "--config", a.config]
-    import bench
-    args = bench.parse()
-    sys.argv = saved
-    from flamingo_mini_amd import FusedAdamW, GraphedTrainStep, ffi
-    ffi.lib()
-    device = torch.device("cuda", 0)
-    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    if args.stock_tuning != "off" and dtype == torch.bfloat16:
-        from flamingo_mini_amd.backbones import load_stock_gemm_tuning
-        load_stock_gemm_tuning()
-    model, cfg = bench.build_model(args, device, dtype)
-    batch = bench.synthetic_batch(args, cfg, device, dtype, 0)
-    model.set_launch_structure(hoist_kv=args.hoist_kv == "on")
-    params = list(model.parameters_trainable())
+    model, batch, params = benchlib.train_setup(a.config)
+    from flamingo_mini_amd import FusedAdamW, GraphedTrainStep
     k = a.micro_batches
 
     class AutogradAccumulation(GraphedTrainStep):
@@ -71,17 +54,7 @@ def main():
         opts[kind] = FusedAdamW(params, lr=1e-4, capturable=True, max_grad_norm=a.max_grad_norm or None)
         cls = AutogradAccumulation if kind == "autograd" else GraphedTrainStep
         steps[kind] = cls(model, opts[kind], batch, warmup=2, **({"micro_batches": k} if kind == "accumulate" else {}))
-    times = {kind: [] for kind in kinds}
-    for _ in range(a.rounds):
-        for kind in kinds:
-            steps[kind]()                                  # (one untimed replay after switching)
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(a.steps):
-                steps[kind]()
-            t1.record()
-            t1.synchronize()
-            times[kind].append(t0.elapsed_time(t1) / a.steps)
+    times = benchlib.replay_rounds(steps, a.rounds, a.steps)
     losses = {kind: float(steps[kind].loss) for kind in kinds}
     for s in steps.values():
         s.close()
@@ -92,11 +65,10 @@ def main():
                accumulate_sweep_bytes=dict(first=grad_bytes + 4 * n, later=grad_bytes + 8 * n),       # read g (+ read acc) + write acc
                last_loss=losses)
     for kind in kinds:
-        out[f"{kind}_ms_median"] = round(statistics.median(times[kind]), 4)
-        out[f"{kind}_ms_all"] = [round(t, 4) for t in times[kind]]
+        out[f"{kind}_ms_median"], out[f"{kind}_ms_all"] = benchlib.ms_summary(times[kind])
     if not a.only:
-        out["accumulate_minus_autograd_ms_median"] = round(statistics.median([x - y for x, y in zip(times["accumulate"], times["autograd"])]), 4)
-        out["accumulate_minus_full_ms_median"] = round(statistics.median([x - y for x, y in zip(times["accumulate"], times["full"])]), 4)
+        out["accumulate_minus_autograd_ms_median"] = benchlib.median_diff(times, "accumulate", "autograd")
+        out["accumulate_minus_full_ms_median"] = benchlib.median_diff(times, "accumulate", "full")
     print(json.dumps(out))
 
 

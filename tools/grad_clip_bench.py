@@ -15,14 +15,9 @@ takes the place of ff_grad_clip_coef, no extra pass), guard - plain (expected: o
 clipped - clipped, the largest per-round |A/A| difference, and the two acceptance checks against it."""
 import argparse
 import json
-import os
 import statistics
-import sys
 
-import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
 
 def main():
@@ -34,21 +29,8 @@ def main():
     ap.add_argument("--only", default="", choices=["", "clipped"])
     ap.add_argument("--skip-nonfinite", action="store_true")
     a = ap.parse_args()
-    saved, sys.argv = sys.argv, [sys.argv[0], "--config", a.config]
-    import bench
-    args = bench.parse()
-    sys.argv = saved
-    from flamingo_mini_amd import FusedAdamW, GraphedTrainStep, ffi
-    ffi.lib()
-    device = torch.device("cuda", 0)
-    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    if args.stock_tuning != "off" and dtype == torch.bfloat16:
-        from flamingo_mini_amd.backbones import load_stock_gemm_tuning
-        load_stock_gemm_tuning()
-    model, cfg = bench.build_model(args, device, dtype)
-    batch = bench.synthetic_batch(args, cfg, device, dtype, 0)
-    model.set_launch_structure(hoist_kv=args.hoist_kv == "on")
-    params = list(model.parameters_trainable())
+    model, batch, params = benchlib.train_setup(a.config)
+    from flamingo_mini_amd import FusedAdamW, GraphedTrainStep
     grad_bytes = sum(p.numel() * p.element_size() for p in params)
     kinds = ["clipped"] if a.only else ["plain", "clipped"]
     if a.skip_nonfinite:
@@ -60,32 +42,21 @@ def main():
         opts[kind] = FusedAdamW(params, lr=1e-4, capturable=True, max_grad_norm=a.max_grad_norm if kind.startswith("clipped") else None,
                                 skip_nonfinite=kind.endswith("guard"))
         steps[kind] = GraphedTrainStep(model, opts[kind], batch, warmup=2)
-    times = {k: [] for k in kinds}
-    for _ in range(a.rounds):
-        for kind in kinds:
-            steps[kind]()                                  # (one untimed replay after switching)
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(a.steps):
-                steps[kind]()
-            t1.record()
-            t1.synchronize()
-            times[kind].append(t0.elapsed_time(t1) / a.steps)
+    times = benchlib.replay_rounds(steps, a.rounds, a.steps)
     for s in steps.values():
         s.close()
     out = dict(config=a.config, trainable_params=sum(p.numel() for p in params), grad_bytes=grad_bytes, max_grad_norm=a.max_grad_norm,
                rounds=a.rounds, steps_per_round=a.steps, grad_norm=float(opts["clipped"].grad_norm))
     for kind in kinds:
-        out[f"{kind}_ms_median"] = round(statistics.median(times[kind]), 4)
-        out[f"{kind}_ms_all"] = [round(t, 4) for t in times[kind]]
+        out[f"{kind}_ms_median"], out[f"{kind}_ms_all"] = benchlib.ms_summary(times[kind])
     if not a.only:
-        out["delta_ms_median"] = round(statistics.median([c - p for c, p in zip(times["clipped"], times["plain"])]), 4)
+        out["delta_ms_median"] = benchlib.median_diff(times, "clipped", "plain")
     if a.skip_nonfinite:
         def diffs(x, y):
-            return [p - q for p, q in zip(times[x], times[y])]
+            return benchlib.round_diffs(times, x, y)
 
         aa = diffs("clipped_aa", "clipped")
-        aa_bound = max(abs(d) for d in aa)
+        aa_bound = benchlib.aa_spread(aa)
         guard_on_clip = statistics.median(diffs("clipped+guard", "clipped"))
         guard_alone = statistics.median(diffs("guard", "plain"))
         out.update(skipped_steps={k: int(opts[k].skipped_steps) for k in ("clipped+guard", "guard")},

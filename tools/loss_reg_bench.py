@@ -18,13 +18,11 @@ Needs the GPU: there is no fallback.
 """
 import argparse
 import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import torch
+
+import benchlib
 
 
 def main():
@@ -37,8 +35,7 @@ def main():
     ap.add_argument("--label-smoothing", type=float, default=0.1)
     ap.add_argument("--z-loss", type=float, default=1e-4)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("loss_reg_bench.py measures on the GPU; none is visible")
+    benchlib.need_gpu(__file__)
     from transformers.trainer_pt_utils import LabelSmoother
     from flamingo_mini_amd import ffi
     lib, dev, dt = ffi.lib(), torch.device("cuda"), torch.bfloat16

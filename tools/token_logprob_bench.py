@@ -9,7 +9,7 @@ random-init backbones, batch 32, bf16, a 4-token prompt with the media tag first
     greedy_off / greedy_on   generate() on the static path without and with return_dict_in_generate=True, output_logprobs=True: tokens/s
                         and ms per replayed decode step
 
-Method: as tools/logits_process_bench.py - every path is warmed up with one full call (sessions built, graphs captured), then timed with a
+Method (benchlib.host_rounds): every path is warmed up with one full call (sessions built, graphs captured), then timed with a
 host clock around `--rounds` calls that each end in a device synchronise, ALTERNATING inside a round; the median is reported with the
 spread.  The default path against the commit before the feature: run `--only off` (it needs nothing of the feature) on both trees.
 `--only kernel` times the launches alone, without building the model - also the program for a kernel trace in a run of its own:
@@ -21,60 +21,34 @@ Needs the GPU: there is no fallback.
 """
 import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import torch
+
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--lm", default="gpt2-large")
-    ap.add_argument("--clip", default="openai/clip-vit-large-patch14")
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--tokens", type=int, default=32, help="new tokens per image")
-    ap.add_argument("--rounds", type=int, default=5)
+    benchlib.caption_arguments(ap)
     ap.add_argument("--launches", type=int, default=200, help="calls captured into the timed graph")
     ap.add_argument("--replays", type=int, default=100, help="replays of that graph inside the timed window")
     ap.add_argument("--eager", action="store_true", help="time plain launches instead of a replayed graph (for a kernel trace)")
     ap.add_argument("--only", choices=["off", "kernel"], default=None,
                     help="off: the default decode leg alone (runs on a tree without the feature); kernel: the launch timings alone, no model")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("token_logprob_bench.py measures on the GPU; none is visible")
+    benchlib.need_gpu(__file__)
     dev, dt = torch.device("cuda"), torch.bfloat16
     res = {"device": torch.cuda.get_device_name(0)}
     times = {}
     if a.only != "kernel":
-        import bench
-        margs = argparse.Namespace(lm=a.lm, clip=a.clip, xattn_every=1, lm_dropout=None, backbone_tweaks="off", batch=a.batch, seq_len=32, images=1, frames=0)
-        model, cfg = bench.build_model(margs, dev, dt)
-        model.eval()
-        batch = bench.synthetic_batch(margs, cfg, dev, dt, 0)
-        ids, ml, am = batch["input_ids"][:, :4], batch["media_locations"][:, :4], batch["attention_mask"][:, :4]
-        L = 4 + a.tokens
-        kw = dict(media_locations=ml, attention_mask=am, pixel_values=batch["pixel_values"], max_length=L)
+        model, ids, kw = benchlib.caption_setup(a, dev, dt)
         paths = {"greedy_off": lambda: model.generate(ids, **kw)}
         if a.only is None:
             paths["greedy_on"] = lambda: model.generate(ids, return_dict_in_generate=True, output_logprobs=True, **kw)
         res.update(geometry=f"{a.lm}, batch {a.batch}, prompt 4 + {a.tokens} new tokens, bf16, random-init backbones", rounds=a.rounds)
-        times = {k: [] for k in paths}
         with torch.no_grad():
-            for fn in paths.values():
-                fn()
-            torch.cuda.synchronize()
-            for _ in range(a.rounds):
-                for name, fn in paths.items():
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    fn()
-                    torch.cuda.synchronize()
-                    times[name].append(time.perf_counter() - t0)
-            res["decode_step_hip_graph"] = all(s.replay is not None and not s.capture_failed for s in model._decode_sessions.values())
+            times, _ = benchlib.host_rounds(paths, a.rounds)
+        res["decode_step_hip_graph"] = all(benchlib.graphed(s) for s in model._decode_sessions.values())
     if a.only != "off":
         from flamingo_mini_amd import functional as F
         V = 50258
@@ -85,25 +59,7 @@ def main():
 
         def timed(fn):
             """microseconds per call: --launches calls in one graph, replayed --replays times between two device events"""
-            for _ in range(5):
-                fn()
-            run, n = fn, a.launches
-            if not a.eager:
-                graph = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                with torch.cuda.graph(graph):
-                    for _ in range(a.launches):
-                        fn()
-                graph.replay()
-                run, n = graph.replay, a.launches * a.replays
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(a.replays if not a.eager else a.launches):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            return round(e0.elapsed_time(e1) / n * 1e3, 2)
+            return benchlib.launch_us(fn, a.launches, a.replays, eager=a.eager, digits=2)
 
         res.update(window=f"{'eager launches' if a.eager else 'graph replay'}, {a.launches if a.eager else a.launches * a.replays} calls per figure",
                    token_logprob_us={}, torch_chain_us={})
@@ -112,9 +68,7 @@ def main():
                 res["token_logprob_us"][name] = timed(lambda: F.token_logprobs(x, tok, out=out))
                 res["torch_chain_us"][name] = timed(lambda: x.float().log_softmax(-1).gather(1, tok[:, None]))
     for name, ts in times.items():
-        n = a.batch * a.tokens
-        res[name] = {"tokens_per_s": round(n / statistics.median(ts), 1), "min": round(n / max(ts), 1), "max": round(n / min(ts), 1),
-                     "ms_per_decode_step": round(statistics.median(ts) / a.tokens * 1e3, 3)}
+        res[name] = benchlib.tokens_report(ts, a.batch, a.tokens)
     print(json.dumps(res))
 
 
