@@ -71,6 +71,133 @@ def check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ng
     return procs if procs.given() else None
 
 
+# ---- constrained decoding: the host-built tables of ff_logits_constrain (include/flamingo_fusion.h) ----
+CONSTRAINT_TABLE_MAX = 1 << 22         # entries per table a session will hold on the device (16 MiB of int32); larger sets take the dynamic loop
+_TABLE_FLOORS = (64, 64, 16, 64)       # node_cap, edge_cap, bw_cap, bw_tok_cap: the smallest capacities a session allocates
+
+
+def _id_lists(name, lists, vocab):
+    """`lists` as a sorted list of distinct tuples of ints in [0, vocab); ValueError for anything else, empty input and empty entries."""
+    if isinstance(lists, (str, bytes)) or not hasattr(lists, "__iter__"):
+        raise ValueError(f"generate(): {name} must be a list of lists of token ids, got {lists!r}")
+    out = set()
+    for entry in lists:
+        if isinstance(entry, (str, bytes)) or not hasattr(entry, "__iter__"):
+            raise ValueError(f"generate(): {name} must be a list of lists of token ids, got the entry {entry!r}")
+        entry = tuple(entry)
+        if not entry:
+            raise ValueError(f"generate(): {name} holds an empty entry")
+        for t in entry:
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < vocab:
+                raise ValueError(f"generate(): {name} holds {t!r}, not a token id in [0, {vocab})")
+        out.add(entry)
+    if not out:
+        raise ValueError(f"generate(): {name} is empty")
+    return sorted(out)
+
+
+def _cap(n, floor):
+    """n rounded up to a power of two, at least `floor`: the capacity class of a table of n entries."""
+    return max(floor, 1 << max(int(n) - 1, 0).bit_length())
+
+
+class TokenTrie:
+    """The candidate sequences of generate(candidate_ids=...) as the CSR trie ff_logits_constrain reads: root = node 0, the edges of node s
+    are node_first[s] .. node_first[s + 1], edge_tok ascending inside a node, node_terminal[s] = a candidate ends at s.  Duplicates are
+    dropped; a candidate that is a prefix of another makes an inner node terminal (there eos and the longer candidate's next token are both
+    allowed).  ValueError: no candidates, an empty candidate, an id outside [0, vocab), a candidate that contains eos."""
+
+    def __init__(self, candidates, vocab, eos):
+        import numpy as np
+        cands = _id_lists("candidate_ids", candidates, vocab)
+        if any(eos in c for c in cands):
+            raise ValueError(f"generate(): a candidate contains eos_token_id {eos}; eos ends a candidate, it cannot be part of one")
+        children, terminal = [{}], [False]
+        for c in cands:
+            s = 0
+            for t in c:
+                nxt = children[s].get(t)
+                if nxt is None:
+                    nxt = children[s][t] = len(children)
+                    children.append({})
+                    terminal.append(False)
+                s = nxt
+            terminal[s] = True
+        self.vocab, self.candidates, self.longest = vocab, cands, max(len(c) for c in cands)
+        self.n_nodes = len(children)
+        self.node_first = np.cumsum([0] + [len(ch) for ch in children]).astype(np.int32)
+        self.edge_tok = np.array([t for ch in children for t in sorted(ch)], np.int32)
+        self.edge_child = np.array([ch[t] for ch in children for t in sorted(ch)], np.int32)
+        self.node_terminal = np.array(terminal, np.uint8)
+
+    DEAD, DONE = -1, -2
+
+    def walk(self, generated, eos):
+        """Rule T1: the node the generated tokens lead to, or DONE / DEAD."""
+        import numpy as np
+        s = 0
+        for t in generated:
+            if t == eos and self.node_terminal[s]:
+                return self.DONE
+            lo, hi = int(self.node_first[s]), int(self.node_first[s + 1])
+            i = lo + int(np.searchsorted(self.edge_tok[lo:hi], t))
+            if i == hi or int(self.edge_tok[i]) != t:
+                return self.DEAD
+            s = int(self.edge_child[i])
+        return s
+
+    def allowed(self, s, eos):
+        """Rule T2: the tokens node s allows."""
+        toks = self.edge_tok[int(self.node_first[s]):int(self.node_first[s + 1])].tolist()
+        return toks + [eos] if self.node_terminal[s] else toks
+
+
+class BadWords:
+    """The words of generate(bad_words_ids=...) as the table ff_logits_constrain reads: word w is bw_tok[bw_off[w] .. bw_off[w + 1]).
+    Duplicates are dropped.  ValueError: no words, an empty word, an id outside [0, vocab)."""
+
+    def __init__(self, words, vocab):
+        import numpy as np
+        self.words = _id_lists("bad_words_ids", words, vocab)
+        self.vocab, self.n = vocab, len(self.words)
+        self.bw_off = np.cumsum([0] + [len(w) for w in self.words]).astype(np.int32)
+        self.bw_tok = np.array([t for w in self.words for t in w], np.int32)
+
+
+class Constraints:
+    """What generate(candidate_ids=, bad_words_ids=) decodes under: a TokenTrie and / or BadWords (either may be None, not both)."""
+
+    def __init__(self, trie=None, bad_words=None):
+        assert trie is not None or bad_words is not None
+        self.trie, self.bad_words = trie, bad_words
+
+    def caps(self):
+        """("constraints", node_cap, edge_cap, bw_cap, bw_tok_cap): the capacity class of the tables - the live sizes rounded up to powers of
+        two, 0 for an absent table - and the trailing element of the key of a session that decodes under them: calls whose tables fall into
+        the same class share the session and its captured graph."""
+        t, w = self.trie, self.bad_words
+        sizes = (t.n_nodes, len(t.edge_tok)) if t is not None else (None, None)
+        sizes += (w.n, len(w.bw_tok)) if w is not None else (None, None)
+        return ("constraints",) + tuple(0 if n is None else _cap(n, f) for n, f in zip(sizes, _TABLE_FLOORS))
+
+
+def check_constraint_args(candidate_ids, bad_words_ids, vocab, eos, procs, L0, max_length) -> Optional[Constraints]:
+    """The checks of generate()'s constraint arguments.  Returns the Constraints, None when both are None (exactly the paths without them)."""
+    if candidate_ids is None and bad_words_ids is None:
+        return None
+    trie = None
+    if candidate_ids is not None:
+        if eos is None:
+            raise ValueError("generate(): candidate_ids needs eos_token_id (eos is what ends a candidate)")
+        if procs is not None and (procs.min_length > 0 or procs.min_new_tokens > 0):
+            raise ValueError("generate(): candidate_ids cannot be combined with min_length / min_new_tokens: at the end of a candidate only eos is "
+                             "allowed, and while the minimum length bans eos no token would be")
+        trie = TokenTrie(candidate_ids, vocab, eos)
+        if L0 + trie.longest + 1 > max_length:
+            raise ValueError(f"generate(): the prompt ({L0} tokens), the longest candidate ({trie.longest}) and eos do not fit max_length {max_length}")
+    return Constraints(trie, BadWords(bad_words_ids, vocab) if bad_words_ids is not None else None)
+
+
 def check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample) -> int:
     """The checks of generate()'s output arguments.  Returns num_return_sequences."""
     n = num_return_sequences
@@ -101,13 +228,15 @@ def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
 
 
 def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_family, L0, max_length, ids_is_int64, procs_on, procs_given=(),
-          logprobs_on=False):
+          logprobs_on=False, constraints_on=False, vocab=0, table_entries=0):
     """Which path a generate() call takes: "static" (a _DecodeSession) or "dynamic" (dynamic_decode / beam_search), from plain values only.
     `static_decode` is generate()'s argument (None, True, False), `model_default` the model's attribute, `procs_given` the processor
     arguments' names for the TypeError on CPU tensors.  Greedy decoding takes the static path by default on the GPU; sampling and beam search
     only when static_decode=True is passed, and then they need GPU tensors: their kernels have no CPU form.  Neither has the log-probability
     kernel (`logprobs_on`): a static session that records them needs GPU tensors, CPU tensors take the dynamic loop unless static_decode=True
-    asks for what cannot be had."""
+    asks for what cannot be had.  Constraints (`constraints_on`, with the LM's `vocab` and `table_entries`, the largest table's size) are
+    the same on CPU tensors - the dynamic loops restate them on the host - and take the static path under the processors' conditions
+    plus the kernel's vocabulary cap and the sessions' table cap."""
     def need_gpu():                     # what ffi.require_cuda raises for a CPU tensor
         if not is_cuda:
             F.ffi.require_cuda(torch.empty(0))
@@ -119,11 +248,12 @@ def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_fam
     if num_beams > 1 and do_sample:
         raise ValueError("beam search with sampling is not implemented")
     on_request = num_beams > 1 or do_sample                                   # static only when static_decode=True is passed
-    if (on_request or logprobs_on) and static_decode:
+    if (on_request or logprobs_on or constraints_on) and static_decode:
         need_gpu()
     if static_decode is None:
         static_decode = is_cuda and model_default and not on_request
-    static_ok = lm_family is not None and L0 + 1 < max_length and num_beams <= F.ffi.BEAM_MAX and (not procs_on or (ids_is_int64 and max_length <= F.ffi.LOGITS_HIST_MAX))
+    static_ok = lm_family is not None and L0 + 1 < max_length and num_beams <= F.ffi.BEAM_MAX and (not (procs_on or constraints_on) or (ids_is_int64 and max_length <= F.ffi.LOGITS_HIST_MAX)) and \
+        (not constraints_on or (vocab <= F.ffi.CONSTRAIN_VOCAB_MAX and table_entries <= CONSTRAINT_TABLE_MAX))
     return "static" if static_decode and static_ok else "dynamic"
 
 
@@ -167,12 +297,41 @@ def process_logits(logits, seqs, repetition_penalty, no_repeat_ngram_size, eos, 
     return out[:, :V].contiguous()
 
 
-def _dynamic_processor(processors, eos, L0):
-    """(logits, sequences so far) -> logits for the dynamic loops: process_logits with the call's settings, the identity without processors."""
-    if processors is None:
+def constrain_logits_torch(logits, seqs, gen_start, eos, trie=None, bad_words=None):
+    """The rules of ff_logits_constrain (T1, T2, B1 of include/flamingo_fusion.h) for the dynamic loops, on tensors of any device: `logits`
+    (rows, V) against the sequences so far `seqs` (rows, n), whose generated tokens begin at `gen_start`; `trie` a TokenTrie, `bad_words` a
+    BadWords.  The trie is walked on the host (one read of `seqs`), the bans are one masked_fill.  Returns new logits."""
+    V, n = logits.shape[-1], seqs.shape[1]
+    n0 = min(max(int(gen_start), 0), n)
+    ban = torch.zeros(logits.shape, dtype=torch.bool)
+    for r, h in enumerate(seqs.tolist()):
+        if trie is not None:
+            s = trie.walk(h[n0:], eos)
+            if s >= 0:                                                            # DONE and DEAD rows stay untouched
+                ban[r] = True
+                ban[r, [t for t in trie.allowed(s, eos) if 0 <= t < V]] = False
+        for w in (bad_words.words if bad_words is not None else ()):
+            m = len(w)
+            if 0 <= w[-1] < V and n >= m - 1 and tuple(h[n - m + 1:]) == w[:-1]:
+                ban[r, w[-1]] = True
+    return logits.masked_fill(ban.to(logits.device), float("-inf"))
+
+
+def _dynamic_processor(processors, eos, L0, constraints=None):
+    """(logits, sequences so far) -> logits for the dynamic loops: process_logits with the call's settings, then constrain_logits_torch with
+    the call's tables; the identity without either."""
+    if processors is None and constraints is None:
         return lambda x, s: x
-    p = Processors(*processors)
-    return lambda x, s: process_logits(x, s, p.repetition_penalty, p.no_repeat_ngram_size, eos, p.min_len(L0))
+    p = Processors(*processors) if processors is not None else None
+    c = constraints
+
+    def process(x, s):
+        if p is not None:
+            x = process_logits(x, s, p.repetition_penalty, p.no_repeat_ngram_size, eos, p.min_len(L0))
+        if c is not None:
+            x = constrain_logits_torch(x, s, L0, eos, c.trie, c.bad_words)
+        return x
+    return process
 
 
 def _pad_finished(nxt, finished, eos, pad):
@@ -245,14 +404,19 @@ class _DecodeSession:
     _all_done and _result, and override neither _append nor run.
     `processors` (a Processors) puts functional.process_logits (one launch, csrc/ff_logits.hip) in front of the selection of every strategy:
     _append edits the step's logits in place against the strategy's token history (_history(), with `pos` as its length) and against
-    `min_len`, a device scalar _begin sets outside any capture.  A session without processors issues none of this."""
+    `min_len`, a device scalar _begin sets outside any capture.  A session without processors issues none of this.
+    `constraints` (Constraints.caps(): capacities, not contents) puts functional.constrain_logits (one launch, csrc/ff_constrain.hip) behind
+    it: the session owns table buffers of those capacities, every call's tables are copied into them before the prompt step together with
+    `gen_start` (the prompt's length), outside any capture, and the captured step reads whatever they hold - a later call with other
+    candidates of the same capacity class replays the same graph.  A session without constraints allocates and issues none of this."""
 
     nb = 1                                 # rows per sequence
 
-    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None, logprobs=False):
+    def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None, logprobs=False,
+                 constraints=None):
         from transformers.cache_utils import StaticCache
         self._model_ref = weakref.ref(model)
-        self.sampling, self.beams, self.processors, self.logprobs = sampling, beams, processors, logprobs
+        self.sampling, self.beams, self.processors, self.logprobs, self.constraints = sampling, beams, processors, logprobs, constraints
         self.n_seq = b
         b = b * self.nb
         self.b, self.max_length, self.eos, self.graph_wanted = b, max_length, eos, graph
@@ -264,6 +428,8 @@ class _DecodeSession:
         self.pos = torch.zeros((1,), dtype=torch.long, device=device)          # position of `tok` (the token the next step consumes)
         self.tok = torch.zeros((b, 1), dtype=ids_dtype, device=device)
         self.tt_step = torch.zeros((b, 1), dtype=torch.int32, device=device)
+        if constraints is not None:
+            self._alloc_constraints()
         self._alloc()
         self.xattn_past = None                                                # persistent (k, v) per layer, filled by every prompt step
         self.replay = None
@@ -290,12 +456,38 @@ class _DecodeSession:
         self.min_len = torch.zeros((1,), dtype=torch.long, device=self.pos.device)
         self.min_on = self.eos is not None and (p.min_length > 0 or p.min_new_tokens > 0)
 
+    def _alloc_constraints(self):
+        _, node_cap, edge_cap, bw_cap, bw_tok_cap = self.constraints
+        i32 = lambda n, dt=torch.int32: torch.zeros((n,), dtype=dt, device=self.pos.device)
+        self.gen_start = torch.zeros((1,), dtype=torch.long, device=self.pos.device)
+        self.trie_bufs = (i32(node_cap + 1), i32(edge_cap), i32(edge_cap), i32(node_cap, torch.uint8), i32(1)) if node_cap else None
+        self.bw_bufs = (i32(bw_cap + 1), i32(bw_tok_cap), i32(1)) if bw_cap else None
+
+    def _begin_constraints(self, c, L0):
+        """A call's tables into the session's buffers (the live prefix; what lies behind it is never read) and gen_start = the prompt's length."""
+        assert c.caps() == self.constraints
+        dev = self.pos.device
+        put = lambda buf, a: buf[:len(a)].copy_(torch.from_numpy(a).to(dev))
+        self.gen_start.fill_(L0)
+        if c.trie is not None:
+            t = c.trie
+            for buf, a in zip(self.trie_bufs, (t.node_first, t.edge_tok, t.edge_child, t.node_terminal)):
+                put(buf, a)
+            self.trie_bufs[4].fill_(t.n_nodes)
+        if c.bad_words is not None:
+            w = c.bad_words
+            put(self.bw_bufs[0], w.bw_off)
+            put(self.bw_bufs[1], w.bw_tok)
+            self.bw_bufs[2].fill_(w.n)
+
     def _append(self, logits):
-        """The single place that receives a step's unprocessed logits: the processors, in place, against the first `pos` tokens of every
-        row of the strategy's history, then the strategy's selection."""
+        """The single place that receives a step's unprocessed logits: the processors, then the constraints, in place, against the first `pos`
+        tokens of every row of the strategy's history, then the strategy's selection."""
         p = self.processors
         if p is not None:
             F.process_logits(logits, self._history(), self.pos, p.repetition_penalty, p.no_repeat_ngram_size, self.eos if self.min_on else None, self.min_len if self.min_on else None)
+        if self.constraints is not None:
+            F.constrain_logits(logits, self._history(), self.pos, self.gen_start, self.eos, trie=self.trie_bufs, bad_words=self.bw_bufs)
         self._select(logits)
 
     def _positions(self, L0=None):
@@ -317,9 +509,11 @@ class _DecodeSession:
         self._append(o.logits[:, -1])
 
     @torch.no_grad()
-    def run(self, ids, ml, am, pixel_values, visual_features, generator=None, n_return=None):
+    def run(self, ids, ml, am, pixel_values, visual_features, generator=None, n_return=None, constraints=None):
         L0, prompt_ids = ids.shape[1], ids
         ids, ml, am, pixel_values, visual_features = self._begin(ids, ml, am, pixel_values, visual_features, generator)
+        if self.constraints is not None:
+            self._begin_constraints(constraints, L0)
         self.cache.reset()
         out = self.model.flamingo(input_ids=ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=(None, self.cache),
                                   pixel_values=pixel_values, visual_features=visual_features, **self._positions(L0))
@@ -433,7 +627,8 @@ class _BeamSession(_DecodeSession):
     index, live positions only) and tok <- next_tok.  The cross-attention K / V, the attention mask and text_time are equal within a
     sequence's beams and are NOT reordered.  The result is read back once, after the loop (_beam_finalize).
     The processors read `seq_buf` (b * nb, max_length), which follows the beams through the same in-place gather as the LM cache (viewed as
-    two 4-byte elements per id); a session without processors allocates no seq_buf."""
+    two 4-byte elements per id), and so do the constraints: a beam's position in the trie is a function of its own tokens.  A session with
+    neither allocates no seq_buf."""
 
     def __init__(self, model, b, *args, beams, **kw):
         self.nb = beams.nb
@@ -446,6 +641,7 @@ class _BeamSession(_DecodeSession):
         self.lm_tensors = None                                                # keys / values of every StaticCache layer (allocated by the first prompt step)
         if self.processors is not None:
             self._alloc_min_len()
+        if self.processors is not None or self.constraints is not None:
             self.seq_buf = torch.full((self.b, self.max_length), self.fill, dtype=torch.long, device=dev)
 
     def _begin(self, ids, ml, am, pixel_values, visual_features, generator):
@@ -457,6 +653,7 @@ class _BeamSession(_DecodeSession):
         self.state.reset()
         if self.processors is not None:
             self.min_len.fill_(self.processors.min_len(ids.shape[1]))
+        if hasattr(self, "seq_buf"):
             self.seq_buf.fill_(self.fill)
             self.seq_buf[:, :ids.shape[1]] = ids
         return ids, ml, am, pixel_values, visual_features
@@ -470,7 +667,7 @@ class _BeamSession(_DecodeSession):
         torch.add(self.pos, 1, out=self.cur_len)
         nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
         F.beam_gather(self.lm_tensors, beam_idx, self.pos, self.nb)           # positions < pos are live: the cache rows follow their beams
-        if self.processors is not None:                                       # ... and so do the histories: an id is two 4-byte elements
+        if hasattr(self, "seq_buf"):                                          # ... and so do the histories: an id is two 4-byte elements
             F.beam_gather([self.seq_buf.view(torch.int32).view(self.b, 1, self.max_length, 2)], beam_idx, self.pos, self.nb)
             self.seq_buf.index_copy_(1, self.pos, nxt[:, None])
         self.tok.copy_(nxt[:, None])
@@ -486,7 +683,7 @@ class _BeamSession(_DecodeSession):
 
 
 def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, beams=None, processors=None,
-                   logprobs=False, n_return=None):
+                   logprobs=False, n_return=None, constraints=None):
     """Greedy, sampled (`sampling`) or beam-search (`beams`) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches
     and buffers plus, on the GPU, the captured HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, device,
     eos, pad, graph, sampling, beams, processors) and reused by later calls, so only the first caption batch of a shape pays for the
@@ -494,13 +691,16 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
     FlamingoModel.reset_decode_sessions() drops them all.
     `logprobs` (greedy and sampling) selects a session that records the chosen tokens' log-probabilities: its key is the same ten elements
     followed by "logprobs", and the call returns (ids, token_logprobs).  `n_return` (beam search) returns (ids, scores) with the n best
-    entries per sequence (_beam_finalize); it changes nothing in the session."""
+    entries per sequence (_beam_finalize); it changes nothing in the session.  `constraints` (a Constraints) selects a session that decodes
+    under a candidate trie and / or banned words: its key ends with Constraints.caps() - the tables' capacities, not their contents."""
     b = ids.shape[0]
     graph = ids.is_cuda and not model.training and model.decode_graph
     sessions = _DECODE_SESSIONS.setdefault(model, {})
     n_media = int(ml.sum(-1).max()) if visual_features is None and pixel_values is None else \
         (visual_features.shape[1] if visual_features is not None else (pixel_values.shape[1] if pixel_values.ndim >= 5 else pixel_values.shape[0]))
     key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams, processors) + (("logprobs",) if logprobs else ())
+    if constraints is not None:
+        key += (constraints.caps(),)
     sess = sessions.get(key)
     if sess is not None and sess.stale():
         sessions.pop(key)
@@ -509,20 +709,21 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
         if len(sessions) >= 4:                                                # a handful of shapes at most: each holds a KV cache and a graph
             sessions.pop(next(iter(sessions)))
         cls = _TokenSession if beams is None else _BeamSession
-        sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors, logprobs=logprobs)
-    return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator, n_return=n_return)
+        sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors, logprobs=logprobs,
+                                   **({"constraints": constraints.caps()} if constraints is not None else {}))
+    return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator, n_return=n_return, **({"constraints": constraints} if constraints is not None else {}))
 
 
 # ---- the dynamic path: growing caches, one forward per step (the only path on CPU tensors, and what the sessions are tested against) ----
 def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, processors=None,
-                   logprob_dtype=None):
+                   logprob_dtype=None, constraints=None):
     """Greedy or, with `sampling`, multinomial decoding over the cached decode path; `step` is FlamingoModel._decode_step.
     With `logprob_dtype` (torch.float32, or torch.float64 for a model that computes in float64) it returns (ids, token_logprobs): the
     log-softmax of the processed logits at the chosen token, taken in that dtype, 0 for a row that had finished before the step."""
     finished = torch.zeros(ids.shape[0], dtype=torch.bool, device=ids.device)
     lps = []
     past, step_ids = None, ids
-    process = _dynamic_processor(processors, eos, ids.shape[1])
+    process = _dynamic_processor(processors, eos, ids.shape[1], constraints)
     while ids.shape[1] < max_length:
         logits, past = step(step_ids, ml, am, past, pixel_values, visual_features)
         logits = process(logits, ids)
@@ -547,7 +748,7 @@ def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length,
 
 
 def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None,
-                n_return=None):
+                n_return=None, constraints=None):
     """Standard beam search over the cached decode path; `step` / `reorder_cache` are FlamingoModel._decode_step / ._reorder_cache.  The
     prompt runs once per sequence; its caches are then replicated per beam (xattn K/V: repeat_interleave; LM cache:
     Cache.batch_repeat_interleave) and re-ordered every step.  `processors` act on every step's logits before the log-softmax.
@@ -555,7 +756,7 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
     the earlier entry on equal scores, with their normalised scores; missing rows are all pad with score -inf (as _beam_finalize)."""
     b, L0 = ids.shape
     dev = ids.device
-    process = _dynamic_processor(processors, eos, L0)
+    process = _dynamic_processor(processors, eos, L0, constraints)
     logits, past = step(ids, ml, am, None, pixel_values, visual_features)
     logp = process(logits, ids).log_softmax(-1)
     V = logp.shape[-1]

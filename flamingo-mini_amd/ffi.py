@@ -95,6 +95,7 @@ class XattnDesc(C.Structure):
 
 BEAM_MAX = 8                   # FF_BEAM_MAX
 LOGITS_HIST_MAX = 4096         # FF_LOGITS_HIST_MAX
+CONSTRAIN_VOCAB_MAX = 262144   # FF_CONSTRAIN_VOCAB_MAX
 
 
 class BeamDesc(C.Structure):
@@ -173,6 +174,7 @@ _SIGNATURES = {
     "ff_beam_gather": (_I, [_I, _P, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P, _P]),
     "ff_logits_process": (_I, [_I, _I, _I, C.c_longlong, _P, _P, C.c_longlong, C.c_longlong, _P, C.c_float, _I, _I, _P, _P]),
     "ff_token_logprob": (_I, [_I, _I, _I, C.c_longlong, _P, _P, _P, _P, _P, _P]),
+    "ff_logits_constrain": (_I, [_I, _I, _I, C.c_longlong, _P, _P, C.c_longlong, C.c_longlong, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P]),
     "ff_xattn_block_bwd_kv": (_I, [C.POINTER(XattnDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _SZ, _P]),
     "ff_kv_project_workspace_bytes": (_SZ, [C.POINTER(KvProjDesc), _I]),
     "ff_kv_project_fwd": (_I, [C.POINTER(KvProjDesc), _P, _P, _P, _P, _SZ, _P]),

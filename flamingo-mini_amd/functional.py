@@ -993,6 +993,51 @@ def process_logits(logits: torch.Tensor, hist: torch.Tensor, hist_len: torch.Ten
     return logits
 
 
+def constrain_logits(logits: torch.Tensor, hist: torch.Tensor, hist_len: torch.Tensor, gen_start: torch.Tensor, eos: Optional[int] = None,
+                     trie=None, bad_words=None) -> torch.Tensor:
+    """A candidate trie and / or a list of banned words applied IN PLACE to `logits` (rows, V), float32 / bfloat16 on the GPU, against the token
+    history `hist` (rows, cap <= 4096) int64, of which the first hist_len positions count and the generated tokens begin at gen_start (each a
+    one-element int64 device tensor, one value for all rows): ff_logits_constrain, one launch, nothing allocated, capturable; the exact rules
+    (T1, T2, B1) are in include/flamingo_fusion.h.  `trie` = (node_first (node_cap + 1,), edge_tok (edge_cap,), edge_child (edge_cap,),
+    node_terminal (node_cap,), n_nodes (1,)) and `bad_words` = (bw_off (bw_cap + 1,), bw_tok (bw_tok_cap,), n_bw (1,)) are contiguous int32
+    device tensors (node_terminal: uint8 / bool) whose SHAPES are the capacities; the live sizes are read on the device, so the tables of a
+    captured call may be overwritten between replays (decoding.TokenTrie / decoding.BadWords build them).  A trie needs `eos`.  Only the last
+    dimension of logits and hist has to be contiguous.  With neither table nothing is launched.  Returns `logits`."""
+    tables = tuple(trie or ()) + tuple(bad_words or ())
+    ffi.require_cuda(logits, hist, hist_len, gen_start, *tables)
+    if logits.ndim != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"constrain_logits: logits must be (rows, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
+    rows, V = logits.shape
+    if hist.dtype != torch.long or hist.ndim != 2 or hist.shape[0] != rows or (hist.shape[1] > 1 and hist.stride(1) != 1):
+        raise ValueError(f"constrain_logits: hist must be ({rows}, cap) int64 with a contiguous last dimension, got {tuple(hist.shape)} {hist.dtype} strides {hist.stride()}")
+    if any(t.dtype != torch.long or t.numel() != 1 for t in (hist_len, gen_start)):
+        raise ValueError("constrain_logits: hist_len and gen_start must each be one int64 value on the device")
+    if any(not t.is_contiguous() for t in tables):
+        raise ValueError("constrain_logits: the tables must be contiguous")
+    node_cap = edge_cap = bw_cap = bw_tok_cap = 0
+    if trie is not None:
+        node_first, edge_tok, edge_child, node_terminal, n_nodes = trie
+        node_cap, edge_cap = node_terminal.numel(), edge_tok.numel()
+        if any(t.dtype != torch.int32 for t in (node_first, edge_tok, edge_child, n_nodes)) or node_terminal.dtype not in (torch.uint8, torch.bool) \
+                or node_first.numel() != node_cap + 1 or edge_child.numel() != edge_cap or n_nodes.numel() != 1:
+            raise ValueError("constrain_logits: trie = (node_first (node_cap + 1,), edge_tok (edge_cap,), edge_child (edge_cap,), node_terminal (node_cap,) uint8, "
+                             "n_nodes (1,)), int32")
+        if eos is None:
+            raise ValueError("constrain_logits: a trie needs eos")
+    if bad_words is not None:
+        bw_off, bw_tok, n_bw = bad_words
+        bw_cap, bw_tok_cap = bw_off.numel() - 1, bw_tok.numel()
+        if any(t.dtype != torch.int32 for t in bad_words) or n_bw.numel() != 1:
+            raise ValueError("constrain_logits: bad_words = (bw_off (bw_cap + 1,), bw_tok (bw_tok_cap,), n_bw (1,)), int32")
+    cap = hist.shape[1]
+    ffi.check(ffi.lib().ff_logits_constrain(ffi.dtype_code(logits.dtype), rows, V, logits.stride(0) if rows > 1 else V, logits.data_ptr(),
+                                            hist.data_ptr(), hist.stride(0) if rows > 1 else cap, cap, hist_len.data_ptr(), gen_start.data_ptr(),
+                                            -1 if eos is None else int(eos), *(ffi.ptr(t) for t in (trie or (None,) * 5)), node_cap, edge_cap,
+                                            *(ffi.ptr(t) for t in (bad_words or (None,) * 3)), bw_cap, bw_tok_cap, ffi.stream_handle(logits.device)),
+              "ff_logits_constrain")
+    return logits
+
+
 def token_logprobs(logits: torch.Tensor, token: torch.Tensor, skip: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                    lse: Optional[torch.Tensor] = None) -> torch.Tensor:
     """log_softmax(logits[r])[token[r]] per row of `logits` (rows, V), float32 / bfloat16 on the GPU, in float32: ff_token_logprob, one launch

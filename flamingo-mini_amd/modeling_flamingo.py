@@ -440,7 +440,7 @@ class FlamingoModel(PreTrainedModel):
                  early_stopping: bool = True, length_penalty: float = 1.0, use_cache: bool = True, generator: Optional[torch.Generator] = None,
                  input_ids=None, static_decode: Optional[bool] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_length: int = 0, min_new_tokens: int = 0, return_dict_in_generate: bool = False, output_logprobs: bool = False,
-                 num_return_sequences: int = 1, **unsupported):
+                 num_return_sequences: int = 1, candidate_ids=None, bad_words_ids=None, **unsupported):
         """Text generation with the cached cross-attention path: the first step runs CLIP + resampler and fills the xattn K/V and LM caches,
         every later step feeds one token (reference: HF `generate` through prepare_inputs_for_generation / _reorder_cache, :464-548).
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
@@ -469,17 +469,35 @@ class FlamingoModel(PreTrainedModel):
         model).  With beam search sequences_scores is the normalised score the search ranked by, and output_logprobs raises ValueError.
         `num_return_sequences=n`: sampling repeats every sequence n times (the visuals are encoded once per sequence), beam search (n <=
         num_beams) returns the n best of the hypotheses and open beams its tail ranks, best first, missing ones all pad with score -inf;
-        output rows s * n + j.  Greedy decoding has one result: n > 1 raises ValueError."""
+        output rows s * n + j.  Greedy decoding has one result: n > 1 raises ValueError.
+        Constraints (lists of lists of token ids, the same for every row; ValueError for empty input, empty entries and ids outside the
+        vocabulary): `candidate_ids` restricts what is generated to one of the candidates followed by eos - every step's logits keep only the
+        tokens that continue a candidate along the row's own generated tokens, and eos where one ends (a candidate may be a prefix of
+        another); it needs eos_token_id, cannot be combined with min_length / min_new_tokens, no candidate may contain eos, and prompt +
+        longest candidate + eos must fit max_length.  `bad_words_ids` bans, as transformers does, the last token of a word whenever the
+        sequence so far - prompt included - ends with the word's other tokens.  Both act after the logits processors and before the
+        selection and token_logprobs of every mode, so log-probabilities and beam scores are renormalised over the allowed set: greedy or
+        beam search under `candidate_ids` with output_logprobs / sequences_scores / num_return_sequences is closed-set classification with
+        the probability of the chosen candidate(s).  On the static path they are one in-place launch inside the replayed step
+        (functional.constrain_logits: int64 ids, max_length <= 4096, a vocabulary of at most 262144 - otherwise the dynamic loop runs) that
+        reads the tables from device buffers, so a later call with other candidates of the same capacity class (sizes rounded up to powers
+        of two) reuses the session and its captured graph; on the dynamic paths decoding.constrain_logits_torch, which - unlike the
+        processors - also runs on CPU tensors.  Known and accepted: beam search with fewer candidates than beams and early_stopping=False
+        never collects num_beams hypotheses, so it runs to max_length with dead beams (score -inf); the result is still the best
+        candidates, on both paths.  The candidates are one set for the whole batch."""
         procs = D.check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos_token_id)
         n_ret = D.check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample)
         ids = inputs if inputs is not None else input_ids
         assert ids is not None and media_locations is not None, "generate() needs input ids and media_locations"
+        cons = D.check_constraint_args(candidate_ids, bad_words_ids, self.flamingo.lm.config.vocab_size, eos_token_id, procs, ids.shape[1], max_length)
+        ckw = {} if cons is None else {"constraints": cons}                   # nothing is passed on without constraints: the calls are what they were
+        rkw = {} if cons is None else dict(constraints_on=True, vocab=self.flamingo.lm.config.vocab_size, table_entries=max(cons.caps()[1:]))
         am = attention_mask if attention_mask is not None else torch.ones_like(ids)
         ml = media_locations
         pad = pad_token_id if pad_token_id is not None else eos_token_id
         path = D.route(is_cuda=ids.is_cuda, num_beams=num_beams, do_sample=do_sample, static_decode=static_decode, model_default=self.static_decode, lm_family=self.flamingo.lm_family,
                        L0=ids.shape[1], max_length=max_length, ids_is_int64=ids.dtype == torch.long, procs_on=procs is not None, procs_given=procs.given() if procs is not None else (),
-                       logprobs_on=bool(output_logprobs))
+                       logprobs_on=bool(output_logprobs), **rkw)
         if n_ret > 1 and num_beams <= 1:                                     # sampling: every sequence n times, its visuals encoded once
             if visual_features is None and pixel_values is not None:
                 visual_features, pixel_values = self.flamingo.encode_resample_visuals(pixel_values), None
@@ -491,17 +509,17 @@ class FlamingoModel(PreTrainedModel):
             res = D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, generator=generator, processors=procs,
                                    sampling=D.Sampling(float(temperature), int(top_k), float(top_p)) if do_sample else None,
                                    beams=D.Beams(int(num_beams), bool(early_stopping), float(length_penalty)) if num_beams > 1 else None,
-                                   logprobs=bool(output_logprobs), n_return=n_beams_out)
+                                   logprobs=bool(output_logprobs), n_return=n_beams_out, **ckw)
         elif num_beams > 1:
             res = self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty, processors=procs,
-                                    n_return=n_beams_out)
+                                    n_return=n_beams_out, **ckw)
         else:
             # the log-softmax is taken in float32, the dtype of the logits _decode_step hands the loop; a model that computes in float64 keeps
             # its precision (a float32 log-softmax would throw away what a float64 evaluation on the host is run for)
             lp_dtype = (torch.float64 if next(self.parameters()).dtype == torch.float64 else torch.float32) if output_logprobs else None
             res = D.dynamic_decode(self._decode_step, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
                                    sampling=D.Sampling(temperature, top_k, top_p) if do_sample else None, generator=generator, processors=procs,
-                                   logprob_dtype=lp_dtype)
+                                   logprob_dtype=lp_dtype, **ckw)
         if not return_dict_in_generate:
             return res[0] if n_beams_out else res
         if n_beams_out:
@@ -518,20 +536,29 @@ class FlamingoModel(PreTrainedModel):
     def reset_decode_sessions(self) -> None:
         D._DECODE_SESSIONS.pop(self, None)
 
-    def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None, n_return=None):
+    def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None, n_return=None,
+                     **constraints):
         """The dynamic beam search (decoding.beam_search) over this model's _decode_step / _reorder_cache."""
         return D.beam_search(self._decode_step, self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors,
-                             n_return=n_return)
+                             n_return=n_return, **constraints)
 
     @torch.no_grad()
     def generate_captions(self, processor, pixel_values=None, images=None, prompt: str = "<image>", max_length: int = 150,
-                          num_beams: int = 1, device=None, return_scores: bool = False, **kwargs):
+                          num_beams: int = 1, device=None, return_scores: bool = False, candidates=None, bad_words=None, **kwargs):
         """Caption a batch of images; the prompt is replicated for every image (reference :550-605).  `kwargs` are generation
         arguments (do_sample, temperature, top_k, top_p, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length,
         min_new_tokens, num_return_sequences, output_logprobs, return_dict_in_generate, ...) and go to generate(), which rejects unknown ones.
         `return_scores=True` returns (captions, scores), the scores floats from GenerateOutput.sequences_scores (beam search: the score the
         search ranked by; greedy and sampling: the length-normalised sum of the token log-probabilities).  With num_return_sequences = n > 1
-        the captions (and the scores) are a list of one list of n per image."""
+        the captions (and the scores) are a list of one list of n per image.
+        `candidates` / `bad_words` (lists of strings) become generate()'s candidate_ids / bad_words_ids: every string is tokenised VERBATIM
+        with processor.tokenizer(s, add_special_tokens=False) - a leading space is part of the string and the caller's business (after a
+        prompt that ends in a word, BPE vocabularies spell the next word " cat", not "cat")."""
+        for name, strings in (("candidate_ids", candidates), ("bad_words_ids", bad_words)):
+            if strings is not None:
+                if isinstance(strings, str):
+                    raise ValueError(f"generate_captions(): pass a list of strings, got the string {strings!r}")
+                kwargs[name] = [list(processor.tokenizer(s, add_special_tokens=False)["input_ids"]) for s in strings]
         if device is None:
             device = self.device
         if images is not None:
@@ -564,9 +591,14 @@ class FlamingoModel(PreTrainedModel):
     @torch.no_grad()
     def score_sequences(self, input_ids, media_locations, attention_mask, pixel_values=None, visual_features=None,
                         k: int = 100000) -> torch.Tensor:
-        """EXPERIMENTAL zero-shot scoring (reference :607-712): log-prob of each candidate sequence given the same
-        visuals.  The shared prefix is run once with use_cache; its cross-attention K/V are reused for the candidates
-        (the LM self-attention prefix is recomputed: HF Cache objects are not sliceable per candidate)."""
+        """Zero-shot scoring as the reference has it (:607-712): the log-prob of each candidate sequence given the same visuals.  Kept for
+        parity; the SUPPORTED route for closed-set tasks (classification, multiple-choice VQA, yes/no) is constrained decoding:
+        generate(..., candidate_ids=, return_dict_in_generate=True, output_logprobs=True) - greedy or beam search restricted to the trie of
+        the candidates inside the cached, graph-replayed decode step, sequences_scores / token_logprobs giving the chosen candidate's
+        probability over the allowed set and num_return_sequences a top-n - which runs the prefix once and never materialises a per-candidate
+        log-softmax.  This method recomputes the LM prefix for every candidate and holds a (k, L, vocab) float32 log-softmax (1 GB for 1000
+        class names of 5 tokens at vocab 50258).  The shared prefix is run once with use_cache; its cross-attention K/V are reused for the
+        candidates (the LM self-attention prefix is recomputed: HF Cache objects are not sliceable per candidate)."""
         assert visual_features is None or visual_features.ndim == 3
         n_choices = input_ids.size(0)
         n_reuse = get_common_prefix_length(input_ids)

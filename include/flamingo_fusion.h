@@ -55,7 +55,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, additions only: stochastic rounding for pure-bf16 training, ff_adamw_step_sr, ff_stochastic_round_bf16;
                                 * still 6, addition only: logits processors on the captured decode step, ff_logits_process;
                                 * still 6, addition only: exponential moving average of the weights, ff_ema_update;
-                                * still 6, addition only: log-probability of the chosen token on the captured decode step, ff_token_logprob) */
+                                * still 6, addition only: log-probability of the chosen token on the captured decode step, ff_token_logprob;
+                                * still 6, addition only: constrained decoding on the captured decode step (candidate trie, bad words), ff_logits_constrain) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -666,6 +667,46 @@ int ff_logits_process(int dtype, int rows, int vocab, long long ld, void* logits
  * ------------------------------------------------------------------------------------------------------ */
 int ff_token_logprob(int dtype, int rows, int vocab, long long ld, const void* logits, const long long* token, const unsigned char* skip,
                      float* logprob, float* lse, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Constrained decoding on the captured decode step (added under ABI 6): a trie of candidate sequences and a list of banned words, applied
+ * IN PLACE to the rows a step is about to select from (argmax, ff_sample_token, ff_beam_step), after ff_logits_process.  The rules only
+ * ever write -inf.  One launch, no allocation, no host synchronisation, no global atomics, capturable; equal inputs give equal bits, eager
+ * or replayed.  Everything the kernel reads about the constraint lives in device memory, with CAPACITIES fixed at launch and live SIZES
+ * read on the device: one captured launch serves every candidate set and word list that fits the capacities.
+ * logits, hist, hist_ld, hist_cap, *hist_len: the contract of ff_logits_process (row r at element r * ld, ld >= vocab, element alignment
+ * only; int64 ids; *hist_len clamped to [0, hist_cap]: n; positions >= n are never read).  *gen_start: a device int64, clamped to
+ * [0, n]: n0, the position at which the generated tokens begin.  h = the row's first n tokens, g = h[n0 .. n), x = the row's logits.
+ * Trie (root = node 0) in CSR form: node_first[node_cap + 1] int32 - the edges of node s are node_first[s] .. node_first[s + 1] - ;
+ * edge_tok[edge_cap] int32, ascending and distinct inside a node; edge_child[edge_cap] int32; node_terminal[node_cap] bytes (non-zero: a
+ * candidate ends here); *n_nodes a device int32, clamped to [0, node_cap].  Entries beyond the live sizes (nodes >= *n_nodes, edges >=
+ * node_first[*n_nodes]) are never read.  *n_nodes == 0: the trie rule does nothing.
+ *   T1 (position).  s = root.  For each t in g, in order: s DONE or DEAD stays; t == eos and terminal(s): DONE; t is a child token of s:
+ *      that child; otherwise DEAD.  (A child token outside [0, vocab) still takes part.)
+ *   T2 (mask).  If s is a node, every x_v, v in [0, vocab), with v neither a child token of s nor eos when terminal(s), becomes -inf - a
+ *      banned NaN like any entry; every other entry keeps its bits.  If s is DONE or DEAD the trie rule leaves the row UNTOUCHED (an
+ *      all -inf row would give ff_beam_step an lse of -inf and NaN candidates; a dead beam already carries the score -inf).
+ * Bad words: bw_off[bw_cap + 1] int32 - word w is bw_tok[bw_off[w] .. bw_off[w + 1]) -, bw_tok[bw_tok_cap] int32, *n_bw a device int32,
+ * clamped to [0, bw_cap].
+ *   B1.  For each word w of length m >= 1, against the WHOLE history h, prompt included (as transformers does): m == 1: x[w_0] = -inf;
+ *      m > 1: if n >= m - 1 and h[n-m+1 .. n) == w[0 .. m-1) then x[w_{m-1}] = -inf.  A last token outside [0, vocab) names no logit;
+ *      earlier tokens outside the range still take part in the comparison.  A word of length 0 does nothing.
+ * The bans of T2 and B1 union.  Nothing outside [0, vocab) of a row is written.  A row left with nothing but -inf gives what
+ * ff_sample_token and ff_beam_step document for it: unspecified but in range.  Offsets and child indices that point outside the capacities
+ * are clamped or end the walk: a malformed table gives unspecified bans but no access outside the capacities.
+ * Either table may be absent (all of its pointers null); with both absent the call returns FF_OK and launches nothing.
+ * FF_ERR_SHAPE: null logits, hist, hist_len or gen_start; a table given in part; rows <= 0, vocab <= 0, ld < vocab; hist_cap < 1, hist_ld <
+ * hist_cap; a capacity of a given table < 1; eos outside [0, vocab) with a trie, outside [-1, vocab) without one.  FF_ERR_UNSUPPORTED:
+ * another dtype, hist_cap > FF_LOGITS_HIST_MAX, vocab > FF_CONSTRAIN_VOCAB_MAX (the allowed set is a vocab-bit bitmap in 32 KiB of LDS).
+ * All before any launch.
+ * ------------------------------------------------------------------------------------------------------ */
+#define FF_CONSTRAIN_VOCAB_MAX 262144
+int ff_logits_constrain(int dtype, int rows, int vocab, long long ld, void* logits,
+                        const long long* hist, long long hist_ld, long long hist_cap, const long long* hist_len, const long long* gen_start, int eos,
+                        const int* node_first, const int* edge_tok, const int* edge_child, const unsigned char* node_terminal, const int* n_nodes,
+                        int node_cap, int edge_cap,
+                        const int* bw_off, const int* bw_tok, const int* n_bw, int bw_cap, int bw_tok_cap,
+                        ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * QuickGELU of the CLIP vision tower, y = x * sigmoid(1.702 x) (transformers.activations.QuickGELUActivation, selected by
