@@ -10,6 +10,7 @@
 //                      union of its rows' top 2 nb.
 //   beam_merge_kernel  one wave per sequence: ranks the nb x 2 nb candidates by counting (keys are integers: a total order whatever the
 //                      row held), then lane 0 walks the best 2 nb as the Python loop does and writes the state block.
+// ff_group_beam_step (diverse beam search) is the same row pass and group_merge_kernel in place of beam_merge_kernel.
 // Every sum has a fixed order (thread-local in column order, xor butterfly in the wave, wave 0..3): equal inputs give equal bits.
 #include <cmath>
 
@@ -169,6 +170,106 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(BeamState st, const floa
     }
 }
 
+// Diverse beam search: one wave per sequence walks the G groups of gs = nb / G rows in order.  A group's penalty lowers at most nb - gs columns
+// of a row, so the row's best 2 gs penalised candidates lie among its best 2 gs + (nb - gs) <= 2 nb unpenalised ones: the row pass above (K =
+// 2 nb, the same workspace) already delivers them.  Per group: subtract lambda * c (c = live rows of earlier groups that chose the column in
+// this step; c = 0 leaves the bits alone), rank the group's gs x K candidates by counting, lane 0 walks the best 2 gs as beam_merge_kernel
+// does with nb = gs, and the tokens it chose are what the next group counts.  done / n_hyp are [b][G], hyp_* are read as [b][G][gs].
+__global__ __launch_bounds__(64) void group_merge_kernel(BeamState st, int G, float lambda, const float* __restrict__ cand_score,
+                                                         const int* __restrict__ cand_col) {
+#pragma clang fp contract(off)                                                     // rule A: the product and the difference are rounded separately
+    __shared__ float raw[FF_BEAM_MAX * kBeamCand];
+    __shared__ int col[FF_BEAM_MAX * kBeamCand];
+    __shared__ unsigned key[FF_BEAM_MAX * kBeamCand];
+    __shared__ float top_s[kBeamCand];
+    __shared__ int top_beam[kBeamCand], top_col[kBeamCand];
+    __shared__ float ns[FF_BEAM_MAX];
+    __shared__ int nt[FF_BEAM_MAX], np[FF_BEAM_MAX], live[FF_BEAM_MAX];
+    const int s = blockIdx.x, nb = st.nb, K = 2 * nb, gs = nb / G, m = gs * K, K2 = 2 * gs, tid = threadIdx.x;
+    const long long r0 = (long long)s * nb;
+    for (int j = tid; j < nb * K; j += 64) {
+        raw[j] = cand_score[r0 * K + j];
+        int c = cand_col[r0 * K + j];
+        col[j] = c < 0 ? 0 : (c >= st.vocab ? st.vocab - 1 : c);
+    }
+    long long cur = *st.cur_len;
+    cur = cur < 1 ? 1 : (cur > st.max_len ? st.max_len : cur);                     // (a length outside the tables: no write leaves them)
+    const float norm = st.len_norm[cur];
+    __syncthreads();
+    for (int g = 0; g < G; g++) {
+        const int b0 = g * gs, j0 = b0 * K;                                        // the group's first row and first candidate
+        for (int i = tid; i < m; i += 64) {
+            const int ci = col[j0 + i];
+            int c = 0;
+            for (int k = 0; k < b0; k++) c += live[k] && nt[k] == ci ? 1 : 0;
+            const float v = raw[j0 + i];
+            key[i] = ordered_key<32>(c ? v - lambda * (float)c : v);
+        }
+        __syncthreads();
+        for (int i = tid; i < m; i += 64) {
+            const unsigned ki = key[i];
+            const int bi = i / K, ci = col[j0 + i];
+            int rank = 0;
+            for (int j = 0; j < m; j++) {
+                const unsigned kj = key[j];
+                const int bj = j / K, cj = col[j0 + j];
+                const bool better = kj > ki || (kj == ki && (bj < bi || (bj == bi && (cj < ci || (cj == ci && j < i)))));
+                rank += better ? 1 : 0;
+            }
+            if (rank < K2) { top_s[rank] = ordered_value<32>(ki); top_beam[rank] = bi; top_col[rank] = ci; }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            float* hs = st.hyp_score + r0 + b0;
+            int* hl = st.hyp_len + r0 + b0;
+            int* hr = st.hyp_row + r0 + b0;
+            const long long sg = (long long)s * G + g;
+            for (int k = 0; k < gs; k++) { ns[b0 + k] = -INFINITY; nt[b0 + k] = st.pad; np[b0 + k] = b0 + k; }
+            if (!st.done[sg]) {
+                int nh = st.n_hyp[sg];
+                nh = nh < 0 ? 0 : (nh > gs ? gs : nh);
+                int k = 0;
+                for (int rank = 0; rank < K2 && k < gs; rank++) {
+                    const float v = top_s[rank];
+                    const int beam = top_beam[rank], tok = top_col[rank];
+                    if (st.eos >= 0 && tok == st.eos) {
+                        if (rank < gs) {                                             // a finished hypothesis of this group: sorted, equal scores in arrival order
+                            const float h = v / norm;
+                            int p = 0;
+                            while (p < nh && hs[p] >= h) p++;
+                            if (p < gs) {
+                                for (int j = nh < gs - 1 ? nh : gs - 1; j > p; j--) { hs[j] = hs[j - 1]; hl[j] = hl[j - 1]; hr[j] = hr[j - 1]; }
+                                hs[p] = h; hl[p] = (int)cur; hr[p] = (int)r0 + b0 + beam;
+                                nh = nh < gs ? nh + 1 : gs;
+                            }
+                        }
+                        continue;
+                    }
+                    ns[b0 + k] = v; nt[b0 + k] = tok; np[b0 + k] = b0 + beam;
+                    k++;
+                }
+                st.n_hyp[sg] = nh;
+                if (nh >= gs) {
+                    float best = ns[b0];
+                    for (int j = 1; j < gs; j++) best = fmaxf(best, ns[b0 + j]);
+                    if (st.early_stopping || hs[gs - 1] >= best / norm) st.done[sg] = 1;
+                }
+            }
+            for (int k = 0; k < gs; k++) live[b0 + k] = ns[b0 + k] > -INFINITY ? 1 : 0;      // (a NaN score counts nothing)
+        }
+        __syncthreads();
+    }
+    const long long h0 = (cur - 1) * (long long)st.b * nb + r0;
+    if (tid < nb) {
+        st.score[r0 + tid] = ns[tid];
+        st.next_tok[r0 + tid] = nt[tid];
+        st.beam_idx[r0 + tid] = r0 + np[tid];
+        st.hist_tok[h0 + tid] = nt[tid];
+        st.hist_parent[h0 + tid] = (int)r0 + np[tid];
+        st.hist_score[h0 + tid] = ns[tid];
+    }
+}
+
 template <typename T, bool STAGED>
 static int beam_rows_launch(int rows, int V, long long ld, const void* logits, int K, const float* score, float* cand_score, int* cand_col, hipStream_t st) {
     if (STAGED) FF_TRY((allow_dynamic_lds<beam_rows_kernel<T, STAGED>>(kBeamScratch + kRowStageMax * 2, "beam_rows")));
@@ -241,18 +342,24 @@ extern "C" size_t ff_beam_workspace_bytes(int b, int nb) {
     return (size_t)b * nb * 2 * nb * (sizeof(float) + sizeof(int));
 }
 
-extern "C" int ff_beam_step(const ff_beam_desc* d, const void* logits, const long long* cur_len, void* workspace, size_t workspace_bytes,
+// the argument checks ff_beam_step and ff_group_beam_step share, under the caller's name
+static int beam_step_check(const char* fn, const ff_beam_desc* d, const void* logits, const long long* cur_len, void* workspace, size_t workspace_bytes) {
+    FF_CHECK(d && logits && cur_len && workspace, FF_ERR_SHAPE, "%s: null descriptor, logits, cur_len or workspace", fn);
+    FF_CHECK(d->score && d->done && d->n_hyp && d->hyp_score && d->hyp_len && d->hyp_row && d->hist_tok && d->hist_parent && d->hist_score &&
+                 d->next_tok && d->beam_idx && d->len_norm, FF_ERR_SHAPE, "%s: null state pointer", fn);
+    FF_CHECK(d->b > 0 && d->nb >= 1 && d->nb <= FF_BEAM_MAX, FF_ERR_SHAPE, "%s: b %d, nb %d (need b > 0, 1 <= nb <= %d)", fn, d->b, d->nb, FF_BEAM_MAX);
+    FF_CHECK(d->vocab >= 2 * d->nb && d->ld >= d->vocab, FF_ERR_SHAPE, "%s: vocab %d, ld %lld (need vocab >= 2 nb = %d, ld >= vocab)", fn, d->vocab, d->ld, 2 * d->nb);
+    FF_CHECK(d->max_len >= 1 && (long long)d->b * d->nb <= 0x7FFFFFFF / (2 * FF_BEAM_MAX), FF_ERR_SHAPE, "%s: max_len %d, %d x %d rows", fn, d->max_len, d->b, d->nb);
+    FF_CHECK(workspace_bytes >= ff_beam_workspace_bytes(d->b, d->nb), FF_ERR_SHAPE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes,
+             ff_beam_workspace_bytes(d->b, d->nb));
+    FF_CHECK(d->dtype == FF_DTYPE_F32 || d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "%s: dtype %d", fn, d->dtype);
+    return FF_OK;
+}
+
+// the row pass and one merge: beam_merge_kernel without groups, group_merge_kernel with them (the same candidates in the same workspace)
+static int beam_step_launch(const ff_beam_desc* d, int n_groups, float diversity_penalty, const void* logits, const long long* cur_len, void* workspace,
                             ff_stream_t stream) {
     using namespace ff;
-    FF_CHECK(d && logits && cur_len && workspace, FF_ERR_SHAPE, "ff_beam_step: null descriptor, logits, cur_len or workspace");
-    FF_CHECK(d->score && d->done && d->n_hyp && d->hyp_score && d->hyp_len && d->hyp_row && d->hist_tok && d->hist_parent && d->hist_score &&
-                 d->next_tok && d->beam_idx && d->len_norm, FF_ERR_SHAPE, "ff_beam_step: null state pointer");
-    FF_CHECK(d->b > 0 && d->nb >= 1 && d->nb <= FF_BEAM_MAX, FF_ERR_SHAPE, "ff_beam_step: b %d, nb %d (need b > 0, 1 <= nb <= %d)", d->b, d->nb, FF_BEAM_MAX);
-    FF_CHECK(d->vocab >= 2 * d->nb && d->ld >= d->vocab, FF_ERR_SHAPE, "ff_beam_step: vocab %d, ld %lld (need vocab >= 2 nb = %d, ld >= vocab)", d->vocab, d->ld, 2 * d->nb);
-    FF_CHECK(d->max_len >= 1 && (long long)d->b * d->nb <= 0x7FFFFFFF / (2 * FF_BEAM_MAX), FF_ERR_SHAPE, "ff_beam_step: max_len %d, %d x %d rows", d->max_len, d->b, d->nb);
-    FF_CHECK(workspace_bytes >= ff_beam_workspace_bytes(d->b, d->nb), FF_ERR_SHAPE, "ff_beam_step: workspace %zu < %zu bytes", workspace_bytes,
-             ff_beam_workspace_bytes(d->b, d->nb));
-    FF_CHECK(d->dtype == FF_DTYPE_F32 || d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "ff_beam_step: dtype %d", d->dtype);
     const hipStream_t st = (hipStream_t)stream;
     const int rows = d->b * d->nb, K = 2 * d->nb, V = d->vocab;
     float* cand_score = (float*)workspace;
@@ -262,8 +369,27 @@ extern "C" int ff_beam_step(const ff_beam_desc* d, const void* logits, const lon
     }));
     BeamState s = {d->b, d->nb, V, d->max_len, d->eos, d->pad, d->early_stopping, d->score, d->done, d->n_hyp, d->hyp_score, d->hyp_len, d->hyp_row,
                    d->hist_tok, d->hist_parent, d->hist_score, d->next_tok, d->beam_idx, d->len_norm, cur_len};
-    beam_merge_kernel<<<dim3(d->b), dim3(64), 0, st>>>(s, cand_score, cand_col);
-    return check_launch("beam_merge");
+    if (n_groups == 1) {
+        beam_merge_kernel<<<dim3(d->b), dim3(64), 0, st>>>(s, cand_score, cand_col);
+        return check_launch("beam_merge");
+    }
+    group_merge_kernel<<<dim3(d->b), dim3(64), 0, st>>>(s, n_groups, diversity_penalty, cand_score, cand_col);
+    return check_launch("group_merge");
+}
+
+extern "C" int ff_beam_step(const ff_beam_desc* d, const void* logits, const long long* cur_len, void* workspace, size_t workspace_bytes,
+                            ff_stream_t stream) {
+    FF_TRY(beam_step_check("ff_beam_step", d, logits, cur_len, workspace, workspace_bytes));
+    return beam_step_launch(d, 1, 0.f, logits, cur_len, workspace, stream);
+}
+
+extern "C" int ff_group_beam_step(const ff_beam_desc* d, int n_groups, float diversity_penalty, const void* logits, const long long* cur_len,
+                                  void* workspace, size_t workspace_bytes, ff_stream_t stream) {
+    FF_TRY(beam_step_check("ff_group_beam_step", d, logits, cur_len, workspace, workspace_bytes));
+    FF_CHECK(n_groups >= 1 && d->nb % n_groups == 0, FF_ERR_SHAPE, "ff_group_beam_step: n_groups %d (need n_groups >= 1 and nb %d a multiple of it)", n_groups, d->nb);
+    FF_CHECK(diversity_penalty >= 0.f && std::isfinite(diversity_penalty), FF_ERR_SHAPE, "ff_group_beam_step: diversity_penalty %g (need a finite value >= 0)",
+             (double)diversity_penalty);
+    return beam_step_launch(d, n_groups, diversity_penalty, logits, cur_len, workspace, stream);   // one group IS ff_beam_step: the same two launches
 }
 
 extern "C" int ff_beam_gather(int n_tensors, void* const* tensors, int elem_size, int b, int nb, long long outer, long long len_max, long long inner,

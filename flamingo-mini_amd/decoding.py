@@ -17,6 +17,7 @@ from .graphs import _prepared_capture_stream
 # ---- options: NamedTuples, so they compare and hash equal to the plain tuples they replaced (session keys, tests, tools) ----
 Sampling = NamedTuple("Sampling", [("temperature", float), ("top_k", int), ("top_p", float)])
 Beams = NamedTuple("Beams", [("nb", int), ("early_stopping", bool), ("length_penalty", float)])
+Groups = NamedTuple("Groups", [("n", int), ("diversity_penalty", float)])      # diverse beam search: beside Beams, which keeps its three fields
 
 
 class Processors(NamedTuple):
@@ -215,6 +216,22 @@ def check_output_args(return_dict_in_generate, output_logprobs, num_return_seque
     return n
 
 
+def check_group_args(num_beam_groups, diversity_penalty, num_beams, do_sample) -> Optional[Groups]:
+    """The checks of generate()'s diverse-beam-search arguments.  Returns the Groups, None for one group (exactly the paths without them)."""
+    G, lam = num_beam_groups, diversity_penalty
+    if isinstance(G, bool) or not isinstance(G, int) or G < 1:
+        raise ValueError(f"generate(): num_beam_groups must be an integer >= 1, got {G!r}")
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0 <= lam < float("inf"):
+        raise ValueError(f"generate(): diversity_penalty must be a finite number >= 0 (0 = off), got {lam!r}")
+    if num_beams % G != 0:
+        raise ValueError(f"generate(): num_beams {num_beams} is not a multiple of num_beam_groups {G}")
+    if G > 1 and do_sample:
+        raise ValueError("generate(): num_beam_groups > 1 cannot be combined with do_sample")
+    if G == 1 and lam != 0:
+        raise ValueError("generate(): diversity_penalty needs num_beam_groups > 1 (one group has nobody to differ from)")
+    return Groups(G, float(lam)) if G > 1 else None
+
+
 def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
     """sum(token_logprobs) / float32(len ** length_penalty) per row, len = L0 + the generated tokens up to and including eos: beam search's
     normalisation (BeamState.len_norm) applied to greedy and sampled sequences."""
@@ -350,7 +367,7 @@ def _pad_finished(nxt, finished, eos, pad):
 _DECODE_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
-def _beam_finalize(state, L0, prompt_ids, nb, pad, *, n_return=None):
+def _beam_finalize(state, L0, prompt_ids, nb, pad, *, n_return=None, n_groups=1):
     """The result of a beam search from the state block of ff_beam_step, on the host (numpy only; `state` = BeamState.to_host(), plus
     "length" = the sequences' length after the last step, default: the whole history): per sequence the best finished hypothesis - or, when
     the sequence is not done (the length limit), the best of the hypotheses and the open beams, normalised in float32 by len_norm[length],
@@ -358,8 +375,12 @@ def _beam_finalize(state, L0, prompt_ids, nb, pad, *, n_return=None):
     downwards from the entry's row; rows are padded with `pad` to the longest.  Returns (b, width) int64 on the CPU.
     With `n_return` = n it returns (ids (b * n, width), scores (b * n,) float32): per sequence the n best of the same entries, best first,
     the earlier entry on equal scores, each with the normalised score it was ranked by; where fewer than n entries exist the missing rows
-    are all `pad` with score -inf."""
+    are all `pad` with score -inf.
+    With `n_groups` = G > 1 (the block of ff_group_beam_step) the entries of a sequence are listed group by group, g = 0 .. G - 1: g's
+    hypotheses, then g's open beams if g is not done; the ranking is the same stable sort.  Groups may hold the same sequence (the penalty
+    is soft), and the scores carry the accumulated penalties."""
     import numpy as np
+    G, gs = n_groups, nb // n_groups
     hist_tok, hist_parent, len_norm = state["hist_tok"], state["hist_parent"], state["len_norm"]
     length, eos = int(state.get("length", hist_tok.shape[0])), int(state.get("eos", -1))
     prompt = np.asarray(prompt_ids)
@@ -372,12 +393,16 @@ def _beam_finalize(state, L0, prompt_ids, nb, pad, *, n_return=None):
         return toks[::-1]
 
     out, scores = [], []
-    for s in range(state["score"].shape[0]):
-        hyps = [(np.float32(state["hyp_score"][s, j]), (int(state["hyp_row"][s, j]), int(state["hyp_len"][s, j]) - 2, [eos]))
-                for j in range(int(state["n_hyp"][s]))]
-        if not state["done"][s]:
-            hyps += [(np.float32(state["score"][s, k]) / np.float32(len_norm[length]), (s * nb + k, length - 1, []))
-                     for k in range(nb) if state["score"][s, k] > -np.inf]
+    n_seq = state["score"].shape[0]
+    n_hyp, done = np.reshape(state["n_hyp"], (n_seq, G)), np.reshape(state["done"], (n_seq, G))
+    for s in range(n_seq):
+        hyps = []
+        for g in range(G):
+            hyps += [(np.float32(state["hyp_score"][s, j]), (int(state["hyp_row"][s, j]), int(state["hyp_len"][s, j]) - 2, [eos]))
+                     for j in range(g * gs, g * gs + int(n_hyp[s, g]))]
+            if not done[s, g]:
+                hyps += [(np.float32(state["score"][s, k]) / np.float32(len_norm[length]), (s * nb + k, length - 1, []))
+                         for k in range(g * gs, (g + 1) * gs) if state["score"][s, k] > -np.inf]
         order = sorted(range(len(hyps)), key=lambda j: -hyps[j][0])            # (a stable sort: the earlier entry on equal scores)
         for j in range(1 if n_return is None else n_return):
             if j < len(order):
@@ -413,10 +438,11 @@ class _DecodeSession:
     nb = 1                                 # rows per sequence
 
     def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None, logprobs=False,
-                 constraints=None):
+                 constraints=None, groups=None):
         from transformers.cache_utils import StaticCache
         self._model_ref = weakref.ref(model)
         self.sampling, self.beams, self.processors, self.logprobs, self.constraints = sampling, beams, processors, logprobs, constraints
+        self.groups = groups
         self.n_seq = b
         b = b * self.nb
         self.b, self.max_length, self.eos, self.graph_wanted = b, max_length, eos, graph
@@ -628,7 +654,10 @@ class _BeamSession(_DecodeSession):
     sequence's beams and are NOT reordered.  The result is read back once, after the loop (_beam_finalize).
     The processors read `seq_buf` (b * nb, max_length), which follows the beams through the same in-place gather as the LM cache (viewed as
     two 4-byte elements per id), and so do the constraints: a beam's position in the trie is a function of its own tokens.  A session with
-    neither allocates no seq_buf."""
+    neither allocates no seq_buf.
+    `groups` (a Groups) makes it DIVERSE beam search: the state block is built with n_groups, _select calls functional.group_beam_step with
+    the penalty as a launch constant, and everything else - the gathers, seq_buf, the processors, the constraints - acts per row and is what
+    it was.  A session without groups calls beam_step."""
 
     def __init__(self, model, b, *args, beams, **kw):
         self.nb = beams.nb
@@ -636,7 +665,8 @@ class _BeamSession(_DecodeSession):
 
     def _alloc(self):
         dev = self.pos.device
-        self.state = F.BeamState(self.n_seq, self.nb, self.max_length, dev, eos=self.eos, pad=self.fill, early_stopping=self.beams.early_stopping, length_penalty=self.beams.length_penalty)
+        self.state = F.BeamState(self.n_seq, self.nb, self.max_length, dev, eos=self.eos, pad=self.fill, early_stopping=self.beams.early_stopping, length_penalty=self.beams.length_penalty,
+                                 **({"n_groups": self.groups.n} if self.groups is not None else {}))
         self.cur_len = torch.zeros((1,), dtype=torch.long, device=dev)        # pos + 1: the length after the token beam_step chooses
         self.lm_tensors = None                                                # keys / values of every StaticCache layer (allocated by the first prompt step)
         if self.processors is not None:
@@ -665,7 +695,10 @@ class _BeamSession(_DecodeSession):
         if self.lm_tensors is None:
             self.lm_tensors = [t for layer in self.cache.layers for t in (layer.keys, layer.values)]
         torch.add(self.pos, 1, out=self.cur_len)
-        nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
+        if self.groups is None:
+            nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
+        else:
+            nxt, beam_idx = F.group_beam_step(logits, self.state, self.cur_len, self.groups.diversity_penalty)
         F.beam_gather(self.lm_tensors, beam_idx, self.pos, self.nb)           # positions < pos are live: the cache rows follow their beams
         if hasattr(self, "seq_buf"):                                          # ... and so do the histories: an id is two 4-byte elements
             F.beam_gather([self.seq_buf.view(torch.int32).view(self.b, 1, self.max_length, 2)], beam_idx, self.pos, self.nb)
@@ -678,12 +711,12 @@ class _BeamSession(_DecodeSession):
     def _result(self, L0, prompt_ids, length, n_return=None):    # one device-to-host copy; steps past the last `done` only wrote padding
         host = self.state.to_host()
         host["length"] = length
-        res = _beam_finalize(host, L0, prompt_ids.cpu(), self.nb, self.fill, n_return=n_return)
+        res = _beam_finalize(host, L0, prompt_ids.cpu(), self.nb, self.fill, n_return=n_return, **({"n_groups": self.groups.n} if self.groups is not None else {}))
         return res.to(prompt_ids.device) if n_return is None else tuple(t.to(prompt_ids.device) for t in res)
 
 
 def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, beams=None, processors=None,
-                   logprobs=False, n_return=None, constraints=None):
+                   logprobs=False, n_return=None, constraints=None, groups=None):
     """Greedy, sampled (`sampling`) or beam-search (`beams`) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches
     and buffers plus, on the GPU, the captured HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, device,
     eos, pad, graph, sampling, beams, processors) and reused by later calls, so only the first caption batch of a shape pays for the
@@ -692,7 +725,9 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
     `logprobs` (greedy and sampling) selects a session that records the chosen tokens' log-probabilities: its key is the same ten elements
     followed by "logprobs", and the call returns (ids, token_logprobs).  `n_return` (beam search) returns (ids, scores) with the n best
     entries per sequence (_beam_finalize); it changes nothing in the session.  `constraints` (a Constraints) selects a session that decodes
-    under a candidate trie and / or banned words: its key ends with Constraints.caps() - the tables' capacities, not their contents."""
+    under a candidate trie and / or banned words: its key ends with Constraints.caps() - the tables' capacities, not their contents.
+    `groups` (a Groups, with `beams`) selects a diverse-beam-search session: its key ends with the Groups - the penalty is a launch constant of
+    the captured step.  A call without groups builds the key it always built."""
     b = ids.shape[0]
     graph = ids.is_cuda and not model.training and model.decode_graph
     sessions = _DECODE_SESSIONS.setdefault(model, {})
@@ -701,6 +736,8 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
     key = (b, max_length, n_media, str(ids.device), eos, pad, bool(graph), sampling, beams, processors) + (("logprobs",) if logprobs else ())
     if constraints is not None:
         key += (constraints.caps(),)
+    if groups is not None:
+        key += (groups,)
     sess = sessions.get(key)
     if sess is not None and sess.stale():
         sessions.pop(key)
@@ -710,7 +747,7 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
             sessions.pop(next(iter(sessions)))
         cls = _TokenSession if beams is None else _BeamSession
         sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors, logprobs=logprobs,
-                                   **({"constraints": constraints.caps()} if constraints is not None else {}))
+                                   **({"constraints": constraints.caps()} if constraints is not None else {}), **({"groups": groups} if groups is not None else {}))
     return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator, n_return=n_return, **({"constraints": constraints} if constraints is not None else {}))
 
 
@@ -748,12 +785,17 @@ def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length,
 
 
 def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None,
-                n_return=None, constraints=None):
+                n_return=None, constraints=None, groups=None):
     """Standard beam search over the cached decode path; `step` / `reorder_cache` are FlamingoModel._decode_step / ._reorder_cache.  The
     prompt runs once per sequence; its caches are then replicated per beam (xattn K/V: repeat_interleave; LM cache:
     Cache.batch_repeat_interleave) and re-ordered every step.  `processors` act on every step's logits before the log-softmax.
     With `n_return` = n it returns (ids (b * n, width), scores (b * n,) float32): per sequence the n best of what the tail ranks, best first,
-    the earlier entry on equal scores, with their normalised scores; missing rows are all pad with score -inf (as _beam_finalize)."""
+    the earlier entry on equal scores, with their normalised scores; missing rows are all pad with score -inf (as _beam_finalize).
+    With `groups` (a Groups) it is DIVERSE beam search, rules A - D of ff_group_beam_step (include/flamingo_fusion.h) restated in torch: the
+    nb beams are G groups of gs, inside a step the groups are searched in order, and a group's candidates pay the penalty for every live next
+    beam of an earlier group that carries their token (the product and the difference rounded in float32); each group has its own
+    hypotheses and done flag, and the tail ranks all groups' entries together.  It also runs on CPU tensors.  Without groups nothing
+    changes: one group of nb beams, the same topk, the same calls."""
     b, L0 = ids.shape
     dev = ids.device
     process = _dynamic_processor(processors, eos, L0, constraints)
@@ -769,43 +811,60 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
     past = (xattn_past, lm_past)
     seqs = _repeat_leading(ids, nb)                                   # (b * nb, L)
     ml, am = _repeat_leading(ml, nb), _repeat_leading(am, nb)
+    G, lam = (groups.n, torch.tensor(groups.diversity_penalty, dtype=torch.float32)) if groups is not None else (1, None)
+    gs = nb // G                                                      # beams per group (no groups: one group of nb)
     scores = torch.full((b, nb), float("-inf"), device=dev)
-    scores[:, 0] = 0.0                                                # all beams of a sequence start identical: only one may branch
+    scores[:, ::gs] = 0.0                                             # all beams of a group start identical: only one may branch
     logp = _repeat_leading(logp, nb)
-    done_hyps = [[] for _ in range(b)]                                # (normalised score, token list) per sequence
-    is_done = [False] * b
+    done_hyps = [[[] for _ in range(G)] for _ in range(b)]            # (normalised score, token list) per sequence and group
+    is_done = [[False] * G for _ in range(b)]
     while True:
         cand = (scores.reshape(-1, 1) + logp).reshape(b, nb * V)
-        top_s, top_i = cand.topk(2 * nb, dim=-1)
         cur_len = seqs.shape[1] + 1
         next_scores = torch.full((b, nb), float("-inf"), device=dev)
         next_tok = torch.full((b, nb), pad if pad is not None else 0, dtype=torch.long, device=dev)
         next_src = torch.arange(nb, device=dev).repeat(b, 1)
-        top_s_c, top_i_c = top_s.cpu(), top_i.cpu()
+        if groups is None:
+            top_s, top_i = cand.topk(2 * nb, dim=-1)
+            top_s_c, top_i_c = top_s.cpu(), top_i.cpu()
+        else:
+            cand_c = cand.cpu().reshape(b, nb, V)
         for bi in range(b):
-            if is_done[bi]:
-                continue
-            k = 0
-            for rank in range(2 * nb):
-                s_, i_ = float(top_s_c[bi, rank]), int(top_i_c[bi, rank])
-                beam, tok = i_ // V, i_ % V
-                if eos is not None and tok == eos:
-                    if rank < nb:
-                        done_hyps[bi].append((s_ / (cur_len ** length_penalty), seqs[bi * nb + beam].tolist() + [tok]))
+            chosen = {}                                               # token -> live next beams of the earlier groups that carry it (rule A's c)
+            for g in range(G):
+                if is_done[bi][g]:
                     continue
-                next_scores[bi, k], next_tok[bi, k], next_src[bi, k] = s_, tok, beam
-                k += 1
-                if k == nb:
-                    break
-            if len(done_hyps[bi]) >= nb:
-                done_hyps[bi] = sorted(done_hyps[bi], key=lambda t: -t[0])[:nb]
-                best_open = float(next_scores[bi].max()) / (cur_len ** length_penalty)
-                if early_stopping or done_hyps[bi][-1][0] >= best_open:
-                    is_done[bi] = True
+                if groups is not None:                                # rule A, then rule B's order: score, then row, then column (a stable sort)
+                    x = cand_c[bi, g * gs:(g + 1) * gs].clone()
+                    for tok, c in chosen.items():
+                        x[:, tok] = x[:, tok] - lam * float(c)
+                    top_s_g, top_i_g = x.reshape(-1).sort(descending=True, stable=True)
+                    ranked = zip(top_s_g[:2 * gs].tolist(), top_i_g[:2 * gs].tolist())
+                else:
+                    ranked = zip(top_s_c[bi].tolist(), top_i_c[bi].tolist())
+                hyps_g, k = done_hyps[bi][g], g * gs
+                for rank, (s_, i_) in enumerate(ranked):
+                    beam, tok = g * gs + i_ // V, i_ % V
+                    if eos is not None and tok == eos:
+                        if rank < gs:
+                            hyps_g.append((s_ / (cur_len ** length_penalty), seqs[bi * nb + beam].tolist() + [tok]))
+                        continue
+                    next_scores[bi, k], next_tok[bi, k], next_src[bi, k] = s_, tok, beam
+                    k += 1
+                    if k == (g + 1) * gs:
+                        break
+                if len(hyps_g) >= gs:
+                    hyps_g[:] = sorted(hyps_g, key=lambda t: -t[0])[:gs]
+                    best_open = float(next_scores[bi, g * gs:(g + 1) * gs].max()) / (cur_len ** length_penalty)
+                    if early_stopping or hyps_g[-1][0] >= best_open:
+                        is_done[bi][g] = True
+                for k in range(g * gs, (g + 1) * gs if groups is not None else 0):
+                    if float(next_scores[bi, k]) > float("-inf"):
+                        chosen[int(next_tok[bi, k])] = chosen.get(int(next_tok[bi, k]), 0) + 1
         beam_idx = (next_src + torch.arange(b, device=dev)[:, None] * nb).reshape(-1)
         seqs = torch.cat([seqs.index_select(0, beam_idx), next_tok.reshape(-1, 1)], dim=1)
         scores = next_scores
-        if all(is_done) or seqs.shape[1] >= max_length:
+        if all(all(d) for d in is_done) or seqs.shape[1] >= max_length:
             break
         past = reorder_cache(past, beam_idx)
         ml = torch.cat([ml, torch.zeros_like(ml[:, :1])], dim=1)
@@ -814,10 +873,12 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
         logp = process(logits, seqs).log_softmax(-1)
     out, out_scores = [], []
     for bi in range(b):
-        hyps = list(done_hyps[bi])
-        if not is_done[bi]:                                           # length limit: the open beams count as hypotheses too
-            hyps += [(float(scores[bi, k]) / (seqs.shape[1] ** length_penalty), seqs[bi * nb + k].tolist()) for k in range(nb)
-                     if float(scores[bi, k]) > float("-inf")]
+        hyps = []
+        for g in range(G):                                            # rule D: group by group, a group's hypotheses, then its open beams
+            hyps += done_hyps[bi][g]
+            if not is_done[bi][g]:                                    # length limit: the open beams count as hypotheses too
+                hyps += [(float(scores[bi, k]) / (seqs.shape[1] ** length_penalty), seqs[bi * nb + k].tolist()) for k in range(g * gs, (g + 1) * gs)
+                         if float(scores[bi, k]) > float("-inf")]
         if n_return is None:
             out.append(max(hyps, key=lambda t: t[0])[1])
             continue

@@ -1068,12 +1068,16 @@ class BeamState:
     """The device state block of ff_beam_step for b sequences x nb beams and histories of max_len positions (layout and rules:
     include/flamingo_fusion.h).  All fields are views of ONE byte buffer, so `to_host()` is one device-to-host copy.  `storage` (uint8,
     at least BeamState.nbytes(b, nb, max_len) bytes, 16-byte aligned) lets the caller own the memory.  reset() is the initialisation the
-    library expects: score[:, 0] = 0, every other score -inf, nothing done, no hypotheses."""
+    library expects: score[:, 0] = 0, every other score -inf, nothing done, no hypotheses.
+    `n_groups` = G > 1 makes it the block of ff_group_beam_step (diverse beam search, nb a multiple of G): `done` and `n_hyp` are (b, G), the
+    hypothesis tables are read as (b, G, nb / G), and reset() gives beam 0 of EVERY group the score 0.  With G = 1 the block is what it was,
+    byte for byte."""
 
     @staticmethod
-    def _layout(b: int, nb: int, max_len: int):
+    def _layout(b: int, nb: int, max_len: int, n_groups: int = 1):
         rows = b * nb
-        fields = [("score", (b, nb), torch.float32), ("done", (b,), torch.int32), ("n_hyp", (b,), torch.int32),
+        per_seq = (b,) if n_groups == 1 else (b, n_groups)
+        fields = [("score", (b, nb), torch.float32), ("done", per_seq, torch.int32), ("n_hyp", per_seq, torch.int32),
                   ("hyp_score", (b, nb), torch.float32), ("hyp_len", (b, nb), torch.int32), ("hyp_row", (b, nb), torch.int32),
                   ("hist_tok", (max_len, rows), torch.int64), ("hist_parent", (max_len, rows), torch.int32),
                   ("hist_score", (max_len, rows), torch.float32), ("next_tok", (rows,), torch.int64), ("beam_idx", (rows,), torch.int64),
@@ -1089,16 +1093,18 @@ class BeamState:
         return out, off
 
     @staticmethod
-    def nbytes(b: int, nb: int, max_len: int) -> int:
-        return BeamState._layout(b, nb, max_len)[1]
+    def nbytes(b: int, nb: int, max_len: int, n_groups: int = 1) -> int:
+        return BeamState._layout(b, nb, max_len, n_groups)[1]
 
     def __init__(self, b: int, nb: int, max_len: int, device, eos: Optional[int] = None, pad: int = 0, early_stopping: bool = True,
-                 length_penalty: float = 1.0, storage: Optional[torch.Tensor] = None):
+                 length_penalty: float = 1.0, storage: Optional[torch.Tensor] = None, n_groups: int = 1):
         if not 1 <= nb <= ffi.BEAM_MAX or b <= 0 or max_len < 1:
             raise ValueError(f"BeamState: b {b}, nb {nb} (1 .. {ffi.BEAM_MAX}), max_len {max_len}")
-        self.b, self.nb, self.max_len = b, nb, max_len
+        if isinstance(n_groups, bool) or not isinstance(n_groups, int) or n_groups < 1 or nb % n_groups:
+            raise ValueError(f"BeamState: n_groups {n_groups!r} must be an integer >= 1 that divides nb {nb}")
+        self.b, self.nb, self.max_len, self.n_groups = b, nb, max_len, n_groups
         self.eos, self.pad, self.early_stopping, self.length_penalty = eos, pad, bool(early_stopping), float(length_penalty)
-        fields, total = self._layout(b, nb, max_len)
+        fields, total = self._layout(b, nb, max_len, n_groups)
         if storage is None:
             storage = _new((total,), torch.uint8, device)
         ffi.require_cuda(storage)
@@ -1114,7 +1120,7 @@ class BeamState:
         import numpy as np
         self.storage.zero_()
         self.score.fill_(float("-inf"))
-        self.score[:, 0] = 0.0
+        self.score[:, ::self.nb // self.n_groups] = 0.0                      # beam 0 of every group (one group: column 0)
         self.hyp_score.fill_(float("-inf"))
         self.next_tok.fill_(self.pad)
         self.beam_idx.copy_(torch.arange(self.b * self.nb, device=self.storage.device))
@@ -1124,9 +1130,24 @@ class BeamState:
     def to_host(self) -> dict:
         """Every field as a numpy array, from one device-to-host copy."""
         host = self.storage.cpu()
-        out = {name: host[off:off + nbytes].view(dt).view(shape).numpy() for name, shape, dt, off, nbytes in self._layout(self.b, self.nb, self.max_len)[0]}
+        out = {name: host[off:off + nbytes].view(dt).view(shape).numpy() for name, shape, dt, off, nbytes in self._layout(self.b, self.nb, self.max_len, self.n_groups)[0]}
         out["eos"] = -1 if self.eos is None else int(self.eos)
         return out
+
+
+def _beam_desc(fn: str, logits: torch.Tensor, state: BeamState, cur_len: torch.Tensor):
+    """The checks beam_step and group_beam_step share, and the ff_beam_desc of the call."""
+    ffi.require_cuda(logits, cur_len)
+    rows = state.b * state.nb
+    if logits.ndim != 2 or logits.shape[0] != rows or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"{fn}: logits must be ({rows}, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
+    if cur_len.dtype != torch.long or cur_len.numel() != 1:
+        raise ValueError(f"{fn}: cur_len must be one int64 value on the device, got {tuple(cur_len.shape)} {cur_len.dtype}")
+    V = logits.shape[1]
+    return ffi.BeamDesc(ffi.dtype_code(logits.dtype), state.b, state.nb, V, logits.stride(0) if rows > 1 else V, state.max_len,
+                        -1 if state.eos is None else int(state.eos), int(state.pad), int(state.early_stopping),
+                        *(getattr(state, n).data_ptr() for n in ("score", "done", "n_hyp", "hyp_score", "hyp_len", "hyp_row", "hist_tok", "hist_parent",
+                                                                 "hist_score", "next_tok", "beam_idx", "len_norm")))
 
 
 def beam_step(logits: torch.Tensor, state: BeamState, cur_len: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1134,19 +1155,25 @@ def beam_step(logits: torch.Tensor, state: BeamState, cur_len: torch.Tensor) -> 
     logits3d[:, -1] is read in place): ff_beam_step, two launches, everything stays on the device and nothing is allocated, so the call can be
     captured.  `cur_len` is a one-element int64 device tensor, the length the sequences have after this step's token.  Returns
     (state.next_tok, state.beam_idx); the rules are in include/flamingo_fusion.h."""
-    ffi.require_cuda(logits, cur_len)
-    rows = state.b * state.nb
-    if logits.ndim != 2 or logits.shape[0] != rows or (logits.shape[1] > 1 and logits.stride(1) != 1):
-        raise ValueError(f"beam_step: logits must be ({rows}, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
-    if cur_len.dtype != torch.long or cur_len.numel() != 1:
-        raise ValueError(f"beam_step: cur_len must be one int64 value on the device, got {tuple(cur_len.shape)} {cur_len.dtype}")
-    V = logits.shape[1]
-    d = ffi.BeamDesc(ffi.dtype_code(logits.dtype), state.b, state.nb, V, logits.stride(0) if rows > 1 else V, state.max_len,
-                     -1 if state.eos is None else int(state.eos), int(state.pad), int(state.early_stopping),
-                     *(getattr(state, n).data_ptr() for n in ("score", "done", "n_hyp", "hyp_score", "hyp_len", "hyp_row", "hist_tok", "hist_parent",
-                                                              "hist_score", "next_tok", "beam_idx", "len_norm")))
+    d = _beam_desc("beam_step", logits, state, cur_len)
+    if state.n_groups != 1:
+        raise ValueError(f"beam_step: the state has {state.n_groups} groups (group_beam_step is its step)")
     ffi.check(ffi.lib().ff_beam_step(d, logits.data_ptr(), cur_len.data_ptr(), state.workspace.data_ptr(), state.workspace.numel(),
                                      ffi.stream_handle(logits.device)), "ff_beam_step")
+    return state.next_tok, state.beam_idx
+
+
+def group_beam_step(logits: torch.Tensor, state: BeamState, cur_len: torch.Tensor, diversity_penalty: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One diverse-beam-search selection: beam_step for a BeamState built with n_groups = G.  The groups of a sequence are searched one after
+    another inside the call, and a group's candidate pays `diversity_penalty` (>= 0, finite; a launch constant) for every live beam of an
+    earlier group that chose its token in this step (rules A, B of ff_group_beam_step in include/flamingo_fusion.h).  Two launches - the row
+    pass of beam_step and one group walk -, nothing allocated, capturable.  Returns (state.next_tok, state.beam_idx)."""
+    d = _beam_desc("group_beam_step", logits, state, cur_len)
+    lam = float(diversity_penalty)
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError(f"group_beam_step: diversity_penalty must be finite and >= 0, got {diversity_penalty!r}")
+    ffi.check(ffi.lib().ff_group_beam_step(d, state.n_groups, lam, logits.data_ptr(), cur_len.data_ptr(), state.workspace.data_ptr(), state.workspace.numel(),
+                                           ffi.stream_handle(logits.device)), "ff_group_beam_step")
     return state.next_tok, state.beam_idx
 
 

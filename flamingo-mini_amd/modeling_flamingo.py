@@ -440,7 +440,8 @@ class FlamingoModel(PreTrainedModel):
                  early_stopping: bool = True, length_penalty: float = 1.0, use_cache: bool = True, generator: Optional[torch.Generator] = None,
                  input_ids=None, static_decode: Optional[bool] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_length: int = 0, min_new_tokens: int = 0, return_dict_in_generate: bool = False, output_logprobs: bool = False,
-                 num_return_sequences: int = 1, candidate_ids=None, bad_words_ids=None, **unsupported):
+                 num_return_sequences: int = 1, candidate_ids=None, bad_words_ids=None, num_beam_groups: int = 1,
+                 diversity_penalty: float = 0.0, **unsupported):
         """Text generation with the cached cross-attention path: the first step runs CLIP + resampler and fills the xattn K/V and LM caches,
         every later step feeds one token (reference: HF `generate` through prepare_inputs_for_generation / _reorder_cache, :464-548).
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
@@ -484,9 +485,21 @@ class FlamingoModel(PreTrainedModel):
         of two) reuses the session and its captured graph; on the dynamic paths decoding.constrain_logits_torch, which - unlike the
         processors - also runs on CPU tensors.  Known and accepted: beam search with fewer candidates than beams and early_stopping=False
         never collects num_beams hypotheses, so it runs to max_length with dead beams (score -inf); the result is still the best
-        candidates, on both paths.  The candidates are one set for the whole batch."""
+        candidates, on both paths.  The candidates are one set for the whole batch.
+        Diverse beam search (Vijayakumar et al.): `num_beam_groups=G` (it must divide num_beams; not with do_sample) splits the beams into G
+        groups of num_beams / G that are searched one after another inside every step, and `diversity_penalty` (>= 0, finite; it needs G > 1)
+        is subtracted from a group's candidate once for every live beam of an earlier group that chose the same token in that step.  Every
+        group keeps its own hypotheses and stops on its own; the result ranks the entries of all groups together, so
+        num_return_sequences=n returns the n best across the groups.  The penalised score is the beam's running score, penalties
+        accumulate over the steps as in the published algorithm: sequences_scores under groups are NOT pure log-probabilities.  The
+        penalty is soft, so two groups may still return the same sequence.  G = 1 is plain beam search, call for call; G > 1 with penalty 0
+        runs G independent searches of num_beams / G beams.  Routing is that of beam search: the static session (functional.group_beam_step
+        inside the replayed step: the row pass of beam_step and one group walk, no host round trip) only with static_decode=True, otherwise
+        the dynamic loop, which also runs on CPU tensors."""
         procs = D.check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos_token_id)
         n_ret = D.check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample)
+        groups = D.check_group_args(num_beam_groups, diversity_penalty, num_beams, do_sample)
+        gkw = {} if groups is None else {"groups": groups}                   # nothing is passed on without groups: the calls are what they were
         ids = inputs if inputs is not None else input_ids
         assert ids is not None and media_locations is not None, "generate() needs input ids and media_locations"
         cons = D.check_constraint_args(candidate_ids, bad_words_ids, self.flamingo.lm.config.vocab_size, eos_token_id, procs, ids.shape[1], max_length)
@@ -509,10 +522,10 @@ class FlamingoModel(PreTrainedModel):
             res = D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, generator=generator, processors=procs,
                                    sampling=D.Sampling(float(temperature), int(top_k), float(top_p)) if do_sample else None,
                                    beams=D.Beams(int(num_beams), bool(early_stopping), float(length_penalty)) if num_beams > 1 else None,
-                                   logprobs=bool(output_logprobs), n_return=n_beams_out, **ckw)
+                                   logprobs=bool(output_logprobs), n_return=n_beams_out, **ckw, **gkw)
         elif num_beams > 1:
             res = self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty, processors=procs,
-                                    n_return=n_beams_out, **ckw)
+                                    n_return=n_beams_out, **ckw, **gkw)
         else:
             # the log-softmax is taken in float32, the dtype of the logits _decode_step hands the loop; a model that computes in float64 keeps
             # its precision (a float32 log-softmax would throw away what a float64 evaluation on the host is run for)
@@ -538,7 +551,8 @@ class FlamingoModel(PreTrainedModel):
 
     def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None, n_return=None,
                      **constraints):
-        """The dynamic beam search (decoding.beam_search) over this model's _decode_step / _reorder_cache."""
+        """The dynamic beam search (decoding.beam_search) over this model's _decode_step / _reorder_cache; `constraints=` and `groups=` travel
+        as keywords and only when given."""
         return D.beam_search(self._decode_step, self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors,
                              n_return=n_return, **constraints)
 
@@ -547,7 +561,9 @@ class FlamingoModel(PreTrainedModel):
                           num_beams: int = 1, device=None, return_scores: bool = False, candidates=None, bad_words=None, **kwargs):
         """Caption a batch of images; the prompt is replicated for every image (reference :550-605).  `kwargs` are generation
         arguments (do_sample, temperature, top_k, top_p, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length,
-        min_new_tokens, num_return_sequences, output_logprobs, return_dict_in_generate, ...) and go to generate(), which rejects unknown ones.
+        min_new_tokens, num_return_sequences, output_logprobs, return_dict_in_generate, num_beam_groups, diversity_penalty, ...) and go to
+        generate(), which rejects unknown ones.  num_beams=4, num_beam_groups=4, diversity_penalty=1.0, num_return_sequences=4,
+        return_scores=True gives the 4 best DIFFERENT captions of diverse beam search with the (penalised) scores they were ranked by.
         `return_scores=True` returns (captions, scores), the scores floats from GenerateOutput.sequences_scores (beam search: the score the
         search ranked by; greedy and sampling: the length-normalised sum of the token log-probabilities).  With num_return_sequences = n > 1
         the captions (and the scores) are a list of one list of n per image.

@@ -56,7 +56,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, addition only: logits processors on the captured decode step, ff_logits_process;
                                 * still 6, addition only: exponential moving average of the weights, ff_ema_update;
                                 * still 6, addition only: log-probability of the chosen token on the captured decode step, ff_token_logprob;
-                                * still 6, addition only: constrained decoding on the captured decode step (candidate trie, bad words), ff_logits_constrain) */
+                                * still 6, addition only: constrained decoding on the captured decode step (candidate trie, bad words), ff_logits_constrain;
+                                * still 6, addition only: diverse beam search on the captured decode step, ff_group_beam_step) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -619,6 +620,31 @@ int ff_beam_step(const ff_beam_desc* d, const void* logits, const long long* cur
                  ff_stream_t stream);
 int ff_beam_gather(int n_tensors, void* const* tensors, int elem_size, int b, int nb, long long outer, long long len_max, long long inner,
                    const long long* beam_idx, const long long* n_pos, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Diverse beam search (Vijayakumar et al.) on the captured decode step (added under ABI 6): ff_group_beam_step is ff_beam_step with the nb
+ * beams of a sequence split into G = n_groups groups of gs = nb / G; the rows of group g are s * nb + g * gs + j, j < gs.  Inside a step the
+ * groups are handled in the order g = 0 .. G - 1, and a group pays diversity_penalty (lambda) for every token an earlier group chose in this
+ * step.  ff_beam_desc is unchanged: done and n_hyp hold b * G entries ([b][G]), hyp_score / hyp_len / hyp_row [b][nb] are read as
+ * [b][G][gs]; every other field and the workspace (ff_beam_workspace_bytes) are those of ff_beam_step.  The caller initialises score to 0 for
+ * beam 0 OF EVERY GROUP and to -inf for every other beam.  Capturable: no allocation, no host synchronisation, fixed order.  Rules:
+ *   A. the score of token v on row r of group g is  fl(fl(fl(x_v - lse_r) + score_r) - fl(lambda * c_g(v))),  each operation rounded once in
+ *      fp32; the row part is rules 1 - 3 above.  c_g(v) = the number of rows of groups 0 .. g - 1 of the same sequence whose NEXT beam of this
+ *      step is live (new score > -inf) and carries token v; dead rows and the rows of a done group hold pad and count nothing.  With c = 0
+ *      nothing is subtracted: no bit changes;
+ *   B. inside group g rules 4 - 7 apply with nb replaced by gs: the 2 gs best of the group's gs * vocab candidates, score descending, then row,
+ *      then column ascending; eos at rank < gs becomes a hypothesis of THAT group, at a later rank it is dropped; every group has its own sorted
+ *      list of gs hypotheses, its own n_hyp and done, its own early-stopping test; the rows of a done group get -inf, pad and the identity
+ *      parent.  The PENALISED score is the beam's running score and the hypothesis' score: penalties accumulate over the steps, as in the
+ *      published algorithm, so scores under groups are not pure log-probabilities;
+ *   F. rule 8 holds: whatever a row contains, every index written stays inside its table.
+ * n_groups = 1 is ff_beam_step: the same two launches, the same bits.  n_groups > 1 with lambda = 0 makes every group an independent
+ * ff_beam_step of gs beams on its rows.  (A row's 2 gs best penalised candidates lie among its 2 nb best unpenalised ones - the penalty lowers
+ * at most nb - gs columns -, so the row pass of ff_beam_step serves unchanged and the group walk is one launch of one wave per sequence.)
+ * FF_ERR_SHAPE: n_groups < 1, nb not a multiple of n_groups, a negative or non-finite diversity_penalty, and everything ff_beam_step rejects.
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_group_beam_step(const ff_beam_desc* d, int n_groups, float diversity_penalty, const void* logits, const long long* cur_len,
+                       void* workspace, size_t workspace_bytes, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Logits processors on the captured decode step (added under ABI 6): repetition penalty, no-repeat n-gram ban and minimum length, applied
