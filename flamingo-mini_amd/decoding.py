@@ -232,6 +232,14 @@ def check_group_args(num_beam_groups, diversity_penalty, num_beams, do_sample) -
     return Groups(G, float(lam)) if G > 1 else None
 
 
+def check_guidance_args(guidance_scale) -> Optional[float]:
+    """The check of generate()'s guidance_scale.  Returns the scale as a float, None for 1.0 (off: exactly the paths without it)."""
+    g = guidance_scale
+    if isinstance(g, bool) or not isinstance(g, (int, float)) or not 0 <= g < float("inf"):
+        raise ValueError(f"generate(): guidance_scale must be a finite number >= 0 (1 = off), got {g!r}")
+    return float(g) if g != 1 else None
+
+
 def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
     """sum(token_logprobs) / float32(len ** length_penalty) per row, len = L0 + the generated tokens up to and including eos: beam search's
     normalisation (BeamState.len_norm) applied to greedy and sampled sequences."""
@@ -245,7 +253,7 @@ def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
 
 
 def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_family, L0, max_length, ids_is_int64, procs_on, procs_given=(),
-          logprobs_on=False, constraints_on=False, vocab=0, table_entries=0):
+          logprobs_on=False, constraints_on=False, vocab=0, table_entries=0, guidance_on=False):
     """Which path a generate() call takes: "static" (a _DecodeSession) or "dynamic" (dynamic_decode / beam_search), from plain values only.
     `static_decode` is generate()'s argument (None, True, False), `model_default` the model's attribute, `procs_given` the processor
     arguments' names for the TypeError on CPU tensors.  Greedy decoding takes the static path by default on the GPU; sampling and beam search
@@ -253,7 +261,9 @@ def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_fam
     kernel (`logprobs_on`): a static session that records them needs GPU tensors, CPU tensors take the dynamic loop unless static_decode=True
     asks for what cannot be had.  Constraints (`constraints_on`, with the LM's `vocab` and `table_entries`, the largest table's size) are
     the same on CPU tensors - the dynamic loops restate them on the host - and take the static path under the processors' conditions
-    plus the kernel's vocabulary cap and the sessions' table cap."""
+    plus the kernel's vocabulary cap and the sessions' table cap.  Guidance (`guidance_on`) routes like the log-probabilities: its kernel has
+    no CPU form but its torch restatement has one, so CPU tensors take the dynamic loop unless static_decode=True asks for what cannot be
+    had; guided greedy decoding is static by default on the GPU, guided sampling and beam search on request."""
     def need_gpu():                     # what ffi.require_cuda raises for a CPU tensor
         if not is_cuda:
             F.ffi.require_cuda(torch.empty(0))
@@ -265,7 +275,7 @@ def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_fam
     if num_beams > 1 and do_sample:
         raise ValueError("beam search with sampling is not implemented")
     on_request = num_beams > 1 or do_sample                                   # static only when static_decode=True is passed
-    if (on_request or logprobs_on or constraints_on) and static_decode:
+    if (on_request or logprobs_on or constraints_on or guidance_on) and static_decode:
         need_gpu()
     if static_decode is None:
         static_decode = is_cuda and model_default and not on_request
@@ -332,6 +342,39 @@ def constrain_logits_torch(logits, seqs, gen_start, eos, trie=None, bad_words=No
             if 0 <= w[-1] < V and n >= m - 1 and tuple(h[n - m + 1:]) == w[:-1]:
                 ban[r, w[-1]] = True
     return logits.masked_fill(ban.to(logits.device), float("-inf"))
+
+
+def guided_logits_torch(cond, uncond, scale):
+    """The rules of ff_guided_logits (G1 - G3 of include/flamingo_fusion.h) in torch, for the dynamic loops and for CPU tensors: lu + scale *
+    (lc - lu) with lc / lu the log-softmax of `cond` / `uncond` (rows, V), in float32 - in float64 for float64 inputs.  An entry that is
+    -inf in either input is -inf for every scale; a row pair that holds NaN or +inf gives a NaN row.  `scale`: a number or a one-element
+    tensor.  Returns a new tensor."""
+    dt = torch.float64 if cond.dtype == torch.float64 else torch.float32
+    c, u = cond.to(dt), uncond.to(dt)
+    lc, lu = c.log_softmax(-1), u.log_softmax(-1)
+    g = scale.to(device=c.device, dtype=dt).reshape(()) if isinstance(scale, torch.Tensor) else torch.tensor(float(scale), dtype=dt, device=c.device)
+    out = torch.addcmul(lu, g, lc - lu)
+    out = out.masked_fill((c == float("-inf")) | (u == float("-inf")), float("-inf"))
+    bad = lambda x: (x.isnan() | (x == float("inf"))).any(-1, keepdim=True)
+    return out.masked_fill(bad(c) | bad(u), float("nan"))
+
+
+def guided_step(step, scale):
+    """`step` (FlamingoModel._decode_step) as the loops see a model under classifier-free guidance: every call runs the LM on [conditional
+    rows ; unconditional rows] - the same tokens, the second half without media (media_locations all zero) - and returns
+    guided_logits_torch of the two halves, (rows, V).  The prompt step doubles the rows (the visual features are repeated, never encoded
+    twice when generate() has encoded them); the caches it returns are twice the rows wide from then on."""
+    def guided(step_ids, ml, am, past, pixel_values, visual_features):
+        R = step_ids.shape[0]
+        two = lambda t: None if t is None else torch.cat([t, t], dim=0)
+        logits, past = step(two(step_ids), torch.cat([ml, torch.zeros_like(ml)], dim=0), two(am), past, two(pixel_values), two(visual_features))
+        return guided_logits_torch(logits[:R], logits[R:], scale), past
+    return guided
+
+
+def guided_reorder(reorder_cache):
+    """`reorder_cache` (FlamingoModel._reorder_cache) for caches of [conditional ; unconditional] rows: row r + R follows row r."""
+    return lambda past, beam_idx: reorder_cache(past, torch.cat([beam_idx, beam_idx + beam_idx.numel()]))
 
 
 def _dynamic_processor(processors, eos, L0, constraints=None):
@@ -433,27 +476,39 @@ class _DecodeSession:
     `constraints` (Constraints.caps(): capacities, not contents) puts functional.constrain_logits (one launch, csrc/ff_constrain.hip) behind
     it: the session owns table buffers of those capacities, every call's tables are copied into them before the prompt step together with
     `gen_start` (the prompt's length), outside any capture, and the captured step reads whatever they hold - a later call with other
-    candidates of the same capacity class replays the same graph.  A session without constraints allocates and issues none of this."""
+    candidates of the same capacity class replays the same graph.  A session without constraints allocates and issues none of this.
+    `guidance` makes it a classifier-free-guidance session: everything on the LM's side - the StaticCache, `am_buf`, `tt_step`, the
+    cross-attention K / V and the LM token buffer `lm_tok` - is 2 R rows wide, [conditional rows ; unconditional rows] (R = b * nb; row r
+    pairs with row r + R, the second half is the same ids with media_locations all zero), while everything the strategies own stays R rows.
+    _append combines the two halves of a step's logits into `guided` (R, V) float32 with functional.guided_logits (one launch,
+    csrc/ff_guidance.hip) and hands THAT to the processors, the constraints and the selection.  The scale is the device scalar `scale`,
+    written by run() outside any capture: a later call with another scale replays the same graph.  A session without guidance allocates
+    and issues none of this."""
 
     nb = 1                                 # rows per sequence
 
     def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None, logprobs=False,
-                 constraints=None, groups=None):
+                 constraints=None, groups=None, guidance=False):
         from transformers.cache_utils import StaticCache
         self._model_ref = weakref.ref(model)
         self.sampling, self.beams, self.processors, self.logprobs, self.constraints = sampling, beams, processors, logprobs, constraints
-        self.groups = groups
+        self.groups, self.guidance = groups, guidance
         self.n_seq = b
         b = b * self.nb
+        lm_b = 2 * b if guidance else b        # rows on the LM's side
         self.b, self.max_length, self.eos, self.graph_wanted = b, max_length, eos, graph
         self.fill = pad if pad is not None else 0
         self.lm_family = model.flamingo.lm_family
         self.cache = StaticCache(config=model.flamingo.lm.config, max_cache_len=max_length)
         self.ids_buf = torch.empty((b, max_length), dtype=ids_dtype, device=device)
-        self.am_buf = torch.empty((b, max_length), dtype=am_dtype, device=device)
+        self.am_buf = torch.empty((lm_b, max_length), dtype=am_dtype, device=device)
         self.pos = torch.zeros((1,), dtype=torch.long, device=device)          # position of `tok` (the token the next step consumes)
         self.tok = torch.zeros((b, 1), dtype=ids_dtype, device=device)
-        self.tt_step = torch.zeros((b, 1), dtype=torch.int32, device=device)
+        self.tt_step = torch.zeros((lm_b, 1), dtype=torch.int32, device=device)
+        if guidance:
+            self.lm_tok = torch.zeros((lm_b, 1), dtype=ids_dtype, device=device)
+            self.scale = torch.ones((1,), dtype=torch.float32, device=device)
+            self.guided = None                                                # (b, V) float32, allocated by the first prompt step
         if constraints is not None:
             self._alloc_constraints()
         self._alloc()
@@ -507,9 +562,14 @@ class _DecodeSession:
             self.bw_bufs[2].fill_(w.n)
 
     def _append(self, logits):
-        """The single place that receives a step's unprocessed logits: the processors, then the constraints, in place, against the first `pos`
-        tokens of every row of the strategy's history, then the strategy's selection."""
+        """The single place that receives a step's unprocessed logits: under guidance the two halves become the guided scores, then the
+        processors, then the constraints, in place, against the first `pos` tokens of every row of the strategy's history, then the
+        strategy's selection."""
         p = self.processors
+        if self.guidance:
+            if self.guided is None:                                           # (the prompt step: never inside a capture)
+                self.guided = torch.empty((self.b, logits.shape[-1]), dtype=torch.float32, device=logits.device)
+            logits = F.guided_logits(logits[:self.b], logits[self.b:], self.scale, out=self.guided)
         if p is not None:
             F.process_logits(logits, self._history(), self.pos, p.repetition_penalty, p.no_repeat_ngram_size, self.eos if self.min_on else None, self.min_len if self.min_on else None)
         if self.constraints is not None:
@@ -529,19 +589,29 @@ class _DecodeSession:
 
     def _step(self):
         self.am_buf.index_fill_(1, self.pos, 1)
-        o = self.model.flamingo(input_ids=self.tok, attention_mask=self.am_buf, use_cache=True, past_key_values=(self.xattn_past, self.cache),
+        if self.guidance:
+            self.lm_tok.view(2, self.b, 1).copy_(self.tok)                   # both halves consume the chosen token
+        o = self.model.flamingo(input_ids=self.lm_tok if self.guidance else self.tok, attention_mask=self.am_buf, use_cache=True, past_key_values=(self.xattn_past, self.cache),
                                 text_time=self.tt_step, **self._positions())
         self.pos.add_(1)
         self._append(o.logits[:, -1])
 
     @torch.no_grad()
-    def run(self, ids, ml, am, pixel_values, visual_features, generator=None, n_return=None, constraints=None):
+    def run(self, ids, ml, am, pixel_values, visual_features, generator=None, n_return=None, constraints=None, guidance_scale=None):
         L0, prompt_ids = ids.shape[1], ids
         ids, ml, am, pixel_values, visual_features = self._begin(ids, ml, am, pixel_values, visual_features, generator)
         if self.constraints is not None:
             self._begin_constraints(constraints, L0)
+        lm_ids = ids
+        if self.guidance:                                                     # [conditional ; unconditional]: the same ids, the second half without media
+            self.scale.fill_(guidance_scale)
+            if visual_features is None and pixel_values is not None:         # encoded once, repeated
+                visual_features, pixel_values = self.model.flamingo.encode_resample_visuals(pixel_values), None
+            lm_ids, ml, am = torch.cat([ids, ids]), torch.cat([ml, torch.zeros_like(ml)]), torch.cat([am, am])
+            if visual_features is not None:
+                visual_features = torch.cat([visual_features, visual_features])
         self.cache.reset()
-        out = self.model.flamingo(input_ids=ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=(None, self.cache),
+        out = self.model.flamingo(input_ids=lm_ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=(None, self.cache),
                                   pixel_values=pixel_values, visual_features=visual_features, **self._positions(L0))
         fresh = out.past_key_values[0]
         if self.xattn_past is None:
@@ -657,7 +727,10 @@ class _BeamSession(_DecodeSession):
     neither allocates no seq_buf.
     `groups` (a Groups) makes it DIVERSE beam search: the state block is built with n_groups, _select calls functional.group_beam_step with
     the penalty as a launch constant, and everything else - the gathers, seq_buf, the processors, the constraints - acts per row and is what
-    it was.  A session without groups calls beam_step."""
+    it was.  A session without groups calls beam_step.
+    Under `guidance` the LM cache is 2 b * nb rows and is gathered with a preallocated doubled index (beam_idx, then beam_idx + b * nb,
+    filled inside the step): ff_beam_gather maps within each run of nb rows, so the unconditional half follows its beams; seq_buf and the
+    state block stay b * nb rows."""
 
     def __init__(self, model, b, *args, beams, **kw):
         self.nb = beams.nb
@@ -671,6 +744,8 @@ class _BeamSession(_DecodeSession):
         self.lm_tensors = None                                                # keys / values of every StaticCache layer (allocated by the first prompt step)
         if self.processors is not None:
             self._alloc_min_len()
+        if self.guidance:
+            self.lm_beam_idx = torch.zeros((2 * self.b,), dtype=torch.long, device=dev)      # beam_idx, then beam_idx + R: the unconditional half follows
         if self.processors is not None or self.constraints is not None:
             self.seq_buf = torch.full((self.b, self.max_length), self.fill, dtype=torch.long, device=dev)
 
@@ -699,7 +774,10 @@ class _BeamSession(_DecodeSession):
             nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
         else:
             nxt, beam_idx = F.group_beam_step(logits, self.state, self.cur_len, self.groups.diversity_penalty)
-        F.beam_gather(self.lm_tensors, beam_idx, self.pos, self.nb)           # positions < pos are live: the cache rows follow their beams
+        if self.guidance:
+            self.lm_beam_idx[:self.b].copy_(beam_idx)
+            torch.add(beam_idx, self.b, out=self.lm_beam_idx[self.b:])
+        F.beam_gather(self.lm_tensors, self.lm_beam_idx if self.guidance else beam_idx, self.pos, self.nb)           # positions < pos are live: the cache rows follow their beams
         if hasattr(self, "seq_buf"):                                          # ... and so do the histories: an id is two 4-byte elements
             F.beam_gather([self.seq_buf.view(torch.int32).view(self.b, 1, self.max_length, 2)], beam_idx, self.pos, self.nb)
             self.seq_buf.index_copy_(1, self.pos, nxt[:, None])
@@ -716,7 +794,7 @@ class _BeamSession(_DecodeSession):
 
 
 def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, beams=None, processors=None,
-                   logprobs=False, n_return=None, constraints=None, groups=None):
+                   logprobs=False, n_return=None, constraints=None, groups=None, guidance=None):
     """Greedy, sampled (`sampling`) or beam-search (`beams`) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches
     and buffers plus, on the GPU, the captured HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, device,
     eos, pad, graph, sampling, beams, processors) and reused by later calls, so only the first caption batch of a shape pays for the
@@ -727,7 +805,9 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
     entries per sequence (_beam_finalize); it changes nothing in the session.  `constraints` (a Constraints) selects a session that decodes
     under a candidate trie and / or banned words: its key ends with Constraints.caps() - the tables' capacities, not their contents.
     `groups` (a Groups, with `beams`) selects a diverse-beam-search session: its key ends with the Groups - the penalty is a launch constant of
-    the captured step.  A call without groups builds the key it always built."""
+    the captured step.  A call without groups builds the key it always built.
+    `guidance` (the scale, a float) selects a classifier-free-guidance session: its key ends with "guidance", NOT with the scale, which is
+    a device scalar the captured step reads - a sweep over scales replays one graph.  A call without it builds the key it always built."""
     b = ids.shape[0]
     graph = ids.is_cuda and not model.training and model.decode_graph
     sessions = _DECODE_SESSIONS.setdefault(model, {})
@@ -738,6 +818,8 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
         key += (constraints.caps(),)
     if groups is not None:
         key += (groups,)
+    if guidance is not None:
+        key += ("guidance",)
     sess = sessions.get(key)
     if sess is not None and sess.stale():
         sessions.pop(key)
@@ -747,8 +829,10 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
             sessions.pop(next(iter(sessions)))
         cls = _TokenSession if beams is None else _BeamSession
         sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors, logprobs=logprobs,
-                                   **({"constraints": constraints.caps()} if constraints is not None else {}), **({"groups": groups} if groups is not None else {}))
-    return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator, n_return=n_return, **({"constraints": constraints} if constraints is not None else {}))
+                                   **({"constraints": constraints.caps()} if constraints is not None else {}), **({"groups": groups} if groups is not None else {}),
+                                   **({"guidance": True} if guidance is not None else {}))
+    return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator, n_return=n_return, **({"constraints": constraints} if constraints is not None else {}),
+                    **({"guidance_scale": guidance} if guidance is not None else {}))
 
 
 # ---- the dynamic path: growing caches, one forward per step (the only path on CPU tensors, and what the sessions are tested against) ----

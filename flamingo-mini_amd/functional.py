@@ -1064,6 +1064,32 @@ def token_logprobs(logits: torch.Tensor, token: torch.Tensor, skip: Optional[tor
     return out
 
 
+def guided_logits(cond: torch.Tensor, uncond: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Classifier-free guidance, lu + scale * (lc - lu) with lc / lu = log_softmax of `cond` / `uncond` (rows, V), float32 / bfloat16 on the
+    GPU, in float32: ff_guided_logits, one launch that reads each row twice and writes neither; the exact rules are in
+    include/flamingo_fusion.h.  Both inputs have one shape and one dtype; only the last dimension has to be contiguous (logits[:b],
+    logits[b:], x3d[:, -1] are read in place through their row strides).  `scale`: ONE float32 on the device, read by the launch - a
+    captured call serves every value written there.  With `out` (float32, (rows, V), last dimension contiguous) nothing is allocated, so
+    the call can be captured into a graph."""
+    ffi.require_cuda(cond, uncond, scale, out)
+    for name, t in (("cond", cond), ("uncond", uncond)):
+        if t.ndim != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"guided_logits: {name} must be (rows, V) with a contiguous last dimension, got shape {tuple(t.shape)} strides {t.stride()}")
+    if cond.shape != uncond.shape or cond.dtype != uncond.dtype:
+        raise ValueError(f"guided_logits: cond and uncond must have one shape and one dtype, got {tuple(cond.shape)} {cond.dtype} and {tuple(uncond.shape)} {uncond.dtype}")
+    rows, V = cond.shape
+    if scale.dtype != torch.float32 or scale.numel() != 1:
+        raise ValueError(f"guided_logits: scale must be one float32 value on the device, got {tuple(scale.shape)} {scale.dtype}")
+    if out is None:
+        out = _new((rows, V), torch.float32, cond.device)
+    if out.dtype != torch.float32 or out.shape != (rows, V) or (V > 1 and out.stride(1) != 1):
+        raise ValueError(f"guided_logits: out must be ({rows}, {V}) float32 with a contiguous last dimension, got {tuple(out.shape)} {out.dtype} strides {out.stride()}")
+    ld = lambda t: t.stride(0) if rows > 1 else V
+    ffi.check(ffi.lib().ff_guided_logits(ffi.dtype_code(cond.dtype), rows, V, ld(cond), cond.data_ptr(), ld(uncond), uncond.data_ptr(), scale.data_ptr(),
+                                         out.data_ptr(), ld(out), ffi.stream_handle(cond.device)), "ff_guided_logits")
+    return out
+
+
 class BeamState:
     """The device state block of ff_beam_step for b sequences x nb beams and histories of max_len positions (layout and rules:
     include/flamingo_fusion.h).  All fields are views of ONE byte buffer, so `to_host()` is one device-to-host copy.  `storage` (uint8,

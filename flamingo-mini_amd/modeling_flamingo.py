@@ -441,7 +441,7 @@ class FlamingoModel(PreTrainedModel):
                  input_ids=None, static_decode: Optional[bool] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_length: int = 0, min_new_tokens: int = 0, return_dict_in_generate: bool = False, output_logprobs: bool = False,
                  num_return_sequences: int = 1, candidate_ids=None, bad_words_ids=None, num_beam_groups: int = 1,
-                 diversity_penalty: float = 0.0, **unsupported):
+                 diversity_penalty: float = 0.0, guidance_scale: float = 1.0, **unsupported):
         """Text generation with the cached cross-attention path: the first step runs CLIP + resampler and fills the xattn K/V and LM caches,
         every later step feeds one token (reference: HF `generate` through prepare_inputs_for_generation / _reorder_cache, :464-548).
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
@@ -495,11 +495,26 @@ class FlamingoModel(PreTrainedModel):
         penalty is soft, so two groups may still return the same sequence.  G = 1 is plain beam search, call for call; G > 1 with penalty 0
         runs G independent searches of num_beams / G beams.  Routing is that of beam search: the static session (functional.group_beam_step
         inside the replayed step: the row pass of beam_step and one group walk, no host round trip) only with static_decode=True, otherwise
-        the dynamic loop, which also runs on CPU tensors."""
+        the dynamic loop, which also runs on CPU tensors.
+        Classifier-free guidance (transformers' `guidance_scale`; Kornblith et al., "Guiding image captioning models toward more specific
+        captions") says how strongly the media count: every sequence is decoded twice, with its media and - the same ids, media_locations all
+        zero, which leaves the frozen LM with the gated feed-forward: the model's own text prior - without, and every step selects from
+            scores = log p(. | text) + guidance_scale * (log p(. | media, text) - log p(. | text)).
+        1.0 is off (exactly the paths without it); any other finite value >= 0 turns it on: > 1 extrapolates away from the prior (captions say
+        what is in THIS image), values in (0, 1) interpolate towards it, 0 is the prior alone.  Negative, non-finite and non-numeric values
+        raise ValueError.  Guidance comes FIRST, as in transformers: the logits processors, the constraints, sampling, beam search, groups and
+        the log-probabilities all act on the guided scores, so token_logprobs and sequences_scores are the log-softmax of the GUIDED scores
+        - renormalised, not model probabilities.  num_return_sequences for sampling repeats the rows before they are doubled.  The LM runs
+        on [conditional rows ; unconditional rows] (2 x the rows; the visuals are encoded once and repeated).  On the static path
+        the combination is one launch inside the replayed step (functional.guided_logits) whose scale is a device scalar: calls with other
+        scales reuse the session and its graph.  Routing: guided greedy decoding takes the static path by default on the GPU, guided sampling
+        and beam search with static_decode=True; CPU tensors take the dynamic loops (decoding.guided_logits_torch), static_decode=True with
+        CPU tensors raises what ffi.require_cuda raises.  A negative prompt (other ids for the unconditional branch) is not offered."""
         procs = D.check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos_token_id)
         n_ret = D.check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample)
         groups = D.check_group_args(num_beam_groups, diversity_penalty, num_beams, do_sample)
         gkw = {} if groups is None else {"groups": groups}                   # nothing is passed on without groups: the calls are what they were
+        guidance = D.check_guidance_args(guidance_scale)
         ids = inputs if inputs is not None else input_ids
         assert ids is not None and media_locations is not None, "generate() needs input ids and media_locations"
         cons = D.check_constraint_args(candidate_ids, bad_words_ids, self.flamingo.lm.config.vocab_size, eos_token_id, procs, ids.shape[1], max_length)
@@ -510,13 +525,21 @@ class FlamingoModel(PreTrainedModel):
         pad = pad_token_id if pad_token_id is not None else eos_token_id
         path = D.route(is_cuda=ids.is_cuda, num_beams=num_beams, do_sample=do_sample, static_decode=static_decode, model_default=self.static_decode, lm_family=self.flamingo.lm_family,
                        L0=ids.shape[1], max_length=max_length, ids_is_int64=ids.dtype == torch.long, procs_on=procs is not None, procs_given=procs.given() if procs is not None else (),
-                       logprobs_on=bool(output_logprobs), **rkw)
+                       logprobs_on=bool(output_logprobs), **rkw, **({} if guidance is None else {"guidance_on": True}))
         if n_ret > 1 and num_beams <= 1:                                     # sampling: every sequence n times, its visuals encoded once
             if visual_features is None and pixel_values is not None:
                 visual_features, pixel_values = self.flamingo.encode_resample_visuals(pixel_values), None
             ids, ml, am = _repeat_leading(ids, n_ret), _repeat_leading(ml, n_ret), _repeat_leading(am, n_ret)
             if visual_features is not None:
                 visual_features = _repeat_leading(visual_features, n_ret)
+        step, reorder = self._decode_step, self._reorder_cache
+        if guidance is not None:
+            if visual_features is None and pixel_values is not None:         # encoded once; both halves of the LM batch carry the same features
+                visual_features, pixel_values = self.flamingo.encode_resample_visuals(pixel_values), None
+            if path == "static":
+                gkw = dict(gkw, guidance=guidance)
+            else:                                                            # the loops see a model whose logits are the guided scores
+                step, reorder = D.guided_step(step, guidance), D.guided_reorder(reorder)
         n_beams_out = n_ret if num_beams > 1 and (return_dict_in_generate or n_ret > 1) else None      # None: the search's single result, as ever
         if path == "static":
             res = D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, generator=generator, processors=procs,
@@ -525,12 +548,12 @@ class FlamingoModel(PreTrainedModel):
                                    logprobs=bool(output_logprobs), n_return=n_beams_out, **ckw, **gkw)
         elif num_beams > 1:
             res = self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty, processors=procs,
-                                    n_return=n_beams_out, **ckw, **gkw)
+                                    n_return=n_beams_out, **ckw, **gkw, **({} if guidance is None else {"step": step, "reorder_cache": reorder}))
         else:
             # the log-softmax is taken in float32, the dtype of the logits _decode_step hands the loop; a model that computes in float64 keeps
             # its precision (a float32 log-softmax would throw away what a float64 evaluation on the host is run for)
             lp_dtype = (torch.float64 if next(self.parameters()).dtype == torch.float64 else torch.float32) if output_logprobs else None
-            res = D.dynamic_decode(self._decode_step, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
+            res = D.dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
                                    sampling=D.Sampling(temperature, top_k, top_p) if do_sample else None, generator=generator, processors=procs,
                                    logprob_dtype=lp_dtype, **ckw)
         if not return_dict_in_generate:
@@ -550,10 +573,10 @@ class FlamingoModel(PreTrainedModel):
         D._DECODE_SESSIONS.pop(self, None)
 
     def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None, n_return=None,
-                     **constraints):
+                     step=None, reorder_cache=None, **constraints):
         """The dynamic beam search (decoding.beam_search) over this model's _decode_step / _reorder_cache; `constraints=` and `groups=` travel
-        as keywords and only when given."""
-        return D.beam_search(self._decode_step, self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors,
+        as keywords and only when given, and so do `step=` / `reorder_cache=`, the guided wrappers of the two (decoding.guided_step)."""
+        return D.beam_search(step or self._decode_step, reorder_cache or self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors,
                              n_return=n_return, **constraints)
 
     @torch.no_grad()
@@ -561,9 +584,11 @@ class FlamingoModel(PreTrainedModel):
                           num_beams: int = 1, device=None, return_scores: bool = False, candidates=None, bad_words=None, **kwargs):
         """Caption a batch of images; the prompt is replicated for every image (reference :550-605).  `kwargs` are generation
         arguments (do_sample, temperature, top_k, top_p, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length,
-        min_new_tokens, num_return_sequences, output_logprobs, return_dict_in_generate, num_beam_groups, diversity_penalty, ...) and go to
+        min_new_tokens, num_return_sequences, output_logprobs, return_dict_in_generate, num_beam_groups, diversity_penalty, guidance_scale,
+        ...) and go to
         generate(), which rejects unknown ones.  num_beams=4, num_beam_groups=4, diversity_penalty=1.0, num_return_sequences=4,
         return_scores=True gives the 4 best DIFFERENT captions of diverse beam search with the (penalised) scores they were ranked by.
+        guidance_scale=1.5 weighs the image against the language model's prior (classifier-free guidance, see generate()).
         `return_scores=True` returns (captions, scores), the scores floats from GenerateOutput.sequences_scores (beam search: the score the
         search ranked by; greedy and sampling: the length-normalised sum of the token log-probabilities).  With num_return_sequences = n > 1
         the captions (and the scores) are a list of one list of n per image.

@@ -57,7 +57,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, addition only: exponential moving average of the weights, ff_ema_update;
                                 * still 6, addition only: log-probability of the chosen token on the captured decode step, ff_token_logprob;
                                 * still 6, addition only: constrained decoding on the captured decode step (candidate trie, bad words), ff_logits_constrain;
-                                * still 6, addition only: diverse beam search on the captured decode step, ff_group_beam_step) */
+                                * still 6, addition only: diverse beam search on the captured decode step, ff_group_beam_step;
+                                * still 6, addition only: classifier-free guidance on the captured decode step, ff_guided_logits) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -733,6 +734,28 @@ int ff_logits_constrain(int dtype, int rows, int vocab, long long ld, void* logi
                         int node_cap, int edge_cap,
                         const int* bw_off, const int* bw_tok, const int* n_bw, int bw_cap, int bw_tok_cap,
                         ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Classifier-free guidance on the captured decode step (added under ABI 6): the scores a step selects from, out of the logits of the same
+ * sequence decoded WITH its media (cond) and WITHOUT (uncond):  out = lu + g (lc - lu),  lc / lu the log-softmax of the two rows
+ * (transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor).  One launch in front of ff_logits_process, ff_logits_constrain and the
+ * selection; no atomics, no allocation, no host synchronisation, capturable; equal inputs give equal bits, eager or replayed.
+ * cond, uncond: `rows` rows of `vocab` elements of `dtype` (FF_DTYPE_F32 / FF_DTYPE_BF16), row r at element r * ld_cond resp. r * ld_uncond,
+ * every ld >= vocab, element alignment only and independent of each other (the two halves of one (2 rows, vocab) buffer, logits[:, -1] of a
+ * (batch, seq, vocab) tensor work in place).  scale: ONE fp32 in DEVICE memory, g, read by the launch: a captured launch serves every g.
+ * out: rows of `vocab` fp32, row r at element r * ld_out, element alignment only; it must not overlap the inputs.
+ *   G1.  lse_c, lse_u: each row's logsumexp in fp32, the max-shifted (max, sum) pairs from (-FLT_MAX, 0) of ff_shifted_ce_fwd /
+ *        ff_token_logprob with their wave and block combine, lse = M + logf(S) (each row walked on its own 16-byte grid).
+ *   G2.  lc = x_c - lse_c, lu = x_u - lse_u, out = fmaf(g, lc - lu, lu).  g = 1: the conditional log-softmax; g = 0: the unconditional one.
+ *   G3.  x_c == -inf or x_u == -inf: out = -inf, for every g (never the +inf or NaN of (1 - g) * (-inf)).  A row pair in which either row
+ *        holds NaN or +inf: the whole out row is NaN (this rule goes first).  A row of nothing but -inf: all -inf.
+ *   G4.  Neither input is written; nothing outside out[r, 0 .. vocab) is written.
+ * g itself is not checked on the device (NaN or infinite g: unspecified values, in bounds).
+ * FF_ERR_SHAPE: null cond, uncond, scale or out; rows <= 0, vocab <= 0, an ld < vocab.  FF_ERR_UNSUPPORTED: another dtype.  Both before any
+ * launch.
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_guided_logits(int dtype, int rows, int vocab, long long ld_cond, const void* cond, long long ld_uncond, const void* uncond,
+                     const float* scale, float* out, long long ld_out, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * QuickGELU of the CLIP vision tower, y = x * sigmoid(1.702 x) (transformers.activations.QuickGELUActivation, selected by
