@@ -18,6 +18,8 @@ from .graphs import _prepared_capture_stream
 Sampling = NamedTuple("Sampling", [("temperature", float), ("top_k", int), ("top_p", float)])
 Beams = NamedTuple("Beams", [("nb", int), ("early_stopping", bool), ("length_penalty", float)])
 Groups = NamedTuple("Groups", [("n", int), ("diversity_penalty", float)])      # diverse beam search: beside Beams, which keeps its three fields
+# the truncation samplers: beside Sampling, which keeps its three fields
+Truncation = NamedTuple("Truncation", [("min_p", float), ("typical_p", float), ("epsilon_cutoff", float), ("eta_cutoff", float)])
 
 
 class Processors(NamedTuple):
@@ -240,6 +242,27 @@ def check_guidance_args(guidance_scale) -> Optional[float]:
     return float(g) if g != 1 else None
 
 
+def check_truncation_args(min_p, typical_p, epsilon_cutoff, eta_cutoff, do_sample, num_beams) -> Optional[Truncation]:
+    """The checks of generate()'s truncation samplers.  Returns the Truncation, None when all four are off (exactly the paths without them)."""
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float))
+    if not (num(min_p) and 0 <= min_p <= 1):
+        raise ValueError(f"generate(): min_p must be a number in [0, 1] (0 = off), got {min_p!r}")
+    if not (num(typical_p) and 0 < typical_p <= 1):
+        raise ValueError(f"generate(): typical_p must be a number in (0, 1] (1 = off), got {typical_p!r}")
+    for name, v in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
+        if not (num(v) and 0 <= v < 1):
+            raise ValueError(f"generate(): {name} must be a number in [0, 1) (0 = off), got {v!r}")
+    t = Truncation(float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff))
+    if t == (0.0, 1.0, 0.0, 0.0):
+        return None
+    given = [n for n, v, off in zip(t._fields, t, (0.0, 1.0, 0.0, 0.0)) if v != off]
+    if num_beams > 1:
+        raise ValueError(f"generate(): {given} are not offered with beam search (num_beams > 1)")
+    if not do_sample:
+        raise ValueError(f"generate(): {given} need do_sample=True (they truncate the distribution a token is sampled from)")
+    return t
+
+
 def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
     """sum(token_logprobs) / float32(len ** length_penalty) per row, len = L0 + the generated tokens up to and including eos: beam search's
     normalisation (BeamState.len_norm) applied to greedy and sampled sequences."""
@@ -297,6 +320,36 @@ def filter_logits(logits, temperature, top_k, top_p):
         cum = srt.softmax(-1).cumsum(-1)
         drop = cum - srt.softmax(-1) >= top_p               # keep the smallest prefix whose mass reaches top_p
         logits = logits.masked_fill(drop.scatter(-1, idx, drop), float("-inf"))
+    return logits
+
+
+def truncate_logits_torch(logits, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+    """Rules 3 - 6 of ff_sample_token_truncated (include/flamingo_fusion.h) in torch, on tensors of any device and in their own dtype: min_p,
+    typical_p, epsilon_cutoff and eta_cutoff as transformers' MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper
+    (min_tokens_to_keep = 1) apply them, in that order.  `logits` (rows, V) are what filter_logits returns: divided by the temperature, -inf
+    where top-k / top-p dropped a column.  Every stage drops by value - equal values stay or go together - and keeps the columns of the
+    largest value it was given.  Returns new logits, dropped columns -inf."""
+    ninf = float("-inf")
+    top = lambda x: x.amax(-1, keepdim=True)
+    entropy = lambda lp: -torch.where(lp > ninf, lp.exp() * lp, torch.zeros_like(lp)).sum(-1, keepdim=True)
+    if min_p > 0:
+        logits = logits.masked_fill((logits - top(logits)).exp() < min_p, ninf)
+    if typical_p < 1:
+        lp = logits.log_softmax(-1)
+        d, idx = (-lp - entropy(lp)).abs().sort(-1)                        # ascending; the -inf columns have d = inf and come last
+        r = lp.exp().gather(-1, idx)
+        before = r.cumsum(-1) - r                                          # the mass sorted in front of a column ...
+        first = torch.ones_like(d, dtype=torch.bool)
+        first[..., 1:] = d[..., 1:] != d[..., :-1]
+        before = torch.where(first, before, torch.zeros_like(before)).cummax(-1).values      # ... of STRICTLY smaller d: that of its run's first
+        drop = before >= typical_p
+        logits = logits.masked_fill(drop.scatter(-1, idx, drop), ninf)
+    if epsilon_cutoff > 0:
+        logits = logits.masked_fill((logits.softmax(-1) < epsilon_cutoff) & (logits < top(logits)), ninf)
+    if eta_cutoff > 0:
+        lp = logits.log_softmax(-1)
+        eta = torch.clamp(eta_cutoff ** 0.5 * (-entropy(lp)).exp(), max=eta_cutoff)
+        logits = logits.masked_fill((lp.exp() < eta) & (logits < top(logits)), ninf)
     return logits
 
 
@@ -488,11 +541,11 @@ class _DecodeSession:
     nb = 1                                 # rows per sequence
 
     def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None, logprobs=False,
-                 constraints=None, groups=None, guidance=False):
+                 constraints=None, groups=None, guidance=False, truncation=None):
         from transformers.cache_utils import StaticCache
         self._model_ref = weakref.ref(model)
         self.sampling, self.beams, self.processors, self.logprobs, self.constraints = sampling, beams, processors, logprobs, constraints
-        self.groups, self.guidance = groups, guidance
+        self.groups, self.guidance, self.truncation = groups, guidance, truncation
         self.n_seq = b
         b = b * self.nb
         lm_b = 2 * b if guidance else b        # rows on the LM's side
@@ -661,6 +714,9 @@ class _TokenSession(_DecodeSession):
     prompt step, outside any capture, into `u_all` (max_length, b): row `pos` serves the token written at position `pos` and the captured
     step picks it with a device-side index_select on `pos`, so the graph holds no random-number generation and eager and replayed steps
     consume identical numbers.  The processors read `ids_buf`, which already is the sequence.
+    `truncation` (a Truncation, with `sampling`) hands min_p / typical_p / epsilon_cutoff / eta_cutoff to the same call, which then is the
+    one launch of csrc/ff_truncate.hip; the values are launch constants of the captured step.  A session without it calls sample_tokens as
+    it always did.
     `logprobs` makes _select record the chosen token's log-probability (functional.token_logprobs on the processed logits, one launch inside
     the captured step) into column `pos` of `lp_buf` (b, max_length) float32; a session without it allocates neither buffer and never
     calls the function."""
@@ -695,8 +751,10 @@ class _TokenSession(_DecodeSession):
     def _select(self, logits):             # choose, apply the eos bookkeeping, append at `pos`
         if self.sampling is None:
             nxt = logits.float().argmax(-1)
-        else:
+        elif self.truncation is None:
             nxt = F.sample_tokens(logits, self.u_all.index_select(0, self.pos).view(-1), *self.sampling, out=self.nxt)
+        else:
+            nxt = F.sample_tokens(logits, self.u_all.index_select(0, self.pos).view(-1), *self.sampling, out=self.nxt, **self.truncation._asdict())
         if self.logprobs:                  # the chosen token's log-softmax, 0 for a row that had finished (one launch, csrc/ff_logprob.hip);
             # `finished` still is what it was before this step: _pad_finished below updates it after the launch, in stream order
             F.token_logprobs(logits, nxt, skip=self.finished, out=self.lp_step)
@@ -794,7 +852,7 @@ class _BeamSession(_DecodeSession):
 
 
 def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, beams=None, processors=None,
-                   logprobs=False, n_return=None, constraints=None, groups=None, guidance=None):
+                   logprobs=False, n_return=None, constraints=None, groups=None, guidance=None, truncation=None):
     """Greedy, sampled (`sampling`) or beam-search (`beams`) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches
     and buffers plus, on the GPU, the captured HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, device,
     eos, pad, graph, sampling, beams, processors) and reused by later calls, so only the first caption batch of a shape pays for the
@@ -807,7 +865,10 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
     `groups` (a Groups, with `beams`) selects a diverse-beam-search session: its key ends with the Groups - the penalty is a launch constant of
     the captured step.  A call without groups builds the key it always built.
     `guidance` (the scale, a float) selects a classifier-free-guidance session: its key ends with "guidance", NOT with the scale, which is
-    a device scalar the captured step reads - a sweep over scales replays one graph.  A call without it builds the key it always built."""
+    a device scalar the captured step reads - a sweep over scales replays one graph.  A call without it builds the key it always built.
+    `truncation` (a Truncation, with `sampling`) selects a session that samples under min_p / typical_p / epsilon_cutoff / eta_cutoff: its
+    key ends with the Truncation - the values are launch constants of the captured step, like the Groups.  A call without it builds the key it
+    always built."""
     b = ids.shape[0]
     graph = ids.is_cuda and not model.training and model.decode_graph
     sessions = _DECODE_SESSIONS.setdefault(model, {})
@@ -820,6 +881,8 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
         key += (groups,)
     if guidance is not None:
         key += ("guidance",)
+    if truncation is not None:
+        key += (truncation,)
     sess = sessions.get(key)
     if sess is not None and sess.stale():
         sessions.pop(key)
@@ -830,15 +893,16 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
         cls = _TokenSession if beams is None else _BeamSession
         sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors, logprobs=logprobs,
                                    **({"constraints": constraints.caps()} if constraints is not None else {}), **({"groups": groups} if groups is not None else {}),
-                                   **({"guidance": True} if guidance is not None else {}))
+                                   **({"guidance": True} if guidance is not None else {}), **({"truncation": truncation} if truncation is not None else {}))
     return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator, n_return=n_return, **({"constraints": constraints} if constraints is not None else {}),
                     **({"guidance_scale": guidance} if guidance is not None else {}))
 
 
 # ---- the dynamic path: growing caches, one forward per step (the only path on CPU tensors, and what the sessions are tested against) ----
 def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, processors=None,
-                   logprob_dtype=None, constraints=None):
+                   logprob_dtype=None, constraints=None, truncation=None):
     """Greedy or, with `sampling`, multinomial decoding over the cached decode path; `step` is FlamingoModel._decode_step.
+    With `truncation` (a Truncation) the filtered logits also pass truncate_logits_torch before the draw; without it nothing changes.
     With `logprob_dtype` (torch.float32, or torch.float64 for a model that computes in float64) it returns (ids, token_logprobs): the
     log-softmax of the processed logits at the chosen token, taken in that dtype, 0 for a row that had finished before the step."""
     finished = torch.zeros(ids.shape[0], dtype=torch.bool, device=ids.device)
@@ -848,7 +912,9 @@ def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length,
     while ids.shape[1] < max_length:
         logits, past = step(step_ids, ml, am, past, pixel_values, visual_features)
         logits = process(logits, ids)
-        if sampling is not None:
+        if sampling is not None and truncation is not None:
+            nxt = torch.multinomial(truncate_logits_torch(filter_logits(logits, *sampling), *truncation).softmax(-1), 1, generator=generator)[:, 0]
+        elif sampling is not None:
             nxt = torch.multinomial(filter_logits(logits, *sampling).softmax(-1), 1, generator=generator)[:, 0]
         else:
             nxt = logits.argmax(-1)

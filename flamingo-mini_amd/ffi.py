@@ -169,6 +169,7 @@ _SIGNATURES = {
     "ff_stochastic_round_bf16": (_I, [_P, _P, C.c_longlong, C.c_longlong, C.c_uint, C.c_uint, _I, _P]),
     "ff_ema_update": (_I, [_I, _I, _P, _P, _P, _P, C.c_float, _I, _I, _I, _P, _P, _P]),
     "ff_sample_token": (_I, [_I, _I, _I, C.c_longlong, _P, C.c_float, _I, C.c_float, _P, _P, _P]),
+    "ff_sample_token_truncated": (_I, [_I, _I, _I, C.c_longlong, _P, C.c_float, _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     "ff_beam_workspace_bytes": (_SZ, [_I, _I]),
     "ff_beam_step": (_I, [C.POINTER(BeamDesc), _P, _P, _P, _SZ, _P]),
     "ff_beam_gather": (_I, [_I, _P, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P, _P]),

@@ -949,11 +949,15 @@ def shifted_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, reduction:
 
 
 def sample_tokens(logits: torch.Tensor, u: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, *, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0,
+                  eta_cutoff: float = 0.0) -> torch.Tensor:
     """One token id per row of `logits` (rows, V), float32 / bfloat16 on the GPU, drawn with the row's uniform number u[r] in [0, 1) under
     temperature, top-k (0 = off; ties with the k-th value are kept) and nucleus filtering (top_p = 1: off): ff_sample_token, one launch, the
     exact rules are in include/flamingo_fusion.h.  Only the last dimension has to be contiguous: a row view such as logits3d[:, -1] is read
-    in place through its row stride.  With `out` (int64, rows, contiguous) nothing is allocated, so the call can be captured into a graph."""
+    in place through its row stride.  With `out` (int64, rows, contiguous) nothing is allocated, so the call can be captured into a graph.
+    `min_p` (0 = off), `typical_p` (1 = off), `epsilon_cutoff` and `eta_cutoff` (0 = off) are transformers' truncation samplers, applied in
+    that order after top-k and top-p: with any of them on the call is ff_sample_token_truncated (csrc/ff_truncate.hip), still one launch;
+    with all four off it is ff_sample_token, exactly as before they existed.  All are launch constants."""
     ffi.require_cuda(logits, u, out)
     if logits.ndim != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
         raise ValueError(f"sample_tokens: logits must be (rows, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
@@ -965,8 +969,13 @@ def sample_tokens(logits: torch.Tensor, u: torch.Tensor, temperature: float = 1.
     elif out.dtype != torch.long or out.shape != (rows,) or not out.is_contiguous():
         raise ValueError(f"sample_tokens: out must be {rows} contiguous int64 values, got {tuple(out.shape)} {out.dtype}")
     ld = logits.stride(0) if rows > 1 else V
-    ffi.check(ffi.lib().ff_sample_token(ffi.dtype_code(logits.dtype), rows, V, ld, logits.data_ptr(), float(temperature), int(top_k), float(top_p),
-                                        u.data_ptr(), out.data_ptr(), ffi.stream_handle(logits.device)), "ff_sample_token")
+    if min_p == 0 and typical_p == 1 and epsilon_cutoff == 0 and eta_cutoff == 0:
+        ffi.check(ffi.lib().ff_sample_token(ffi.dtype_code(logits.dtype), rows, V, ld, logits.data_ptr(), float(temperature), int(top_k), float(top_p),
+                                            u.data_ptr(), out.data_ptr(), ffi.stream_handle(logits.device)), "ff_sample_token")
+    else:
+        ffi.check(ffi.lib().ff_sample_token_truncated(ffi.dtype_code(logits.dtype), rows, V, ld, logits.data_ptr(), float(temperature), int(top_k), float(top_p),
+                                                      float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff),
+                                                      u.data_ptr(), out.data_ptr(), ffi.stream_handle(logits.device)), "ff_sample_token_truncated")
     return out
 
 

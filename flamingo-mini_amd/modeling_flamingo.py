@@ -441,7 +441,8 @@ class FlamingoModel(PreTrainedModel):
                  input_ids=None, static_decode: Optional[bool] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_length: int = 0, min_new_tokens: int = 0, return_dict_in_generate: bool = False, output_logprobs: bool = False,
                  num_return_sequences: int = 1, candidate_ids=None, bad_words_ids=None, num_beam_groups: int = 1,
-                 diversity_penalty: float = 0.0, guidance_scale: float = 1.0, **unsupported):
+                 diversity_penalty: float = 0.0, guidance_scale: float = 1.0, min_p: float = 0.0, typical_p: float = 1.0,
+                 epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0, **unsupported):
         """Text generation with the cached cross-attention path: the first step runs CLIP + resampler and fills the xattn K/V and LM caches,
         every later step feeds one token (reference: HF `generate` through prepare_inputs_for_generation / _reorder_cache, :464-548).
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
@@ -509,12 +510,25 @@ class FlamingoModel(PreTrainedModel):
         the combination is one launch inside the replayed step (functional.guided_logits) whose scale is a device scalar: calls with other
         scales reuse the session and its graph.  Routing: guided greedy decoding takes the static path by default on the GPU, guided sampling
         and beam search with static_decode=True; CPU tensors take the dynamic loops (decoding.guided_logits_torch), static_decode=True with
-        CPU tensors raises what ffi.require_cuda raises.  A negative prompt (other ids for the unconditional branch) is not offered."""
+        CPU tensors raises what ffi.require_cuda raises.  A negative prompt (other ids for the unconditional branch) is not offered.
+        Truncation samplers (with do_sample=True, not with beam search; ValueError otherwise and for values out of range), transformers'
+        warpers with min_tokens_to_keep = 1, applied in transformers' order after temperature, top_k and top_p: `min_p` in [0, 1] (0 = off)
+        keeps the tokens whose probability is at least min_p times the largest; `typical_p` in (0, 1] (1 = off) keeps the tokens whose
+        information content is nearest the distribution's entropy until they hold typical_p of the mass (locally typical sampling);
+        `epsilon_cutoff` in [0, 1) (0 = off) drops the tokens below that probability; `eta_cutoff` in [0, 1) (0 = off) drops those below
+        min(eta, sqrt(eta) exp(-entropy)) (eta sampling).  Every rule acts on values, so equal logits stay or go together, and each keeps the
+        largest.  The exact rules are those of ff_sample_token_truncated in include/flamingo_fusion.h.  Routing is that of sampling: the
+        static session (the rules and the draw are one launch inside the replayed step, functional.sample_tokens; the values are launch
+        constants and part of the session key) only with static_decode=True, otherwise the dynamic loop with
+        decoding.truncate_logits_torch, which also runs on CPU tensors.  token_logprobs stay the log-softmax before temperature and every
+        filter.  Not offered: min_tokens_to_keep > 1, per-row values, truncation for beam sampling."""
         procs = D.check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos_token_id)
         n_ret = D.check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample)
         groups = D.check_group_args(num_beam_groups, diversity_penalty, num_beams, do_sample)
         gkw = {} if groups is None else {"groups": groups}                   # nothing is passed on without groups: the calls are what they were
         guidance = D.check_guidance_args(guidance_scale)
+        trunc = D.check_truncation_args(min_p, typical_p, epsilon_cutoff, eta_cutoff, do_sample, num_beams)
+        tkw = {} if trunc is None else {"truncation": trunc}                 # nothing is passed on without them: the calls are what they were
         ids = inputs if inputs is not None else input_ids
         assert ids is not None and media_locations is not None, "generate() needs input ids and media_locations"
         cons = D.check_constraint_args(candidate_ids, bad_words_ids, self.flamingo.lm.config.vocab_size, eos_token_id, procs, ids.shape[1], max_length)
@@ -545,7 +559,7 @@ class FlamingoModel(PreTrainedModel):
             res = D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, generator=generator, processors=procs,
                                    sampling=D.Sampling(float(temperature), int(top_k), float(top_p)) if do_sample else None,
                                    beams=D.Beams(int(num_beams), bool(early_stopping), float(length_penalty)) if num_beams > 1 else None,
-                                   logprobs=bool(output_logprobs), n_return=n_beams_out, **ckw, **gkw)
+                                   logprobs=bool(output_logprobs), n_return=n_beams_out, **ckw, **gkw, **tkw)
         elif num_beams > 1:
             res = self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty, processors=procs,
                                     n_return=n_beams_out, **ckw, **gkw, **({} if guidance is None else {"step": step, "reorder_cache": reorder}))
@@ -555,7 +569,7 @@ class FlamingoModel(PreTrainedModel):
             lp_dtype = (torch.float64 if next(self.parameters()).dtype == torch.float64 else torch.float32) if output_logprobs else None
             res = D.dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad,
                                    sampling=D.Sampling(temperature, top_k, top_p) if do_sample else None, generator=generator, processors=procs,
-                                   logprob_dtype=lp_dtype, **ckw)
+                                   logprob_dtype=lp_dtype, **ckw, **tkw)
         if not return_dict_in_generate:
             return res[0] if n_beams_out else res
         if n_beams_out:
@@ -585,7 +599,7 @@ class FlamingoModel(PreTrainedModel):
         """Caption a batch of images; the prompt is replicated for every image (reference :550-605).  `kwargs` are generation
         arguments (do_sample, temperature, top_k, top_p, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length,
         min_new_tokens, num_return_sequences, output_logprobs, return_dict_in_generate, num_beam_groups, diversity_penalty, guidance_scale,
-        ...) and go to
+        min_p, typical_p, epsilon_cutoff, eta_cutoff, ...) and go to
         generate(), which rejects unknown ones.  num_beams=4, num_beam_groups=4, diversity_penalty=1.0, num_return_sequences=4,
         return_scores=True gives the 4 best DIFFERENT captions of diverse beam search with the (penalised) scores they were ranked by.
         guidance_scale=1.5 weighs the image against the language model's prior (classifier-free guidance, see generate()).

@@ -58,7 +58,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, addition only: log-probability of the chosen token on the captured decode step, ff_token_logprob;
                                 * still 6, addition only: constrained decoding on the captured decode step (candidate trie, bad words), ff_logits_constrain;
                                 * still 6, addition only: diverse beam search on the captured decode step, ff_group_beam_step;
-                                * still 6, addition only: classifier-free guidance on the captured decode step, ff_guided_logits) */
+                                * still 6, addition only: classifier-free guidance on the captured decode step, ff_guided_logits;
+                                * still 6, addition only: truncation samplers (min_p, typical_p, epsilon / eta cutoff), ff_sample_token_truncated) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -559,6 +560,34 @@ int ff_shifted_ce_bwd_reg(int dtype, int batch, int seq, int vocab, const void* 
  * ------------------------------------------------------------------------------------------------------ */
 int ff_sample_token(int dtype, int rows, int vocab, long long ld, const void* logits, float temperature, int top_k, float top_p,
                     const float* u, long long* token, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Token selection under the truncation samplers (added under ABI 6): ff_sample_token's filters followed by min_p, typical_p,
+ * epsilon_cutoff and eta_cutoff - transformers' MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper (each with
+ * min_tokens_to_keep = 1), in transformers' order - and the draw, one launch, no sort, capturable.  logits, ld, u and token are as in
+ * ff_sample_token.  Per row, x_i the logits as stored, z_i = x_i / temperature; "q renormalised over a set" is exp(z_i - max z) divided
+ * by its sum over that set:
+ *   1. K0 = rule 1 of ff_sample_token (top-k).
+ *   2. K1 = rule 3 of ff_sample_token (the nucleus within K0).
+ *   3. min_p:  K2 = {i in K1 : exp(z_i - max z) >= min_p}, i.e. q_i >= min_p * max q.   min_p == 0: K2 = K1.
+ *   4. typical_p:  r = q renormalised over K2, H = -sum_{K2} r log r, d_i = |-log r_i - H|;
+ *      K3 = {i in K2 : sum of r_j over the j in K2 with d_j < d_i (strictly) < typical_p}.   typical_p == 1: K3 = K2.
+ *   5. epsilon_cutoff:  r = q renormalised over K3;  K4 = {i in K3 : r_i >= epsilon_cutoff, or x_i is the largest value of K3}.
+ *      epsilon_cutoff == 0: K4 = K3.
+ *   6. eta_cutoff:  r and H over K4, eta* = min(eta_cutoff, sqrt(eta_cutoff) * exp(-H));
+ *      K5 = {i in K4 : r_i >= eta*, or x_i is the largest value of K4}.   eta_cutoff == 0: K5 = K4.
+ *   7. S = sum over K5 of q; token = the smallest i in K5 whose inclusive prefix sum over K5, in index order, exceeds u * S (the last
+ *      element of K5 if rounding leaves none): rule 4 of ff_sample_token over K5.
+ * Every stage is a function of the value: equal values stay or go together, every stage keeps all columns of its largest kept value, so K5
+ * is never empty.  -inf logits are never chosen.  A row that holds a NaN or +inf, or nothing but -inf, gives an unspecified token inside
+ * [0, vocab).  fp32 math in a fixed order: equal inputs give equal tokens, eager or replayed from a graph.  The four values are launch
+ * constants.  With all four off the result is ff_sample_token's.
+ * FF_ERR_SHAPE: what ff_sample_token rejects; min_p outside [0, 1], typical_p outside (0, 1], epsilon_cutoff or eta_cutoff outside [0, 1),
+ * any of them not finite.  FF_ERR_UNSUPPORTED: another dtype.
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_sample_token_truncated(int dtype, int rows, int vocab, long long ld, const void* logits, float temperature, int top_k, float top_p,
+                              float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff, const float* u, long long* token,
+                              ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Beam search on the captured decode step (added under ABI 6): ff_beam_step selects and keeps ALL bookkeeping on the device (no host

@@ -1,6 +1,6 @@
 """The measuring methods the per-feature bench tools share, each stated once: two figures from two tools are comparable when both come
 through the same function here.  A tool keeps what it measures: its docstring, its own arguments, its arms or paths, its byte counts and
-its feature-specific figures.  The decode-feature tools (beam, group_beam, decode_sample, logits_process, token_logprob, guidance) use the caption set-up, the
+its feature-specific figures.  The decode-feature tools (beam, group_beam, decode_sample, logits_process, token_logprob, guidance, truncation) use the caption set-up, the
 host-clock rounds, the tokens report and launch_us; the optimizer-arm tools (ema, adamw_sr, grad_clip, grad_accum) use the config and
 arm set-up, the replay rounds and the per-round arithmetic.
 """
