@@ -1,5 +1,5 @@
 from .configuration_flamingo import FlamingoConfig
-from .decoding import GenerateOutput
+from .decoding import CandidateScores, GenerateOutput
 from .flamingo_processor import FlamingoProcessor
 from .gated_cross_attention import GatedCrossAttentionBlock, MaskedCrossAttention, ModifiedLMBlock
 from .modeling_flamingo import FlamingoBaseModel, FlamingoGPT2, FlamingoModel, FlamingoOPT
@@ -9,4 +9,4 @@ from .perceiver_resampler import PerceiverAttentionLayer, PerceiverResampler
 
 __all__ = ["FlamingoConfig", "FlamingoModel", "FlamingoProcessor", "FlamingoBaseModel", "FlamingoGPT2", "FlamingoOPT",
            "PerceiverResampler", "PerceiverAttentionLayer", "GatedCrossAttentionBlock", "MaskedCrossAttention", "ModifiedLMBlock",
-           "FusedAdamW", "clip_grad_norm_", "GraphedTrainStep", "GenerateOutput"]
+           "FusedAdamW", "clip_grad_norm_", "GraphedTrainStep", "GenerateOutput", "CandidateScores"]

@@ -1040,3 +1040,171 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
     fill = pad if pad is not None else 0
     ids = torch.tensor([o + [fill] * (width - len(o)) for o in out], dtype=torch.long, device=dev)
     return ids if n_return is None else (ids, torch.tensor(out_scores, dtype=torch.float32, device=dev))
+
+
+# ---- exact closed-set scoring: the candidate trie walked level by level (FlamingoModel.score_candidates) ----
+@dataclasses.dataclass
+class CandidateScores:
+    """What score_candidates() returns.  `logprobs` (b, k), float32 (float64 for a model that computes in float64): for sequence s and
+    candidate j, in the caller's order, sum_t log p(c_j[t] | media_s, prompt_s, c_j[:t]), plus log p(eos | media_s, prompt_s, c_j) when eos
+    is scored.  `token_counts` (k,) int64: the number of scored tokens, eos included when it is scored."""
+    logprobs: torch.Tensor
+    token_counts: torch.Tensor
+
+
+def logprob_gather_torch(logits, row_first, tok, base=None):
+    """Rules S1 - S3 of ff_logprob_gather (include/flamingo_fusion.h) restated in torch, on tensors of any device: out[q] = (base[r] +)
+    log_softmax(logits[r])[tok[q]] for the queries q in [row_first[r], row_first[r + 1]) of row r, bounds clamped into [0, n_q].  The math
+    is float32, float64 for float64 logits, and so is the result; a token outside [0, V) gives NaN, -inf at the token -inf, a row holding
+    NaN or +inf NaN; only rows with a non-empty list are read, and a query no row owns stays NaN."""
+    rows, V = logits.shape
+    n_q = tok.numel()
+    dt = torch.float64 if logits.dtype == torch.float64 else torch.float32
+    dev = logits.device
+    out = torch.full((n_q,), float("nan"), dtype=dt, device=dev)
+    rf = row_first.to(torch.long).clamp(0, n_q)
+    counts = (rf[1:] - rf[:-1]).clamp(min=0)
+    total = int(counts.sum())
+    if total == 0:
+        return out
+    row_of = torch.repeat_interleave(torch.arange(rows, device=dev), counts)
+    q = rf[:-1][row_of] + torch.arange(total, device=dev) - (counts.cumsum(0) - counts)[row_of]
+    used = (counts > 0).nonzero()[:, 0]
+    x = logits.index_select(0, used).to(dt)                                 # rows without queries are not read
+    lse = torch.logsumexp(x, dim=-1)
+    lse = torch.where(torch.isnan(lse) | (lse == float("inf")), torch.full_like(lse, float("nan")), lse)
+    slot = torch.zeros(rows, dtype=torch.long, device=dev)
+    slot[used] = torch.arange(used.numel(), device=dev)
+    t = tok.to(torch.long)[q]
+    valid = (t >= 0) & (t < V)
+    lp = x[slot[row_of], t.clamp(0, V - 1)] - lse[slot[row_of]]
+    lp = torch.where(valid, lp, torch.full_like(lp, float("nan")))
+    if base is not None:
+        lp = base.to(dt)[row_of] + lp
+    out[q] = lp
+    return out
+
+
+def _ranges(starts, counts):
+    """numpy: the concatenation of arange(starts[i], starts[i] + counts[i])"""
+    import numpy as np
+    return np.repeat(starts - (np.cumsum(counts) - counts), counts) + np.arange(int(counts.sum()))
+
+
+def trie_levels(trie, eos, b, max_rows):
+    """The host-side tables of score_trie, built once per call from the TokenTrie arrays with numpy.  A node NEEDS LOGITS when it has an
+    edge, or when it is terminal and eos is scored.  The root's subtrees are split, in edge order, into groups in which the widest level
+    (nodes needing logits) times b stays within max_rows; a single subtree wider than that forms a group alone.  Returns a list of groups,
+    each a list of levels (depth 0 = the root, restricted to the group's edges), each level a dict:
+    `R` nodes / rows per sequence, `Q` queries per sequence, `row_first` (b R + 1,) and `tok` (b Q,) int32, sequence-major - a node's
+    queries are its edge tokens, then eos if it is terminal and eos is scored -; `fin_q` / `fin_nodes`: the queries whose result is the
+    finished score of a terminal node; `next_q` / `next_parent` / `next_tok`: the queries that open a row of the next level, the row (within
+    the sequence) they hang from and the token to feed."""
+    import numpy as np
+    nf, et, ec = trie.node_first.astype(np.int64), trie.edge_tok.astype(np.int64), trie.edge_child.astype(np.int64)
+    term = trie.node_terminal.astype(bool)
+    N, deg = trie.n_nodes, np.diff(trie.node_first.astype(np.int64))
+    eos_on = eos is not None
+    needs = (deg > 0) | (term & eos_on)
+    edge_parent = np.repeat(np.arange(N), deg)
+    depth, sub = np.zeros(N, np.int64), np.full(N, -1, np.int64)        # sub: the root edge a node descends from
+    frontier, d = np.array([0]), 0
+    while frontier.size:
+        e = _ranges(nf[frontier], deg[frontier])
+        depth[ec[e]] = d + 1
+        sub[ec[e]] = e if d == 0 else sub[edge_parent[e]]
+        frontier, d = ec[e], d + 1
+    n_sub = int(deg[0])
+    width = np.zeros((n_sub, int(depth.max()) + 1), np.int64)
+    inner = np.flatnonzero(needs[1:]) + 1
+    np.add.at(width, (sub[inner], depth[inner]), 1)
+    bounds, cur = [0], np.zeros(width.shape[1], np.int64)
+    for s in range(n_sub):
+        if s > bounds[-1] and int((cur + width[s]).max()) * b > max_rows:
+            bounds.append(s)
+            cur = np.zeros_like(cur)
+        cur = cur + width[s]
+    bounds.append(n_sub)
+    groups = []
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        levels, nodes = [], np.array([0])
+        while nodes.size:
+            R = nodes.size
+            starts, counts = (np.array([lo]), np.array([hi - lo])) if not levels else (nf[nodes], deg[nodes])
+            has_eos = term[nodes] & eos_on
+            cnt = counts + has_eos
+            first = np.cumsum(cnt) - cnt
+            Q = int(cnt.sum())
+            e, qe = _ranges(starts, counts), _ranges(first, counts)
+            tok = np.empty(Q, np.int64)
+            tok[qe] = et[e]
+            if eos_on:
+                tok[(first + counts)[has_eos]] = eos
+            children = ec[e]
+            fin = term[children] & (not eos_on)
+            opens = needs[children]
+            levels.append(dict(R=R, Q=Q, tok=np.tile(tok, b).astype(np.int32),
+                               row_first=np.concatenate([[0], np.cumsum(np.tile(cnt, b))]).astype(np.int32),
+                               fin_q=(first + counts)[has_eos] if eos_on else qe[fin], fin_nodes=nodes[has_eos] if eos_on else children[fin],
+                               next_q=qe[opens], next_parent=np.repeat(np.arange(R), counts)[opens], next_tok=et[e][opens]))
+            nodes = children[opens]
+        groups.append(levels)
+    return groups
+
+
+def score_trie(step, reorder_cache, ids, ml, am, pixel_values, visual_features, candidate_ids, vocab, eos=None, max_rows=1024):
+    """Exact log p(candidate | media, prompt) of every candidate for every sequence, each distinct candidate prefix run once: the candidate
+    trie (TokenTrie) walked level-synchronously over the cached decode path.  `step(step_ids, ml, am, past, pixel_values, visual_features)`
+    returns (the last position's logits (rows, V) - in the model's dtype, a view is fine -, past), `reorder_cache(past, idx)` gathers cache
+    rows (idx may be longer than the cache has rows): FlamingoModel._score_step / ._reorder_cache.
+    The prompt step runs on the b rows; its logits are the root's.  At depth d the rows are (sequence, node needing logits at depth d),
+    sequence-major, a sequence's nodes in lexicographic order of their prefixes; ONE logprob_gather serves the level - functional.logprob_gather (ff_logprob_gather, the logits read in place in their
+    dtype, no (rows, V) float32 temporary) on GPU tensors, logprob_gather_torch on CPU tensors -, with the path's accumulated score as
+    `base`, and its result splits into the next level's bases and the finished scores.  The next level is one LM step on the edge tokens,
+    the caches gathered from the parent rows; media_locations gains a zero column, the attention mask a one column.  After the prompt that
+    is longest - 1 steps, longest when eos is scored.
+    `max_rows` bounds memory: the root's subtrees are split, in edge order, into groups whose widest level times b stays within it (a
+    single subtree wider than that runs alone, over the bound), and each group is walked on its own.  For every group the b-row prompt step
+    is RE-RUN (the caches of a group are gathered in place, and a prompt step of b rows costs less than a deep copy of its caches is worth
+    keeping); pass `visual_features`, not pixel_values, so that the visuals are not encoded again (score_candidates does).
+    This is the dynamic path: the row count changes with every level, nothing is captured into a graph.
+    ValueError: what TokenTrie raises for the candidates; max_rows not an int >= 1."""
+    import numpy as np
+    if isinstance(max_rows, bool) or not isinstance(max_rows, int) or max_rows < 1:
+        raise ValueError(f"score_candidates(): max_rows must be an integer >= 1, got {max_rows!r}")
+    if eos is not None and (isinstance(eos, bool) or not isinstance(eos, int) or not 0 <= eos < vocab):
+        raise ValueError(f"score_candidates(): eos_token_id must be a token id in [0, {vocab}), got {eos!r}")
+    if hasattr(candidate_ids, "__iter__") and not isinstance(candidate_ids, (str, bytes)):
+        candidate_ids = list(candidate_ids)                            # (read twice: by the trie, and for the columns)
+    trie = TokenTrie(candidate_ids, vocab, eos)
+    b, dev = ids.shape[0], ids.device
+    child = dict(zip(zip(np.repeat(np.arange(trie.n_nodes), np.diff(trie.node_first)).tolist(), trie.edge_tok.tolist()), trie.edge_child.tolist()))
+    columns = []                                                       # caller column -> terminal node (duplicates share one)
+    for c in candidate_ids:
+        s = 0
+        for t in c:
+            s = child[(s, int(t))]
+        columns.append(s)
+    dev_idx = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    node_scores = None
+    for levels in trie_levels(trie, eos, b, max_rows):
+        logits, past = step(ids, ml, am, None, pixel_values, visual_features)
+        ml_g, am_g, base = ml, am, None
+        for lv in levels:
+            gather = F.logprob_gather if logits.is_cuda else logprob_gather_torch
+            out = gather(logits, dev_idx(lv["row_first"]), dev_idx(lv["tok"]), base).view(b, lv["Q"])
+            if node_scores is None:
+                node_scores = torch.full((b, trie.n_nodes), float("nan"), dtype=out.dtype, device=dev)
+            if lv["fin_q"].size:
+                node_scores[:, dev_idx(lv["fin_nodes"])] = out[:, dev_idx(lv["fin_q"])]
+            if not lv["next_q"].size:
+                break
+            rows_from = dev_idx((np.arange(b)[:, None] * lv["R"] + lv["next_parent"][None, :]).reshape(-1))
+            base = out[:, dev_idx(lv["next_q"])].reshape(-1)
+            past = reorder_cache(past, rows_from)
+            ml_g = torch.cat([ml_g.index_select(0, rows_from), torch.zeros_like(ml_g[:1, :1]).expand(rows_from.numel(), 1)], dim=1)
+            am_g = torch.cat([am_g.index_select(0, rows_from), torch.ones_like(am_g[:1, :1]).expand(rows_from.numel(), 1)], dim=1)
+            step_ids = dev_idx(np.tile(lv["next_tok"], b)).to(ids.dtype)[:, None]
+            logits, past = step(step_ids, ml_g, am_g, past, None, None)
+    counts = torch.tensor([len(c) + (eos is not None) for c in candidate_ids], dtype=torch.long, device=dev)
+    return CandidateScores(logprobs=node_scores[:, dev_idx(np.array(columns, np.int64))], token_counts=counts)

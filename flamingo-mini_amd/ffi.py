@@ -176,6 +176,7 @@ _SIGNATURES = {
     "ff_group_beam_step": (_I, [C.POINTER(BeamDesc), _I, C.c_float, _P, _P, _P, _SZ, _P]),
     "ff_logits_process": (_I, [_I, _I, _I, C.c_longlong, _P, _P, C.c_longlong, C.c_longlong, _P, C.c_float, _I, _I, _P, _P]),
     "ff_token_logprob": (_I, [_I, _I, _I, C.c_longlong, _P, _P, _P, _P, _P, _P]),
+    "ff_logprob_gather": (_I, [_I, _I, _I, C.c_longlong, _P, _P, _P, _I, _P, _P, _P]),
     "ff_logits_constrain": (_I, [_I, _I, _I, C.c_longlong, _P, _P, C.c_longlong, C.c_longlong, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P]),
     "ff_guided_logits": (_I, [_I, _I, _I, C.c_longlong, _P, C.c_longlong, _P, _P, _P, C.c_longlong, _P]),
     "ff_xattn_block_bwd_kv": (_I, [C.POINTER(XattnDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _SZ, _P]),

@@ -1073,6 +1073,35 @@ def token_logprobs(logits: torch.Tensor, token: torch.Tensor, skip: Optional[tor
     return out
 
 
+def logprob_gather(logits: torch.Tensor, row_first: torch.Tensor, tok: torch.Tensor, base: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[q] = (base[r] +) log_softmax(logits[r])[tok[q]] for the queries q in [row_first[r], row_first[r + 1]) of every row r of `logits`
+    (rows, V), float32 / bfloat16 on the GPU, in float32: ff_logprob_gather, one launch that reads each row with a non-empty list once, in
+    its own dtype, and never writes it - no (rows, V) float32 temporary; the exact rules (S1 - S5) are in include/flamingo_fusion.h.  Only
+    the last dimension has to be contiguous (logits3d[:, -1] is read in place through its row stride).  `row_first`: rows + 1 int32, the
+    CSR table; `tok`: n_q int32; `base` (rows, float32): added to the row's values with one rounded add.  A token outside [0, V) gives NaN.
+    With `out` (float32, n_q, contiguous) nothing is allocated, so the call can be captured into a graph."""
+    ffi.require_cuda(logits, row_first, tok, base, out)
+    if logits.ndim != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logprob_gather: logits must be (rows, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
+    rows, V = logits.shape
+    if row_first.dtype != torch.int32 or row_first.shape != (rows + 1,) or not row_first.is_contiguous():
+        raise ValueError(f"logprob_gather: row_first must be {rows + 1} contiguous int32 values, got {tuple(row_first.shape)} {row_first.dtype}")
+    if tok.dtype != torch.int32 or tok.ndim != 1 or tok.numel() < 1 or not tok.is_contiguous():
+        raise ValueError(f"logprob_gather: tok must be n_q >= 1 contiguous int32 values, got {tuple(tok.shape)} {tok.dtype}")
+    n_q = tok.numel()
+    if base is not None and (base.dtype != torch.float32 or base.shape != (rows,) or not base.is_contiguous()):
+        raise ValueError(f"logprob_gather: base must be {rows} contiguous float32 values, got {tuple(base.shape)} {base.dtype}")
+    if out is None:
+        out = _new((n_q,), torch.float32, logits.device)
+    if out.dtype != torch.float32 or out.shape != (n_q,) or not out.is_contiguous():
+        raise ValueError(f"logprob_gather: out must be {n_q} contiguous float32 values, got {tuple(out.shape)} {out.dtype}")
+    ld = logits.stride(0) if rows > 1 else V
+    ffi.check(ffi.lib().ff_logprob_gather(ffi.dtype_code(logits.dtype), rows, V, ld, logits.data_ptr(), row_first.data_ptr(), tok.data_ptr(), n_q,
+                                          ffi.ptr(base), out.data_ptr(), ffi.stream_handle(logits.device)), "ff_logprob_gather")
+    return out
+
+
 def guided_logits(cond: torch.Tensor, uncond: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Classifier-free guidance, lu + scale * (lc - lu) with lc / lu = log_softmax of `cond` / `uncond` (rows, V), float32 / bfloat16 on the
     GPU, in float32: ff_guided_logits, one launch that reads each row twice and writes neither; the exact rules are in

@@ -430,6 +430,13 @@ class FlamingoModel(PreTrainedModel):
                             pixel_values=pixel_values if past is None else None, visual_features=visual_features if past is None else None)
         return out.logits[:, -1].float(), out.past_key_values
 
+    def _score_step(self, step_ids, ml, am, past, pixel_values, visual_features):
+        """_decode_step for score_candidates: the last position's logits as a VIEW in the model's dtype (no .float() copy) - what
+        functional.logprob_gather reads in place through the row stride."""
+        out = self.flamingo(input_ids=step_ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=past,
+                            pixel_values=pixel_values if past is None else None, visual_features=visual_features if past is None else None)
+        return out.logits[:, -1], out.past_key_values
+
     _filter_logits = staticmethod(D.filter_logits)         # the torch restatements the dynamic loops use
     _process_logits = staticmethod(D.process_logits)
 
@@ -644,10 +651,70 @@ class FlamingoModel(PreTrainedModel):
         return group(captions)
 
     @torch.no_grad()
+    def score_candidates(self, input_ids, media_locations, attention_mask=None, pixel_values=None, visual_features=None, *,
+                         candidate_ids, eos_token_id: Optional[int] = None, max_rows: int = 1024) -> D.CandidateScores:
+        """EXACT closed-set scoring (classification, multiple choice, yes / no, reranking): for every sequence s of the batch and every
+        candidate j of ONE candidate set (lists of token ids, as generate(candidate_ids=)),
+            logprobs[s, j] = sum_t log p(c_j[t] | media_s, prompt_s, c_j[:t])   (+ log p(eos | media_s, prompt_s, c_j) with eos_token_id)
+        in a decoding.CandidateScores (logprobs (b, k) float32 - float64 for a float64 model -, token_counts (k,)).  Columns follow the
+        caller's order; duplicate candidates get equal columns; a candidate that is a prefix of another is fine, and with eos scored the
+        two become comparable.  Unlike generate(candidate_ids=) this is no search and nothing is renormalised over the allowed tokens:
+        calibration, top-k accuracy and ranking metrics can be computed from it.
+        The visuals are encoded once, the prompt runs once per sequence and group through the cross-attention / LM caches, and every
+        distinct candidate prefix runs once: decoding.score_trie walks the candidates' trie level by level, one LM step and one launch of
+        ff_logprob_gather per level (functional.logprob_gather reads the queried tokens' log-probabilities from the step's logits in the
+        model's dtype - no float32 copy, no vocabulary-wide log-softmax); on CPU tensors the same walk runs with
+        decoding.logprob_gather_torch.  `max_rows` bounds the LM batch of a level: the first tokens' subtrees are split into groups whose
+        widest level times b stays within it (one subtree wider than that runs alone); every group re-runs the b-row prompt step, the
+        visuals are never encoded twice.  The path is dynamic - shapes change per level, no graph is captured, no decode session is built.
+        ValueError: no candidates, an empty one, an id outside the vocabulary, a candidate that contains eos; max_rows not an int >= 1."""
+        am = attention_mask if attention_mask is not None else torch.ones_like(input_ids)
+        if visual_features is None and pixel_values is not None:         # encoded once, whatever the number of groups
+            visual_features, pixel_values = self.flamingo.encode_resample_visuals(pixel_values), None
+        return D.score_trie(self._score_step, self._reorder_cache, input_ids, media_locations, am, pixel_values, visual_features,
+                            candidate_ids, self.flamingo.lm.config.vocab_size, eos=eos_token_id, max_rows=max_rows)
+
+    @torch.no_grad()
+    def classify(self, processor, pixel_values=None, images=None, prompt: str = "<image>", candidates=None, score_eos: bool = False,
+                 normalize: Optional[str] = None, max_rows: int = 1024):
+        """Closed-set classification of a batch of images over strings: (labels, probs), `labels` the best candidate string per image,
+        `probs` (b, k) the softmax over the candidates of the ranked quantity - score_candidates' logprobs with normalize=None, logprobs /
+        token_counts with normalize="tokens" (anything else: ValueError).  The prompt is replicated for every image; every candidate is
+        tokenised VERBATIM with processor.tokenizer(s, add_special_tokens=False), as generate_captions(candidates=) does (a leading space
+        is the caller's business).  score_eos=True also scores the LM's eos after each candidate, which makes a candidate comparable
+        with its own extensions."""
+        if normalize not in (None, "tokens"):
+            raise ValueError(f"classify(): normalize must be None or 'tokens', got {normalize!r}")
+        if candidates is None or isinstance(candidates, str):
+            raise ValueError(f"classify(): pass a list of strings, got {'the string ' if isinstance(candidates, str) else ''}{candidates!r}")
+        candidates = list(candidates)
+        cand_ids = [list(processor.tokenizer(s, add_special_tokens=False)["input_ids"]) for s in candidates]
+        device = self.device
+        if images is not None:
+            assert pixel_values is None, "you can only pass either images or visual features to classify()!"
+            if not isinstance(images, (list, tuple)):
+                images = [images]
+            pixel_values = processor(images=images, device=device)["pixel_values"]
+        assert pixel_values is not None, "you must pass either images or visual features to classify()!"
+        batch_size = pixel_values.size(0)
+        input_ids, media_locations, attention_mask = processor.encode_text(prompt, device)
+        input_ids = input_ids[:1].expand(batch_size, -1).contiguous()
+        media_locations = media_locations[:1].expand(batch_size, -1).contiguous()
+        attention_mask = attention_mask[:1].expand(batch_size, -1).contiguous()
+        if pixel_values.ndim == 4:
+            pixel_values = pixel_values[:, None]       # (b c h w) -> one image per sequence
+        res = self.score_candidates(input_ids, media_locations, attention_mask, pixel_values=pixel_values, candidate_ids=cand_ids,
+                                    eos_token_id=self.flamingo.lm.config.eos_token_id if score_eos else None, max_rows=max_rows)
+        ranked = res.logprobs if normalize is None else res.logprobs / res.token_counts.to(res.logprobs.dtype)
+        probs = ranked.softmax(-1)
+        return [candidates[i] for i in probs.argmax(-1).tolist()], probs
+
+    @torch.no_grad()
     def score_sequences(self, input_ids, media_locations, attention_mask, pixel_values=None, visual_features=None,
                         k: int = 100000) -> torch.Tensor:
         """Zero-shot scoring as the reference has it (:607-712): the log-prob of each candidate sequence given the same visuals.  Kept for
-        parity; the SUPPORTED route for closed-set tasks (classification, multiple-choice VQA, yes/no) is constrained decoding:
+        parity.  For EXACT scores of a closed set - every candidate's log-probability for a whole batch, shared prefixes run once, no
+        vocabulary-wide log-softmax - use score_candidates() (or classify() on strings); for SEARCH use constrained decoding,
         generate(..., candidate_ids=, return_dict_in_generate=True, output_logprobs=True) - greedy or beam search restricted to the trie of
         the candidates inside the cached, graph-replayed decode step, sequences_scores / token_logprobs giving the chosen candidate's
         probability over the allowed set and num_return_sequences a top-n - which runs the prefix once and never materialises a per-candidate

@@ -59,7 +59,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, addition only: constrained decoding on the captured decode step (candidate trie, bad words), ff_logits_constrain;
                                 * still 6, addition only: diverse beam search on the captured decode step, ff_group_beam_step;
                                 * still 6, addition only: classifier-free guidance on the captured decode step, ff_guided_logits;
-                                * still 6, addition only: truncation samplers (min_p, typical_p, epsilon / eta cutoff), ff_sample_token_truncated) */
+                                * still 6, addition only: truncation samplers (min_p, typical_p, epsilon / eta cutoff), ff_sample_token_truncated;
+                                * still 6, addition only: exact closed-set scoring over a candidate trie, ff_logprob_gather) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -785,6 +786,29 @@ int ff_logits_constrain(int dtype, int rows, int vocab, long long ld, void* logi
  * ------------------------------------------------------------------------------------------------------ */
 int ff_guided_logits(int dtype, int rows, int vocab, long long ld_cond, const void* cond, long long ld_uncond, const void* uncond,
                      const float* scale, float* out, long long ld_out, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Log-probabilities of many queried tokens per row (added under ABI 6): what FlamingoModel.score_candidates reads from the logits of one
+ * level of the candidate trie.  logits follows the contract of ff_token_logprob: `rows` rows of `vocab` elements of `dtype` (FF_DTYPE_F32 /
+ * FF_DTYPE_BF16), row r at element r * ld, ld >= vocab, element alignment only (logits[:, -1] of a (rows, 1, vocab) or (rows, 2, vocab)
+ * tensor is read in place); never written.  row_first: rows + 1 int32 on the device, a CSR table over the rows - row r owns the queries q
+ * in [row_first[r], row_first[r + 1]).  tok: n_q int32 on the device.  base: rows fp32 on the device, or null.  out: n_q fp32 on the
+ * device, out[q] belongs to query q.
+ *   S1.  lse_r is computed with ff_token_logprob's row pass, operation for operation (one 256-thread workgroup per row, (max, sum) pairs
+ *        from (-FLT_MAX, 0), the fixed wave and block combine, lse = M + logf(S)): for a row at the same address lse_r has the bits
+ *        ff_token_logprob stores.
+ *   S2.  For every query q of row r, t = tok[q]:  lp = NaN if t is outside [0, vocab), and nothing is read;  otherwise lp = x_t - lse_r.
+ *        x_t == -inf gives -inf; a row holding NaN or +inf gives NaN.  out[q] = lp when base is null, otherwise out[q] = base[r] + lp:
+ *        one fp32 add, rounded once, never contracted with the subtraction.
+ *   S3.  A row with an empty list is not read, and nothing is written for it.
+ *   S4.  row_first is read as given and every bound is clamped into [0, n_q]: nothing outside tok[0 .. n_q) and out[0 .. n_q) is touched,
+ *        whatever the table holds.  It is the caller's duty that the lists partition [0, n_q); then every out[q] is written exactly once.
+ *   S5.  One launch, no atomics, no allocation, no host synchronisation, capturable; equal inputs give equal bits, eager or replayed.
+ * FF_ERR_SHAPE: null logits, row_first, tok or out; rows <= 0, vocab <= 0, ld < vocab, n_q <= 0.  FF_ERR_UNSUPPORTED: another dtype.  Both
+ * before any launch.
+ * ------------------------------------------------------------------------------------------------------ */
+int ff_logprob_gather(int dtype, int rows, int vocab, long long ld, const void* logits, const int* row_first, const int* tok, int n_q,
+                      const float* base, float* out, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * QuickGELU of the CLIP vision tower, y = x * sigmoid(1.702 x) (transformers.activations.QuickGELUActivation, selected by
