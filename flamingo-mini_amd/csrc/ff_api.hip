@@ -1042,6 +1042,32 @@ extern "C" size_t ff_xattn_kv_offset(const ff_xattn_desc* d) {
     (void)d;
     return 0;
 }
+// answered from xa_saved_layout itself: the layout is walked over a base address that is never dereferenced
+extern "C" int ff_xattn_saved_view(const ff_xattn_desc* d, int what, size_t* offset, size_t* bytes) {
+    using namespace ff;
+    FF_TRY(xa_check(d));
+    FF_CHECK(offset && bytes, FF_ERR_SHAPE, "ff_xattn_saved_view: null argument");
+    const XaDims s(*d);
+    XaSaved S;
+    const uintptr_t base = 4096;
+    xa_saved_layout(s, (void*)base, 0, S);
+    const size_t M = (size_t)s.b * s.L, stat = M * 4, act = M * s.d * s.es;
+    const void* p = nullptr;
+    size_t n = 0;
+    switch (what) {
+        case FF_XA_SAVED_MEAN_A: p = S.mean_a; n = stat; break;
+        case FF_XA_SAVED_RSTD_A: p = S.rstd_a; n = stat; break;
+        case FF_XA_SAVED_YN: p = S.yn; n = act; break;
+        case FF_XA_SAVED_Y1: p = S.y1; n = act; break;
+        case FF_XA_SAVED_MEAN_F: p = S.mean_f; n = stat; break;
+        case FF_XA_SAVED_RSTD_F: p = S.rstd_f; n = stat; break;
+        case FF_XA_SAVED_XN_F: p = S.xn_f; n = act; break;
+        default: FF_CHECK(false, FF_ERR_SHAPE, "ff_xattn_saved_view: what = %d", what);
+    }
+    *offset = (size_t)((uintptr_t)p - base);
+    *bytes = n;
+    return FF_OK;
+}
 extern "C" int ff_xattn_block_fwd(const ff_xattn_desc* d, const void* y, const void* visual_features, const int* text_time,
                                   const void* const* params, const void* cached_k, const void* cached_v, void* y_out, void* saved,
                                   size_t saved_bytes, void* scratch, size_t scratch_bytes, ff_stream_t stream) {

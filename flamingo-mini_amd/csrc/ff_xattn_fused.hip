@@ -331,7 +331,8 @@ __global__ __launch_bounds__(256) void xa_qattn_fwd_kernel(const XaFusedArgs a_i
     }
     FF_XTL(1);
 
-    // ---- LayerNorm statistics: sums shifted by the mean of the row's first piece (x0), so the one-pass variance has two-pass accuracy ----
+    // ---- LayerNorm statistics: sums shifted by the mean of the row's first piece (x0); bf16 takes the variance from them in the same pass,
+    //      fp32 by a second pass around the mean (below) ----
     {
         float x0 = 0.f, s1 = 0.f, s2 = 0.f;
         for (int base = 0; base < nchunk; base += TPR * NB) {
@@ -366,7 +367,39 @@ __global__ __launch_bounds__(256) void xa_qattn_fwd_kernel(const XaFusedArgs a_i
         for (int o = TPR / 2; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
         const float sh1 = s1 / (float)a.dim;
         const float mu_r = x0 + sh1;
-        const float rs_r = rsqrtf(fmaxf(s2 / (float)a.dim - sh1 * sh1, 0.f) + a.eps);
+        float rs_r;
+        if constexpr (IsBf16<T>::value) {
+            rs_r = rsqrtf(fmaxf(s2 / (float)a.dim - sh1 * sh1, 0.f) + a.eps);
+        } else {
+            // fp32: the variance by a second pass around the mean.  With the 4-element shift a row whose head stands apart from its body
+            // (a massive channel in columns 0..3, the first columns raised) left rstd off by up to 1.6e-5 relative at dim 1536 - measured,
+            // tests/test_hip_layernorm_bounds.py -, above the fp32 tolerance of the parity tests (5e-6).  The row is still in registers
+            // (one_batch) or in cache.
+            float m2 = 0.f;
+            for (int base = 0; base < nchunk; base += TPR * NB) {
+                const int left = ppt - base / TPR;       // wave-uniform
+                if (!one_batch) {
+#pragma unroll
+                    for (int u = 0; u < NB; u++)
+                        if (u < left) raw[u] = *(const uint4*)(yr + (base + sub + u * TPR) * VN);
+                }
+#pragma unroll
+                for (int u = 0; u < NB; u++) {
+                    if (u < left) {
+                        float v[VN];
+                        unpack16(raw[u], v, T());
+#pragma unroll
+                        for (int e = 0; e < VN; e++) {
+                            const float dlt = v[e] - mu_r;
+                            m2 += dlt * dlt;
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = TPR / 2; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);
+            rs_r = rsqrtf(m2 / (float)a.dim + a.eps);
+        }
         if (sub == 0) {
             s_mean[r] = rok ? mu_r : 0.f;
             s_rstd[r] = rok ? rs_r : 0.f;

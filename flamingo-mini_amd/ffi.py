@@ -24,7 +24,8 @@ ACT_NONE, ACT_GELU, ACT_SQRELU, ACT_RELU = -1, 0, 1, 2
 ACTS = {"gelu": ACT_GELU, "sqrelu": ACT_SQRELU, "relu": ACT_RELU}
 ATTN_DENSE, ATTN_MEDIA = 0, 1
 RESAMPLER_GLOBAL_PARAMS, RESAMPLER_LAYER_PARAMS, XATTN_PARAMS = 4, 12, 11
-WGRAD_GROUP_MAX = 12           # capacity of one ff_xattn_wgrad_grouped call (FF_WGRAD_GROUP_MAX); functional._WgradQueue.group = how many it batches
+XA_SAVED = {"mean_a": 0, "rstd_a": 1, "yn": 2, "y1": 3, "mean_f": 4, "rstd_f": 5, "xn_f": 6}      # FF_XA_SAVED_*: selectors of ff_xattn_saved_view
+WGRAD_GROUP_MAX = 12          # capacity of one ff_xattn_wgrad_grouped call (FF_WGRAD_GROUP_MAX); functional._WgradQueue.group = how many it batches
 
 
 class FusionLibraryError(RuntimeError):
@@ -146,6 +147,7 @@ _SIGNATURES = {
     "ff_xattn_saved_bytes": (_SZ, [C.POINTER(XattnDesc)]),
     "ff_xattn_scratch_bytes": (_SZ, [C.POINTER(XattnDesc)]),
     "ff_xattn_kv_offset": (_SZ, [C.POINTER(XattnDesc)]),
+    "ff_xattn_saved_view": (_I, [C.POINTER(XattnDesc), _I, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "ff_xattn_block_fwd": (_I, [C.POINTER(XattnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P]),
     "ff_quick_gelu_fwd": (_I, [_I, C.c_longlong, _P, _P, _P]),
     "ff_quick_gelu_bwd": (_I, [_I, C.c_longlong, _P, _P, _P, _P]),

@@ -316,6 +316,13 @@ int ff_xattn_sync_status(const void* sync, ff_stream_t stream);   /* synchronise
 size_t ff_xattn_saved_bytes(const ff_xattn_desc* d);
 size_t ff_xattn_scratch_bytes(const ff_xattn_desc* d);
 size_t ff_xattn_kv_offset(const ff_xattn_desc* d);
+/* Where ff_xattn_block_fwd leaves the LayerNorm by-products that the backward reads, inside `saved` (host only; for tests and tools).
+ * mean_a / rstd_a: fp32 (batch * n_tokens) statistics of attn.norm; yn = attn.norm(y); y1 = y + tanh(alpha_attn) * to_out(...);
+ * mean_f / rstd_f: statistics of ffw.0 over y1; xn_f = ffw.0(y1).  yn, y1 and xn_f are (batch * n_tokens, dim) in the descriptor's dtype.
+ * Returns FF_OK and the region's byte offset and size, or FF_ERR_SHAPE for a bad descriptor, selector or pointer. */
+enum { FF_XA_SAVED_MEAN_A = 0, FF_XA_SAVED_RSTD_A = 1, FF_XA_SAVED_YN = 2, FF_XA_SAVED_Y1 = 3, FF_XA_SAVED_MEAN_F = 4, FF_XA_SAVED_RSTD_F = 5,
+       FF_XA_SAVED_XN_F = 6 };
+int ff_xattn_saved_view(const ff_xattn_desc* d, int what, size_t* offset, size_t* bytes);
 int ff_xattn_block_fwd(const ff_xattn_desc* d, const void* y, const void* visual_features, const int* text_time,
                        const void* const* params, const void* cached_k, const void* cached_v, void* y_out,
                        void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, ff_stream_t stream);

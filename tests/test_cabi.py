@@ -143,6 +143,19 @@ def test_workspace_queries_and_error_codes_without_a_device():
     assert b"num_time_embeds" in lib.ff_last_error()
     x = ffi.XattnDesc(ffi.DTYPE_BF16, 32, 32, 1280, 1024, 1, 64, 8, 64, 4, ffi.ACT_GELU, 32, 0)
     assert lib.ff_xattn_saved_bytes(x) > 0 and lib.ff_xattn_kv_offset(x) == 0
+    # ff_xattn_saved_view: the seven by-product regions lie inside `saved`, behind the K / V region, in layout order and apart
+    off, nb = C.c_size_t(), C.c_size_t()
+    views = []
+    for what in range(7):
+        assert lib.ff_xattn_saved_view(x, what, C.byref(off), C.byref(nb)) == 0
+        views.append((off.value, nb.value))
+    kv_bytes = 32 * 64 * 2 * 8 * 64 * 2
+    rows = 32 * 32
+    assert [n for _, n in views] == [rows * 4, rows * 4, rows * 1280 * 2, rows * 1280 * 2, rows * 4, rows * 4, rows * 1280 * 2]
+    assert views[0][0] >= kv_bytes and all(o % 16 == 0 for o, _ in views)
+    assert all(a[0] + a[1] <= b[0] for a, b in zip(views, views[1:])) and views[-1][0] + views[-1][1] <= lib.ff_xattn_saved_bytes(x)
+    assert lib.ff_xattn_saved_view(x, 7, C.byref(off), C.byref(nb)) == -1 and b"what" in lib.ff_last_error()
+    assert lib.ff_xattn_saved_view(x, 0, None, C.byref(nb)) == -1
     assert lib.ff_xattn_block_fwd(x, None, None, None, None, None, None, None, None, 0, None, 0, None) == -1     # null arguments
     g = ffi.GemmDesc(ffi.DTYPE_BF16, 1024, 1280, 5120, 0, 0, ffi.rowmap(5120), ffi.rowmap(5120), ffi.rowmap(1280), 1.0, -1, -1, 0)
     assert lib.ff_gemm_workspace_bytes(g) > 0                                                                      # long K, few tiles -> split-K

@@ -459,3 +459,100 @@ def attn_bound_ok(what, got, ref, storage_dtype, c=None):
 def attn_excess(what, got, ref, storage_dtype):
     fixed, t = _attn_parts(what, ref, storage_dtype)
     return _excess(got, ref[what], t, fixed)
+
+
+# ---- LayerNorm, element by element (tests/test_hip_layernorm_bounds.py; the checkers' own tests: tests/test_ln_cases.py) ----
+# The project has five LayerNorm implementations that compute row statistics (csrc/ff_rowwise.hip: two passes, one wave per row; the general
+# fused kernel, the resident kernel and the decode feed-forward kernel: ONE pass, sums shifted by the mean of the row's first 4 / 8 / 16
+# elements; phase 3 of the resident kernel: two passes per head slice and a Chan combine).  rel() / rel_rows() at 5e-6 / 8e-3 on N(0, 2^2)
+# rows cannot tell a shifted from an unshifted one-pass variance, a wrong divisor, a missing piece of a sum or two swapped rows.
+# ln_cases.ln_ref gives every output in float64 from what the kernel saw; y, dx, dgamma and dbeta are computed from the statistics the kernel
+# STORED, so the normalising step is judged apart from them.  u = 2^-24, T the storage type, nothing excluded, NaN = inf:
+#   mean:    |mean - mean*| <= c_m u (|s0| + mean_c |x_c - s0|)        s0 = 0 (two-pass), the row's shift s* (one-pass)
+#   rstd:    |rstd - rstd*| <= rstd* u (c_r + c_v kappa)               kappa = (var* + 2 (mean* - s*)^2) / (var* + eps): what the rounding of
+#            the one-pass sums (relative to sum (x - s)^2 = n (var + (mean - s)^2), and of its correction (mean - s)^2) is to var + eps
+#   y:       1/2 ulp_T(y) + c_y u (|x - mean| rstd |g| + |b|)          (+ u |mean rstd| |g| for the decode kernel: it forms x rs - mean rs)
+#   dx:      1/2 ulp_T + c_x u rstd (|dy g| + mean|dy g| + |xh| mean|dy g xh|) + 1/2 ulp_T(residual) where a residual is added
+#   dgamma, dbeta, rows_reduce:   1/2 ulp_T + c_p u sum |terms|;        gate_grad:  1/2 ulp_T + c_p u (1 - tanh^2 alpha) sum |a b|
+# Where every term is zero (an all-zero dy row without residual, an all-zero row's mean) the kernel must store an exact zero.
+# The constants: measured, not derived (tools/ln_c.py, on the CPU): 4 x the worst excess of the float32 restatements of the kernels in their
+# operation order (tests/ln_cases.py) over ln_ref, at exactly the inputs of tests/test_hip_layernorm_bounds.py; the factor 4 as for ADAMW_C:
+# the device's rsqrtf, its FMA contraction and its reduction order cannot be shown on the CPU.  c_r comes from the two-pass restatements
+# (kappa <= 1 there: the excess is |d rstd| / (u rstd*)), c_v from the one-pass ones (|d rstd| / (u rstd* max(kappa, 1))).
+# Worst excess, and the case that set it: c_m 13.30 (mean_a of general-bf16: the bf16 general kernel at dim 512, a massive-head row - each
+# thread adds 64 deviations of -250 one after the other) -> 53.3; c_r 8.36 (rstd of bf16-1025x4096: 64 squares per lane in one chain) ->
+# 33.5; c_v 5.45 (rstd_a of general-bf16, massive-head, kappa 62) -> 21.9; c_y 2.58 (y of f32-1025x4096-add) -> 10.4; c_x 3.21 (dx of
+# f32-1025x2048) -> 12.9; c_p 2.02 (dgamma of f32-5x256; rows_reduce <= 1.40, gate_grad <= 0.27) -> 8.1.
+# The decode kernel's y: 1/2 ulp_T is taken at |y| + u |mean rstd| |g|, not at |y|.  The kernel forms x rs - mean rs, so the float32 value it
+# rounds to bf16 is off by up to u |mean rstd| |g| whatever |y| is, and may lie in the binade above y's: with 1/2 ulp_T(y) the restatement
+# itself is 1.4 % over at decode-dim128 (a const row, mean rstd = 1028, beta = 4.7e-4 just below 2^-11: error 4.196e-5, bound 4.139e-5).
+# Two conditions that are not measurements (tests/test_ln_cases.py asserts both): kappa <= 512 on every designed row of every block case
+# (largest: 192.4, head-off and massive-head- rows at dim 1536) and <= 2 on every row of at least four families; on every fp32 case
+# |rstd - rstd*| / rstd* <= TOL[float32]["out"] = 5e-6 whatever kappa is (the GPU test asserts that one on the device as well).
+# On the MI355X (worst error / bound per checker, the [elem] entries of an FF_TOL_REPORT run of tests/test_hip_layernorm_bounds.py):
+#   fp32: mean 0.121 (general-f32-bm64-reload), rstd 0.097 (general-f32-widest), y 0.246 (general-f32-multitile), dx 0.651 (f32-1025x4096-add: ln_bwd_dx_kernel),
+#   dgamma 0.328, dbeta 0.244, rows_reduce 0.194, gate_grad 0.011; the block kernels' mean_f 0.040, rstd_f 0.037, xn_f 0.216;
+#   bf16: mean 0.250, rstd 0.224 (both general-bf16: the restatement's worst case at the 1 / 4 the factor leaves), mean_f 0.038, rstd_f
+#   0.066 (phase3-dim1280), gate_grad 0.693; y, dx, dgamma, dbeta, rows_reduce 1.000: results on a rounding tie, where half a storage ulp is
+#   all of the error.  No device figure is above 1.  Relative rstd error of the bf16 one-pass kernels: up to 9.0e-6 (separate-ln-dim1536,
+#   a head-off row, kappa 184), 5.3e-6 in the bf16 general kernel (massive-head, kappa 62).
+# The fp32 defect (the one-pass general kernel with its 4-element shift): CONFIRMED on the device and fixed.  Before: rstd_a of
+# general-f32-widest (dim 1536) off by 1.647e-5 relative on a massive-head- row (kappa 192.4; the restatement: 1.70e-5, head-off 1.12e-5),
+# 2.72e-6 at dim 256, 1.26e-6 at dim 128 - above the 5e-6 the fp32 parity tests promise.  A 16-element shift would not have helped the
+# head-off rows (their first 16 columns ARE the shift: kappa stays 184), so the fp32 kernel now takes the variance by a second pass around
+# the mean (csrc/ff_xattn_fused.hip; the bf16 instantiations are unchanged).  After: 3.20e-7 at dim 1536 (massive-head), 1.58e-7 at dim
+# 256, 1.71e-7 at dim 128.  Worst |rstd - rstd*| / rstd* per family over the fp32 block cases, on the device, after the fix:
+#   plain 1.29e-7, offset+ 1.01e-7, offset- 1.06e-7, massive-head 3.20e-7, massive-head- 2.14e-7, massive-body 2.44e-7, massive-tail 1.09e-7,
+#   head-off 1.30e-7, const 5.5e-8, zero 5.5e-8, tiny-var 7.6e-8, big 9.3e-8, small 7.7e-8.
+# LN_CONSTANTS_BEGIN (tools/ln_c.py prints these lines)
+LN_C_M = 53.3
+LN_C_R = 33.5
+LN_C_V = 21.9
+LN_C_Y = 10.4
+LN_C_X = 12.9
+LN_C_P = 8.1
+# LN_CONSTANTS_END
+_LN_C = {"y": "LN_C_Y", "dx": "LN_C_X", "dgamma": "LN_C_P", "dbeta": "LN_C_P", "rows_reduce": "LN_C_P", "gate_grad": "LN_C_P"}
+
+
+def _ln_parts(what, ref, storage_dtype, decode=False):
+    """(fixed, scaled): the part of the bound that carries no constant and the terms one float32 rounding is proportional to"""
+    r, t = _t64(ref[what]), _t64(ref["t_" + what])
+    fixed = 0.5 * _ulp(r, storage_dtype)
+    if what == "y" and decode:      # the storage rounding is taken where the fp32 value may lie: |y| + u |mean rstd| |g| can be in the next binade
+        dec = 2.0 ** -24 * _t64(ref["t_y_dec"])
+        fixed = 0.5 * _ulp(r.abs() + dec, storage_dtype) + dec
+    if what == "dx":
+        if ref.get("residual") is not None:
+            fixed = fixed + 0.5 * _ulp(_t64(ref["residual"]), storage_dtype)
+        else:
+            fixed = torch.where(t == 0, torch.zeros_like(fixed), fixed)
+    return fixed, t
+
+
+def ln_bound_ok(what, got, ref, storage_dtype=torch.float32, c=None, decode=False):
+    """One output of a LayerNorm kernel (what = "mean", "rstd", "y", "dx", "dgamma", "dbeta", "rows_reduce", "gate_grad") against
+    ln_cases.ln_ref's dict (rows_reduce_ref's, gate_grad_ref's), element by element.  c: the constant (rstd: the pair (c_r, c_v)).
+    Returns (ok, worst error / bound, index of that element in the output's own shape)."""
+    u = 2.0 ** -24
+    if what == "mean":
+        bound = (LN_C_M if c is None else c) * u * _t64(ref["t_mean"])
+    elif what == "rstd":
+        cr, cv = (LN_C_R, LN_C_V) if c is None else c
+        bound = _t64(ref["rstd"]) * u * (cr + cv * _t64(ref["kappa"]))
+    else:
+        fixed, t = _ln_parts(what, ref, storage_dtype, decode)
+        bound = fixed + (globals()[_LN_C[what]] if c is None else c) * u * t
+    worst, i = _elem_ratio(got, ref[what], bound)
+    _report("elem", worst)
+    return worst <= 1.0, worst, tuple(int(x) for x in np.unravel_index(i, tuple(np.shape(ref[what]))))
+
+
+def ln_excess(what, got, ref, storage_dtype=torch.float32, decode=False):
+    """the quantity the constants bound: mean - |err| / (u t_mean); rstd - |err| / (u rstd* max(kappa, 1)); else (|err| - fixed) / (u terms)"""
+    if what == "mean":
+        return _excess(got, ref["mean"], ref["t_mean"], torch.zeros_like(_t64(ref["mean"])))
+    if what == "rstd":
+        return _excess(got, ref["rstd"], _t64(ref["rstd"]) * _t64(ref["kappa"]).clamp(min=1.0), torch.zeros_like(_t64(ref["rstd"])))
+    fixed, t = _ln_parts(what, ref, storage_dtype, decode)
+    return _excess(got, ref[what], t, fixed)
