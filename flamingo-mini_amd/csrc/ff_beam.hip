@@ -9,17 +9,18 @@
 //                      by SCORE even where two different logits round to one score.  A sequence's top 2 nb over nb V candidates lies in the
 //                      union of its rows' top 2 nb.
 //   beam_merge_kernel  one wave per sequence: ranks the nb x 2 nb candidates by counting (keys are integers: a total order whatever the
-//                      row held), then lane 0 walks the best 2 nb as the Python loop does and writes the state block.
+//                      row held), then lane 0 walks the best 2 nb as the Python loop does (beam_walk of ff_beam_walk.h, which every merge
+//                      calls - beam sampling's in ff_beam_sample.hip too) and writes the state block.
 // ff_group_beam_step (diverse beam search) is the same row pass and group_merge_kernel in place of beam_merge_kernel.
 // Every sum has a fixed order (thread-local in column order, xor butterfly in the wave, wave 0..3): equal inputs give equal bits.
 #include <cmath>
 
+#include "ff_beam_walk.h"
 #include "ff_row_keys.h"
 
 namespace ff {
 
 constexpr int kBeamScratch = 2304;            // n_gt[256] ints | n_eq[256] ints | red[16] words | cand score[16] | cand column[16]: the key image starts behind them
-constexpr int kBeamCand = 2 * FF_BEAM_MAX;    // candidates a row contributes at most
 
 // cand_score / cand_col: [rows][K], this row's best K candidates in no particular order (the merge ranks them)
 template <typename T, bool STAGED>
@@ -84,13 +85,6 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(int V, long long ld, con
     }
 }
 
-struct BeamState {
-    int b, nb, vocab, max_len, eos, pad, early_stopping;
-    float* score; int* done; int* n_hyp; float* hyp_score; int* hyp_len; int* hyp_row;
-    long long* hist_tok; int* hist_parent; float* hist_score; long long* next_tok; long long* beam_idx;
-    const float* len_norm; const long long* cur_len;
-};
-
 // one wave per sequence: rank the nb K candidates (score descending, beam then column ascending = flat index ascending, slot last), walk
 __global__ __launch_bounds__(64) void beam_merge_kernel(BeamState st, const float* __restrict__ cand_score, const int* __restrict__ cand_col) {
     __shared__ unsigned key[FF_BEAM_MAX * kBeamCand];
@@ -122,52 +116,9 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(BeamState st, const floa
     __syncthreads();
     if (tid != 0) return;
 
-    long long cur = *st.cur_len;
-    cur = cur < 1 ? 1 : (cur > st.max_len ? st.max_len : cur);                     // (a length outside the tables: no write leaves them)
-    const float norm = st.len_norm[cur];
-    float* hs = st.hyp_score + r0;
-    int* hl = st.hyp_len + r0;
-    int* hr = st.hyp_row + r0;
-    for (int k = 0; k < nb; k++) { ns[k] = -INFINITY; nt[k] = st.pad; np[k] = k; }
-    if (!st.done[s]) {
-        int nh = st.n_hyp[s];
-        nh = nh < 0 ? 0 : (nh > nb ? nb : nh);
-        int k = 0;
-        for (int rank = 0; rank < K && k < nb; rank++) {
-            const float v = top_s[rank];
-            const int beam = top_beam[rank], tok = top_col[rank];
-            if (st.eos >= 0 && tok == st.eos) {
-                if (rank < nb) {                                                     // a finished hypothesis: kept sorted, equal scores in arrival order
-                    const float h = v / norm;
-                    int p = 0;
-                    while (p < nh && hs[p] >= h) p++;
-                    if (p < nb) {
-                        for (int j = nh < nb - 1 ? nh : nb - 1; j > p; j--) { hs[j] = hs[j - 1]; hl[j] = hl[j - 1]; hr[j] = hr[j - 1]; }
-                        hs[p] = h; hl[p] = (int)cur; hr[p] = (int)r0 + beam;
-                        nh = nh < nb ? nh + 1 : nb;
-                    }
-                }
-                continue;
-            }
-            ns[k] = v; nt[k] = tok; np[k] = beam;
-            k++;
-        }
-        st.n_hyp[s] = nh;
-        if (nh >= nb) {
-            float best = ns[0];
-            for (int j = 1; j < nb; j++) best = fmaxf(best, ns[j]);
-            if (st.early_stopping || hs[nb - 1] >= best / norm) st.done[s] = 1;
-        }
-    }
-    const long long h0 = (cur - 1) * (long long)st.b * nb + r0;
-    for (int k = 0; k < nb; k++) {
-        st.score[r0 + k] = ns[k];
-        st.next_tok[r0 + k] = nt[k];
-        st.beam_idx[r0 + k] = r0 + np[k];
-        st.hist_tok[h0 + k] = nt[k];
-        st.hist_parent[h0 + k] = (int)r0 + np[k];
-        st.hist_score[h0 + k] = ns[k];
-    }
+    const long long cur = beam_cur_len(st);
+    beam_walk(st, s, nb, 0, r0, cur, st.len_norm[cur], top_s, top_beam, top_col, ns, nt, np);     // the walk all merges share (ff_beam_walk.h)
+    for (int k = 0; k < nb; k++) beam_store(st, r0, cur, k, ns, nt, np);
 }
 
 // Diverse beam search: one wave per sequence walks the G groups of gs = nb / G rows in order.  A group's penalty lowers at most nb - gs columns
@@ -192,8 +143,7 @@ __global__ __launch_bounds__(64) void group_merge_kernel(BeamState st, int G, fl
         int c = cand_col[r0 * K + j];
         col[j] = c < 0 ? 0 : (c >= st.vocab ? st.vocab - 1 : c);
     }
-    long long cur = *st.cur_len;
-    cur = cur < 1 ? 1 : (cur > st.max_len ? st.max_len : cur);                     // (a length outside the tables: no write leaves them)
+    const long long cur = beam_cur_len(st);
     const float norm = st.len_norm[cur];
     __syncthreads();
     for (int g = 0; g < G; g++) {
@@ -220,54 +170,12 @@ __global__ __launch_bounds__(64) void group_merge_kernel(BeamState st, int G, fl
         }
         __syncthreads();
         if (tid == 0) {
-            float* hs = st.hyp_score + r0 + b0;
-            int* hl = st.hyp_len + r0 + b0;
-            int* hr = st.hyp_row + r0 + b0;
-            const long long sg = (long long)s * G + g;
-            for (int k = 0; k < gs; k++) { ns[b0 + k] = -INFINITY; nt[b0 + k] = st.pad; np[b0 + k] = b0 + k; }
-            if (!st.done[sg]) {
-                int nh = st.n_hyp[sg];
-                nh = nh < 0 ? 0 : (nh > gs ? gs : nh);
-                int k = 0;
-                for (int rank = 0; rank < K2 && k < gs; rank++) {
-                    const float v = top_s[rank];
-                    const int beam = top_beam[rank], tok = top_col[rank];
-                    if (st.eos >= 0 && tok == st.eos) {
-                        if (rank < gs) {                                             // a finished hypothesis of this group: sorted, equal scores in arrival order
-                            const float h = v / norm;
-                            int p = 0;
-                            while (p < nh && hs[p] >= h) p++;
-                            if (p < gs) {
-                                for (int j = nh < gs - 1 ? nh : gs - 1; j > p; j--) { hs[j] = hs[j - 1]; hl[j] = hl[j - 1]; hr[j] = hr[j - 1]; }
-                                hs[p] = h; hl[p] = (int)cur; hr[p] = (int)r0 + b0 + beam;
-                                nh = nh < gs ? nh + 1 : gs;
-                            }
-                        }
-                        continue;
-                    }
-                    ns[b0 + k] = v; nt[b0 + k] = tok; np[b0 + k] = b0 + beam;
-                    k++;
-                }
-                st.n_hyp[sg] = nh;
-                if (nh >= gs) {
-                    float best = ns[b0];
-                    for (int j = 1; j < gs; j++) best = fmaxf(best, ns[b0 + j]);
-                    if (st.early_stopping || hs[gs - 1] >= best / norm) st.done[sg] = 1;
-                }
-            }
+            beam_walk(st, (long long)s * G + g, gs, b0, r0, cur, norm, top_s, top_beam, top_col, ns, nt, np);      // with nb = gs, on the group's rows
             for (int k = 0; k < gs; k++) live[b0 + k] = ns[b0 + k] > -INFINITY ? 1 : 0;      // (a NaN score counts nothing)
         }
         __syncthreads();
     }
-    const long long h0 = (cur - 1) * (long long)st.b * nb + r0;
-    if (tid < nb) {
-        st.score[r0 + tid] = ns[tid];
-        st.next_tok[r0 + tid] = nt[tid];
-        st.beam_idx[r0 + tid] = r0 + np[tid];
-        st.hist_tok[h0 + tid] = nt[tid];
-        st.hist_parent[h0 + tid] = (int)r0 + np[tid];
-        st.hist_score[h0 + tid] = ns[tid];
-    }
+    if (tid < nb) beam_store(st, r0, cur, tid, ns, nt, np);
 }
 
 template <typename T, bool STAGED>
@@ -342,16 +250,16 @@ extern "C" size_t ff_beam_workspace_bytes(int b, int nb) {
     return (size_t)b * nb * 2 * nb * (sizeof(float) + sizeof(int));
 }
 
-// the argument checks ff_beam_step and ff_group_beam_step share, under the caller's name
-static int beam_step_check(const char* fn, const ff_beam_desc* d, const void* logits, const long long* cur_len, void* workspace, size_t workspace_bytes) {
+// the argument checks every beam step shares, under the caller's name
+int ff::beam_step_check(const char* fn, const ff_beam_desc* d, const void* logits, const long long* cur_len, void* workspace, size_t workspace_bytes,
+                        size_t workspace_need) {
     FF_CHECK(d && logits && cur_len && workspace, FF_ERR_SHAPE, "%s: null descriptor, logits, cur_len or workspace", fn);
     FF_CHECK(d->score && d->done && d->n_hyp && d->hyp_score && d->hyp_len && d->hyp_row && d->hist_tok && d->hist_parent && d->hist_score &&
                  d->next_tok && d->beam_idx && d->len_norm, FF_ERR_SHAPE, "%s: null state pointer", fn);
     FF_CHECK(d->b > 0 && d->nb >= 1 && d->nb <= FF_BEAM_MAX, FF_ERR_SHAPE, "%s: b %d, nb %d (need b > 0, 1 <= nb <= %d)", fn, d->b, d->nb, FF_BEAM_MAX);
     FF_CHECK(d->vocab >= 2 * d->nb && d->ld >= d->vocab, FF_ERR_SHAPE, "%s: vocab %d, ld %lld (need vocab >= 2 nb = %d, ld >= vocab)", fn, d->vocab, d->ld, 2 * d->nb);
     FF_CHECK(d->max_len >= 1 && (long long)d->b * d->nb <= 0x7FFFFFFF / (2 * FF_BEAM_MAX), FF_ERR_SHAPE, "%s: max_len %d, %d x %d rows", fn, d->max_len, d->b, d->nb);
-    FF_CHECK(workspace_bytes >= ff_beam_workspace_bytes(d->b, d->nb), FF_ERR_SHAPE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes,
-             ff_beam_workspace_bytes(d->b, d->nb));
+    FF_CHECK(workspace_bytes >= workspace_need, FF_ERR_SHAPE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, workspace_need);
     FF_CHECK(d->dtype == FF_DTYPE_F32 || d->dtype == FF_DTYPE_BF16, FF_ERR_UNSUPPORTED, "%s: dtype %d", fn, d->dtype);
     return FF_OK;
 }
@@ -379,13 +287,13 @@ static int beam_step_launch(const ff_beam_desc* d, int n_groups, float diversity
 
 extern "C" int ff_beam_step(const ff_beam_desc* d, const void* logits, const long long* cur_len, void* workspace, size_t workspace_bytes,
                             ff_stream_t stream) {
-    FF_TRY(beam_step_check("ff_beam_step", d, logits, cur_len, workspace, workspace_bytes));
+    FF_TRY(ff::beam_step_check("ff_beam_step", d, logits, cur_len, workspace, workspace_bytes, d ? ff_beam_workspace_bytes(d->b, d->nb) : 0));
     return beam_step_launch(d, 1, 0.f, logits, cur_len, workspace, stream);
 }
 
 extern "C" int ff_group_beam_step(const ff_beam_desc* d, int n_groups, float diversity_penalty, const void* logits, const long long* cur_len,
                                   void* workspace, size_t workspace_bytes, ff_stream_t stream) {
-    FF_TRY(beam_step_check("ff_group_beam_step", d, logits, cur_len, workspace, workspace_bytes));
+    FF_TRY(ff::beam_step_check("ff_group_beam_step", d, logits, cur_len, workspace, workspace_bytes, d ? ff_beam_workspace_bytes(d->b, d->nb) : 0));
     FF_CHECK(n_groups >= 1 && d->nb % n_groups == 0, FF_ERR_SHAPE, "ff_group_beam_step: n_groups %d (need n_groups >= 1 and nb %d a multiple of it)", n_groups, d->nb);
     FF_CHECK(diversity_penalty >= 0.f && std::isfinite(diversity_penalty), FF_ERR_SHAPE, "ff_group_beam_step: diversity_penalty %g (need a finite value >= 0)",
              (double)diversity_penalty);

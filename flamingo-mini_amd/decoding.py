@@ -276,7 +276,7 @@ def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
 
 
 def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_family, L0, max_length, ids_is_int64, procs_on, procs_given=(),
-          logprobs_on=False, constraints_on=False, vocab=0, table_entries=0, guidance_on=False):
+          logprobs_on=False, constraints_on=False, vocab=0, table_entries=0, guidance_on=False, beam_sample_on=False):
     """Which path a generate() call takes: "static" (a _DecodeSession) or "dynamic" (dynamic_decode / beam_search), from plain values only.
     `static_decode` is generate()'s argument (None, True, False), `model_default` the model's attribute, `procs_given` the processor
     arguments' names for the TypeError on CPU tensors.  Greedy decoding takes the static path by default on the GPU; sampling and beam search
@@ -286,7 +286,11 @@ def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_fam
     the same on CPU tensors - the dynamic loops restate them on the host - and take the static path under the processors' conditions
     plus the kernel's vocabulary cap and the sessions' table cap.  Guidance (`guidance_on`) routes like the log-probabilities: its kernel has
     no CPU form but its torch restatement has one, so CPU tensors take the dynamic loop unless static_decode=True asks for what cannot be
-    had; guided greedy decoding is static by default on the GPU, guided sampling and beam search on request."""
+    had; guided greedy decoding is static by default on the GPU, guided sampling and beam search on request.
+    `do_sample` here means TOKEN sampling (one token per row from its own distribution): together with num_beams > 1 it raises, as it always
+    has.  Beam sampling (generate(num_beams > 1, do_sample=True)) is a beam search whose selection draws: generate() asks for it with
+    do_sample=False and `beam_sample_on=True`, and it routes exactly like beam search - static only with static_decode=True, which on CPU
+    tensors raises what ffi.require_cuda raises (its kernel has no CPU form), otherwise the dynamic loop, which also runs on CPU tensors."""
     def need_gpu():                     # what ffi.require_cuda raises for a CPU tensor
         if not is_cuda:
             F.ffi.require_cuda(torch.empty(0))
@@ -297,7 +301,7 @@ def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_fam
         raise TypeError(f"generate(): unsupported generation arguments {list(procs_given)} on CPU tensors (the logits processors run on the GPU only)")
     if num_beams > 1 and do_sample:
         raise ValueError("beam search with sampling is not implemented")
-    on_request = num_beams > 1 or do_sample                                   # static only when static_decode=True is passed
+    on_request = num_beams > 1 or do_sample or beam_sample_on                 # static only when static_decode=True is passed
     if (on_request or logprobs_on or constraints_on or guidance_on) and static_decode:
         need_gpu()
     if static_decode is None:
@@ -351,6 +355,55 @@ def truncate_logits_torch(logits, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, 
         eta = torch.clamp(eta_cutoff ** 0.5 * (-entropy(lp)).exp(), max=eta_cutoff)
         logits = logits.masked_fill((lp.exp() < eta) & (logits < top(logits)), ninf)
     return logits
+
+
+def gumbel_noise_torch(shape, generator=None, device=None):
+    """Standard Gumbel noise as rule S4 of ff_beam_sample_step forms it from a uniform number: u on the 23-bit grid ((k + 0.5) 2^-23, k <
+    2^23: strictly inside (0, 1)), g = -log(-log(u)) - with the uniform numbers from torch.rand(generator=), not from the kernel's Philox."""
+    u = (torch.rand(shape, generator=generator, device=device, dtype=torch.float32) * 2.0 ** 23).floor().add_(0.5).mul_(2.0 ** -23)
+    return -(-u.log()).log()
+
+
+def beam_sample_select_torch(logits, score, g, nb, temperature=1.0, top_k=0, top_p=1.0):
+    """Rules S1 - S5 of ff_beam_sample_step (include/flamingo_fusion.h) in torch, on tensors of any device: `logits` (b * nb, V), `score`
+    (b, nb) the beams' running scores, `g` (b * nb, V) the noise.  Per row: lse and logp = x - lse; top-k by value (ties kept) and the nucleus
+    over softmax(logp / T) within it (equal values stay or go together, the maximum stays); z = logp / T where kept, -inf elsewhere, nothing
+    renormalised; a = z + score; p = a + g.  Per sequence the 2 nb largest p, by p descending, then flat index ascending - a Gumbel top-k: a
+    draw of 2 nb continuations without replacement from softmax(a).  The math is float32, float64 for float64 logits.
+    Returns (a, beam, token), each (b, 2 nb), in the order of p."""
+    dt = torch.float64 if logits.dtype == torch.float64 else torch.float32
+    x = logits.to(dt)
+    rows, V = x.shape
+    b, ninf = rows // nb, float("-inf")
+    m = x.amax(-1, keepdim=True)
+    logp = x - (m + (x - m).exp().sum(-1, keepdim=True).log())
+    keep = torch.ones_like(x, dtype=torch.bool)
+    if 0 < top_k < V:
+        keep = x >= x.topk(top_k, dim=-1).values[..., -1:]
+    if top_p < 1.0:
+        keep = keep & (x > ninf)
+        srt, idx = x.masked_fill(~keep, ninf).sort(-1, descending=True)
+        w = torch.where(srt > ninf, ((srt - m) * (1.0 / temperature)).exp(), torch.zeros_like(srt))
+        before = w.cumsum(-1) - w                                           # the mass sorted in front of a column ...
+        first = torch.ones_like(keep)
+        first[..., 1:] = srt[..., 1:] != srt[..., :-1]
+        above = torch.where(first, before, torch.zeros_like(before)).cummax(-1).values      # ... of STRICTLY larger values: that of its run's first
+        drop = above >= top_p * w.sum(-1, keepdim=True)
+        keep = keep & ~torch.zeros_like(keep).scatter(-1, idx, drop)
+    z = logp if temperature == 1.0 else logp / temperature
+    a = (torch.where(keep, z, torch.full_like(z, ninf)) + score.to(dt).reshape(-1, 1)).reshape(b, nb * V)
+    p = a + g.to(dt).reshape(b, nb * V)
+    flat = p.sort(dim=-1, descending=True, stable=True).indices[:, :2 * nb]    # (a stable sort: the lower flat index on equal p)
+    return a.gather(-1, flat), flat // V, flat % V
+
+
+def order_by_score(a, beam, token, V):
+    """Rule S6: the drawn candidates ordered by accumulated score descending, then flat index ascending.  Returns (a, flat index)."""
+    flat = beam * V + token
+    o = flat.argsort(dim=-1, stable=True)
+    a, flat = a.gather(-1, o), flat.gather(-1, o)
+    o = a.argsort(dim=-1, descending=True, stable=True)
+    return a.gather(-1, o), flat.gather(-1, o)
 
 
 def process_logits(logits, seqs, repetition_penalty, no_repeat_ngram_size, eos, min_len):
@@ -788,7 +841,12 @@ class _BeamSession(_DecodeSession):
     it was.  A session without groups calls beam_step.
     Under `guidance` the LM cache is 2 b * nb rows and is gathered with a preallocated doubled index (beam_idx, then beam_idx + b * nb,
     filled inside the step): ff_beam_gather maps within each run of nb rows, so the unconditional half follows its beams; seq_buf and the
-    state block stay b * nb rows."""
+    state block stay b * nb rows.
+    `sampling` (a Sampling, beside `beams`) makes it BEAM SAMPLING: _select calls functional.beam_sample_step - the selection draws 2 nb
+    continuations per sequence by a Gumbel top-k whose noise is a function of (seed, cur_len, row, column), recomputed inside the kernel -
+    with temperature / top_k / top_p as launch constants and `seed`, a device int64 that _begin fills from the call's generator with one
+    torch.randint outside the capture.  Eager and replayed steps therefore draw the same numbers; everything else - the gathers, seq_buf,
+    the processors, the constraints, guidance - is what it was.  A session without sampling holds no seed and calls beam_step."""
 
     def __init__(self, model, b, *args, beams, **kw):
         self.nb = beams.nb
@@ -802,6 +860,8 @@ class _BeamSession(_DecodeSession):
         self.lm_tensors = None                                                # keys / values of every StaticCache layer (allocated by the first prompt step)
         if self.processors is not None:
             self._alloc_min_len()
+        if self.sampling is not None:
+            self.seed = torch.zeros((1,), dtype=torch.long, device=dev)      # what the step's noise is a function of, beside cur_len, row and column
         if self.guidance:
             self.lm_beam_idx = torch.zeros((2 * self.b,), dtype=torch.long, device=dev)      # beam_idx, then beam_idx + R: the unconditional half follows
         if self.processors is not None or self.constraints is not None:
@@ -814,6 +874,8 @@ class _BeamSession(_DecodeSession):
         if visual_features is not None:
             visual_features = _repeat_leading(visual_features, self.nb)
         self.state.reset()
+        if self.sampling is not None:                                         # one draw per call, outside any capture: the replayed step only reads it
+            self.seed.copy_(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator, device=ids.device, dtype=torch.long))
         if self.processors is not None:
             self.min_len.fill_(self.processors.min_len(ids.shape[1]))
         if hasattr(self, "seq_buf"):
@@ -828,7 +890,9 @@ class _BeamSession(_DecodeSession):
         if self.lm_tensors is None:
             self.lm_tensors = [t for layer in self.cache.layers for t in (layer.keys, layer.values)]
         torch.add(self.pos, 1, out=self.cur_len)
-        if self.groups is None:
+        if self.sampling is not None:
+            nxt, beam_idx = F.beam_sample_step(logits, self.state, self.cur_len, self.seed, *self.sampling)
+        elif self.groups is None:
             nxt, beam_idx = F.beam_step(logits, self.state, self.cur_len)
         else:
             nxt, beam_idx = F.group_beam_step(logits, self.state, self.cur_len, self.groups.diversity_penalty)
@@ -868,7 +932,9 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
     a device scalar the captured step reads - a sweep over scales replays one graph.  A call without it builds the key it always built.
     `truncation` (a Truncation, with `sampling`) selects a session that samples under min_p / typical_p / epsilon_cutoff / eta_cutoff: its
     key ends with the Truncation - the values are launch constants of the captured step, like the Groups.  A call without it builds the key it
-    always built."""
+    always built.
+    `sampling` TOGETHER with `beams` selects a beam-sampling session (a _BeamSession whose selection draws): the key's own `sampling` and
+    `beams` elements tell it from both, nothing is appended."""
     b = ids.shape[0]
     graph = ids.is_cuda and not model.training and model.decode_graph
     sessions = _DECODE_SESSIONS.setdefault(model, {})
@@ -935,7 +1001,7 @@ def dynamic_decode(step, ids, ml, am, pixel_values, visual_features, max_length,
 
 
 def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None,
-                n_return=None, constraints=None, groups=None):
+                n_return=None, constraints=None, groups=None, sampling=None, generator=None, noise=None):
     """Standard beam search over the cached decode path; `step` / `reorder_cache` are FlamingoModel._decode_step / ._reorder_cache.  The
     prompt runs once per sequence; its caches are then replicated per beam (xattn K/V: repeat_interleave; LM cache:
     Cache.batch_repeat_interleave) and re-ordered every step.  `processors` act on every step's logits before the log-softmax.
@@ -945,12 +1011,17 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
     nb beams are G groups of gs, inside a step the groups are searched in order, and a group's candidates pay the penalty for every live next
     beam of an earlier group that carries their token (the product and the difference rounded in float32); each group has its own
     hypotheses and done flag, and the tail ranks all groups' entries together.  It also runs on CPU tensors.  Without groups nothing
-    changes: one group of nb beams, the same topk, the same calls."""
+    changes: one group of nb beams, the same topk, the same calls.
+    With `sampling` (a Sampling; not with groups) it is BEAM SAMPLING, rules S1 - S6 of ff_beam_sample_step restated in torch
+    (beam_sample_select_torch, order_by_score): every step draws its 2 nb candidates without replacement by a Gumbel top-k on the warped,
+    accumulated scores, with noise from gumbel_noise_torch(generator=) - a different stream than the static path's Philox, as with token
+    sampling - or, for tests, from `noise(rows, V, cur_len)`.  It also runs on CPU tensors.  Without sampling nothing changes."""
     b, L0 = ids.shape
     dev = ids.device
     process = _dynamic_processor(processors, eos, L0, constraints)
     logits, past = step(ids, ml, am, None, pixel_values, visual_features)
-    logp = process(logits, ids).log_softmax(-1)
+    x = process(logits, ids)
+    logp = x.log_softmax(-1)
     V = logp.shape[-1]
     xattn_past, lm_past = past
     xattn_past = tuple(tuple(_repeat_leading(t, nb) for t in kv) for kv in xattn_past)
@@ -966,6 +1037,7 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
     scores = torch.full((b, nb), float("-inf"), device=dev)
     scores[:, ::gs] = 0.0                                             # all beams of a group start identical: only one may branch
     logp = _repeat_leading(logp, nb)
+    x = _repeat_leading(x, nb) if sampling is not None else None      # the processed logits: what rule S1 starts from
     done_hyps = [[[] for _ in range(G)] for _ in range(b)]            # (normalised score, token list) per sequence and group
     is_done = [[False] * G for _ in range(b)]
     while True:
@@ -974,7 +1046,11 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
         next_scores = torch.full((b, nb), float("-inf"), device=dev)
         next_tok = torch.full((b, nb), pad if pad is not None else 0, dtype=torch.long, device=dev)
         next_src = torch.arange(nb, device=dev).repeat(b, 1)
-        if groups is None:
+        if sampling is not None:
+            g = noise(b * nb, V, cur_len) if noise is not None else gumbel_noise_torch((b * nb, V), generator, dev)
+            top_s, top_i = order_by_score(*beam_sample_select_torch(x, scores, g, nb, *sampling), V)
+            top_s_c, top_i_c = top_s.to(torch.float32).cpu(), top_i.cpu()
+        elif groups is None:
             top_s, top_i = cand.topk(2 * nb, dim=-1)
             top_s_c, top_i_c = top_s.cpu(), top_i.cpu()
         else:
@@ -1020,7 +1096,8 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
         ml = torch.cat([ml, torch.zeros_like(ml[:, :1])], dim=1)
         am = torch.cat([am, torch.ones_like(am[:, :1])], dim=1)
         logits, past = step(seqs[:, -1:], ml, am, past, None, None)
-        logp = process(logits, seqs).log_softmax(-1)
+        x = process(logits, seqs)
+        logp = x.log_softmax(-1)
     out, out_scores = [], []
     for bi in range(b):
         hyps = []

@@ -176,6 +176,9 @@ _SIGNATURES = {
     "ff_beam_step": (_I, [C.POINTER(BeamDesc), _P, _P, _P, _SZ, _P]),
     "ff_beam_gather": (_I, [_I, _P, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P, _P]),
     "ff_group_beam_step": (_I, [C.POINTER(BeamDesc), _I, C.c_float, _P, _P, _P, _SZ, _P]),
+    "ff_beam_sample_workspace_bytes": (_SZ, [_I, _I]),
+    "ff_beam_sample_step": (_I, [C.POINTER(BeamDesc), C.c_float, _I, C.c_float, _P, _P, _P, _P, _SZ, _P]),
+    "ff_beam_sample_noise": (_I, [_I, _I, _P, _P, _P, _P]),
     "ff_logits_process": (_I, [_I, _I, _I, C.c_longlong, _P, _P, C.c_longlong, C.c_longlong, _P, C.c_float, _I, _I, _P, _P]),
     "ff_token_logprob": (_I, [_I, _I, _I, C.c_longlong, _P, _P, _P, _P, _P, _P]),
     "ff_logprob_gather": (_I, [_I, _I, _I, C.c_longlong, _P, _P, _P, _I, _P, _P, _P]),

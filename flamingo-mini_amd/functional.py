@@ -1177,7 +1177,8 @@ class BeamState:
         self.storage = storage[:total]
         for name, shape, dt, off, nbytes in fields:
             setattr(self, name, self.storage[off:off + nbytes].view(dt).view(shape))
-        self.workspace = _new((max(int(ffi.lib().ff_beam_workspace_bytes(b, nb)), 16),), torch.uint8, storage.device)
+        # one workspace serves every step of this block: beam_sample_step's candidates carry (p, a, column), the others (score, column)
+        self.workspace = _new((max(int(ffi.lib().ff_beam_workspace_bytes(b, nb)), int(ffi.lib().ff_beam_sample_workspace_bytes(b, nb)), 16),), torch.uint8, storage.device)
         self.reset()
 
     def reset(self) -> None:
@@ -1239,6 +1240,50 @@ def group_beam_step(logits: torch.Tensor, state: BeamState, cur_len: torch.Tenso
     ffi.check(ffi.lib().ff_group_beam_step(d, state.n_groups, lam, logits.data_ptr(), cur_len.data_ptr(), state.workspace.data_ptr(), state.workspace.numel(),
                                            ffi.stream_handle(logits.device)), "ff_group_beam_step")
     return state.next_tok, state.beam_idx
+
+
+def _seed_scalar(fn: str, seed: torch.Tensor) -> None:
+    if seed.dtype != torch.long or seed.numel() != 1:
+        raise ValueError(f"{fn}: seed must be one int64 value on the device, got {tuple(seed.shape)} {seed.dtype}")
+
+
+def beam_sample_step(logits: torch.Tensor, state: BeamState, cur_len: torch.Tensor, seed: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
+                     top_p: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One beam-SAMPLING selection: beam_step with the "2 nb best" replaced by a draw of 2 nb continuations without replacement from the
+    softmax over each sequence's accumulated scores, after temperature / top-k / nucleus warping of every row's log-probabilities (rules
+    S1 - S6 of ff_beam_sample_step in include/flamingo_fusion.h: a Gumbel top-k).  `seed` is a one-element int64 device tensor; the noise
+    is a function of (seed, cur_len, row, column) alone, recomputed inside the kernel - no tensor of random numbers exists -, so the same
+    seed gives the same step, eager or replayed.  The three warper values are launch constants (ValueError for values ff_sample_token
+    rejects).  Two launches, nothing allocated, capturable.  Returns (state.next_tok, state.beam_idx)."""
+    d = _beam_desc("beam_sample_step", logits, state, cur_len)
+    ffi.require_cuda(seed)
+    _seed_scalar("beam_sample_step", seed)
+    if state.n_groups != 1:
+        raise ValueError(f"beam_sample_step: the state has {state.n_groups} groups (beam sampling has none)")
+    t, k, p = float(temperature), int(top_k), float(top_p)
+    if not (0.0 < t < float("inf")) or k < 0 or not (0.0 < p <= 1.0):
+        raise ValueError(f"beam_sample_step: temperature {temperature!r} must be positive and finite, top_k {top_k!r} >= 0, top_p {top_p!r} in (0, 1]")
+    ffi.check(ffi.lib().ff_beam_sample_step(d, t, k, p, seed.data_ptr(), logits.data_ptr(), cur_len.data_ptr(), state.workspace.data_ptr(), state.workspace.numel(),
+                                            ffi.stream_handle(logits.device)), "ff_beam_sample_step")
+    return state.next_tok, state.beam_idx
+
+
+def beam_sample_noise(rows: int, vocab: int, seed: torch.Tensor, cur_len: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The Gumbel noise g of rule S4 that beam_sample_step adds at (row, column) for this `seed` and `cur_len` (one-element int64 device
+    tensors), as a (rows, vocab) float32 tensor: ff_beam_sample_noise, one launch.  What ties the kernel's draw to a restatement - feed it to
+    decoding.beam_sample_select_torch and the selection is the kernel's."""
+    ffi.require_cuda(seed, cur_len)
+    _seed_scalar("beam_sample_noise", seed)
+    if cur_len.dtype != torch.long or cur_len.numel() != 1:
+        raise ValueError(f"beam_sample_noise: cur_len must be one int64 value on the device, got {tuple(cur_len.shape)} {cur_len.dtype}")
+    if not (0 < rows <= 65535 and vocab > 0):
+        raise ValueError(f"beam_sample_noise: rows {rows} (1 .. 65535), vocab {vocab} (> 0)")
+    if out is None:
+        out = _new((rows, vocab), torch.float32, seed.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, vocab) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"beam_sample_noise: out must be a contiguous ({rows}, {vocab}) float32 tensor on the device")
+    ffi.check(ffi.lib().ff_beam_sample_noise(rows, vocab, seed.data_ptr(), cur_len.data_ptr(), out.data_ptr(), ffi.stream_handle(seed.device)), "ff_beam_sample_noise")
+    return out
 
 
 def beam_gather(tensors: Sequence[torch.Tensor], beam_idx: torch.Tensor, n_pos: torch.Tensor, nb: int) -> None:

@@ -528,7 +528,21 @@ class FlamingoModel(PreTrainedModel):
         static session (the rules and the draw are one launch inside the replayed step, functional.sample_tokens; the values are launch
         constants and part of the session key) only with static_decode=True, otherwise the dynamic loop with
         decoding.truncate_logits_torch, which also runs on CPU tensors.  token_logprobs stay the log-softmax before temperature and every
-        filter.  Not offered: min_tokens_to_keep > 1, per-row values, truncation for beam sampling."""
+        filter.  Not offered: min_tokens_to_keep > 1, per-row values, the four truncation samplers under beam sampling.
+        Beam sampling (transformers' beam-sample): `do_sample=True` with `num_beams > 1` is beam search whose every step DRAWS its 2 *
+        num_beams candidates instead of taking the best: temperature, top_k and top_p warp each beam's log-probabilities (nothing is
+        renormalised, as in transformers), the beam's running score is added, and 2 * num_beams continuations are drawn without replacement
+        from the softmax over the sequence's num_beams * vocab accumulated scores - a Gumbel top-k, the Plackett-Luce law of
+        torch.multinomial(replacement=False) -; the drawn ones are sorted by accumulated score and walked as in beam search.  It returns
+        several distinct, reasonably likely sequences, each with its score: num_return_sequences, sequences_scores, the processors,
+        candidate_ids, bad_words_ids and guidance_scale compose as with beam search.  The exact rules are S1 - S6 of ff_beam_sample_step in
+        include/flamingo_fusion.h.  Routing is that of beam search: the static session (functional.beam_sample_step inside the replayed
+        step; the noise is a function of a per-call seed drawn from `generator`, the step's length, the row and the column, so no random
+        tensor exists and eager and replayed steps agree; num_beams <= 8) only with static_decode=True, otherwise the dynamic loop
+        (decoding.beam_sample_select_torch), which also runs on CPU tensors.  As with token sampling the two paths draw DIFFERENT streams
+        from one seed; each is reproducible per `generator`.  Known and accepted: with top_k < 2 * num_beams the first step has fewer
+        finite candidates than it draws and the missing beams are dead.  num_beam_groups > 1, min_p / typical_p / epsilon_cutoff /
+        eta_cutoff and output_logprobs keep their ValueErrors under beam sampling."""
         procs = D.check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos_token_id)
         n_ret = D.check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample)
         groups = D.check_group_args(num_beam_groups, diversity_penalty, num_beams, do_sample)
@@ -544,9 +558,14 @@ class FlamingoModel(PreTrainedModel):
         am = attention_mask if attention_mask is not None else torch.ones_like(ids)
         ml = media_locations
         pad = pad_token_id if pad_token_id is not None else eos_token_id
-        path = D.route(is_cuda=ids.is_cuda, num_beams=num_beams, do_sample=do_sample, static_decode=static_decode, model_default=self.static_decode, lm_family=self.flamingo.lm_family,
+        beam_sample = bool(do_sample) and num_beams > 1                      # a beam search whose selection draws: route() sees it as one
+        if beam_sample and not (0 < temperature < float("inf") and top_k >= 0 and 0 < top_p <= 1):
+            raise ValueError(f"generate(): beam sampling needs a positive, finite temperature, top_k >= 0 and top_p in (0, 1], got {temperature!r}, {top_k!r}, {top_p!r}")
+        skw = dict(sampling=D.Sampling(float(temperature), int(top_k), float(top_p)), generator=generator) if beam_sample else {}
+        path = D.route(is_cuda=ids.is_cuda, num_beams=num_beams, do_sample=do_sample and not beam_sample, static_decode=static_decode, model_default=self.static_decode, lm_family=self.flamingo.lm_family,
                        L0=ids.shape[1], max_length=max_length, ids_is_int64=ids.dtype == torch.long, procs_on=procs is not None, procs_given=procs.given() if procs is not None else (),
-                       logprobs_on=bool(output_logprobs), **rkw, **({} if guidance is None else {"guidance_on": True}))
+                       logprobs_on=bool(output_logprobs), **rkw, **({} if guidance is None else {"guidance_on": True}),
+                       **({"beam_sample_on": True} if beam_sample else {}))
         if n_ret > 1 and num_beams <= 1:                                     # sampling: every sequence n times, its visuals encoded once
             if visual_features is None and pixel_values is not None:
                 visual_features, pixel_values = self.flamingo.encode_resample_visuals(pixel_values), None
@@ -569,7 +588,7 @@ class FlamingoModel(PreTrainedModel):
                                    logprobs=bool(output_logprobs), n_return=n_beams_out, **ckw, **gkw, **tkw)
         elif num_beams > 1:
             res = self._beam_search(ids, ml, am, pixel_values, visual_features, max_length, num_beams, eos_token_id, pad, early_stopping, length_penalty, processors=procs,
-                                    n_return=n_beams_out, **ckw, **gkw, **({} if guidance is None else {"step": step, "reorder_cache": reorder}))
+                                    n_return=n_beams_out, **ckw, **gkw, **skw, **({} if guidance is None else {"step": step, "reorder_cache": reorder}))
         else:
             # the log-softmax is taken in float32, the dtype of the logits _decode_step hands the loop; a model that computes in float64 keeps
             # its precision (a float32 log-softmax would throw away what a float64 evaluation on the host is run for)
@@ -595,8 +614,8 @@ class FlamingoModel(PreTrainedModel):
 
     def _beam_search(self, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors=None, n_return=None,
                      step=None, reorder_cache=None, **constraints):
-        """The dynamic beam search (decoding.beam_search) over this model's _decode_step / _reorder_cache; `constraints=` and `groups=` travel
-        as keywords and only when given, and so do `step=` / `reorder_cache=`, the guided wrappers of the two (decoding.guided_step)."""
+        """The dynamic beam search (decoding.beam_search) over this model's _decode_step / _reorder_cache; `constraints=`, `groups=` and
+        `sampling=` / `generator=` (beam sampling) travel as keywords and only when given, and so do `step=` / `reorder_cache=`, the guided wrappers of the two (decoding.guided_step)."""
         return D.beam_search(step or self._decode_step, reorder_cache or self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, nb, eos, pad, early_stopping, length_penalty, processors,
                              n_return=n_return, **constraints)
 

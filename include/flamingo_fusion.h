@@ -60,7 +60,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, addition only: diverse beam search on the captured decode step, ff_group_beam_step;
                                 * still 6, addition only: classifier-free guidance on the captured decode step, ff_guided_logits;
                                 * still 6, addition only: truncation samplers (min_p, typical_p, epsilon / eta cutoff), ff_sample_token_truncated;
-                                * still 6, addition only: exact closed-set scoring over a candidate trie, ff_logprob_gather) */
+                                * still 6, addition only: exact closed-set scoring over a candidate trie, ff_logprob_gather;
+                                * still 6, additions only: beam sampling on the captured decode step, ff_beam_sample_step, ff_beam_sample_noise) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -683,6 +684,45 @@ int ff_beam_gather(int n_tensors, void* const* tensors, int elem_size, int b, in
  * ------------------------------------------------------------------------------------------------------ */
 int ff_group_beam_step(const ff_beam_desc* d, int n_groups, float diversity_penalty, const void* logits, const long long* cur_len,
                        void* workspace, size_t workspace_bytes, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Beam sampling (transformers' beam-sample: num_beams > 1 with do_sample) on the captured decode step (added under ABI 6):
+ * ff_beam_sample_step is ff_beam_step with its rule 4 replaced by a DRAW.  As in current transformers (_get_top_k_continuations) the warpers
+ * act on each row's log-probabilities, the beam's running score is added, 2 nb continuations are drawn WITHOUT replacement from the softmax
+ * over the sequence's nb * vocab accumulated scores, and the drawn ones are sorted by accumulated score and walked as in plain beam search.
+ * The draw is a Gumbel top-k: the 2 nb largest values of a + g, g i.i.d. standard Gumbel noise, have exactly the law of
+ * torch.multinomial(softmax(a), 2 nb, replacement=False) - the Plackett-Luce law (Kool et al., "Stochastic Beams and Where to Find Them",
+ * 2019, section 3).  ff_beam_desc, the state block and its initialisation are those of ff_beam_step.  seed: a device int64.
+ * Per sequence s, row r = s * nb + k, x the logits as stored:
+ *  S1. lse_r and logp_v = x_v - lse_r, exactly as rules 1 - 2 of ff_beam_step.
+ *  S2. the warpers, per row, in transformers' order, by the value rules of ff_sample_token: K = its rule 1 (top-k by value, ties all kept),
+ *      P = its rule 3 (the nucleus over q = softmax(logp / T) within K; equal values stay or go together, the maximum always stays);
+ *      z_v = logp_v / T for v in P, -inf otherwise, rounded once.  Nothing is renormalised, as in transformers.  With T = 1, top_k = 0 and
+ *      top_p = 1, z_v is logp_v bit for bit.
+ *  S3. a(k, v) = fl(z_v + score[s][k]).  With the warpers off this is ff_beam_step's candidate score, bit for bit.
+ *  S4. the noise: w = word v & 3 of Philox4x32-7 (Random123's round function, 7 rounds) with key (seed low 32 bits, seed high 32 bits) and
+ *      counter (v >> 2, r, (unsigned)*cur_len, 0x42534D50);  u = ((w >> 9) + 0.5) * 2^-23, exact in fp32 and inside [2^-24, 1 - 2^-24];
+ *      g = -logf(-logf(u)).  Nothing of the launch geometry enters: eager and replayed steps draw the same numbers whatever the grid.
+ *  S5. p(k, v) = fl(a + g).  The sequence's candidates are the 2 nb largest p, ordered by p descending, then by flat index k * vocab + v
+ *      ascending.  A candidate with a = -inf (a filtered token, a dead beam, a masked logit) has p = -inf and is taken only if fewer finite
+ *      ones exist (rule 5), lowest flat index first.
+ *  S6. the 2 nb candidates are ordered by a descending, then by flat index ascending, and rules 6 - 9 of ff_beam_step apply to them
+ *      unchanged: hypotheses, done, the history tables, next_tok, beam_idx.  Running and hypothesis scores are a, never p.
+ * Known and accepted: with top_k < 2 nb the first step has fewer than 2 nb finite candidates and the missing beams are dead.  The law of the
+ * draw is truncated at |g| ~ 16.6 (the 23-bit grid of u), which has probability about 6e-8 per entry.
+ * Capturable: two launches, no allocation, no host synchronisation, no global atomics, a fixed order - equal inputs and an equal seed give
+ * equal bits.  temperature, top_k and top_p are launch constants.  workspace: ff_beam_sample_workspace_bytes(b, nb) bytes (0 for arguments
+ * the step rejects).  After the call it holds what the rows handed the merge, for inspection: p [b * nb][2 nb] fp32, then a [b * nb][2 nb]
+ * fp32, then the column [b * nb][2 nb] int32 - each row's best 2 nb candidates by (p, column); with nb = 1 that is the sequence's draw.
+ * ff_beam_sample_noise writes g of rule S4 for rows 0 .. rows - 1 and columns 0 .. vocab - 1 into a (rows, vocab) fp32 buffer, rows <= 65535:
+ * the hook that ties the kernels' noise to a restatement.
+ * FF_ERR_SHAPE: everything ff_beam_step rejects; temperature, top_k, top_p as ff_sample_token rejects them; a null seed.
+ * FF_ERR_UNSUPPORTED: other dtypes.
+ * ------------------------------------------------------------------------------------------------------ */
+size_t ff_beam_sample_workspace_bytes(int b, int nb);
+int ff_beam_sample_step(const ff_beam_desc* d, float temperature, int top_k, float top_p, const long long* seed, const void* logits,
+                        const long long* cur_len, void* workspace, size_t workspace_bytes, ff_stream_t stream);
+int ff_beam_sample_noise(int rows, int vocab, const long long* seed, const long long* cur_len, float* g, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Logits processors on the captured decode step (added under ABI 6): repetition penalty, no-repeat n-gram ban and minimum length, applied
