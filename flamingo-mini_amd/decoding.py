@@ -20,6 +20,8 @@ Beams = NamedTuple("Beams", [("nb", int), ("early_stopping", bool), ("length_pen
 Groups = NamedTuple("Groups", [("n", int), ("diversity_penalty", float)])      # diverse beam search: beside Beams, which keeps its three fields
 # the truncation samplers: beside Sampling, which keeps its three fields
 Truncation = NamedTuple("Truncation", [("min_p", float), ("typical_p", float), ("epsilon_cutoff", float), ("eta_cutoff", float)])
+# contrastive search: k candidates per sequence and step (a session's shape: part of its key), alpha (a device scalar of the session: not part of it)
+Contrastive = NamedTuple("Contrastive", [("k", int), ("penalty_alpha", float)])
 
 
 class Processors(NamedTuple):
@@ -263,6 +265,28 @@ def check_truncation_args(min_p, typical_p, epsilon_cutoff, eta_cutoff, do_sampl
     return t
 
 
+def check_contrastive_args(penalty_alpha, top_k, do_sample, num_beams, num_beam_groups=1, guidance_scale=1.0, num_return_sequences=1) -> Optional[Contrastive]:
+    """The checks of generate()'s penalty_alpha.  Returns the Contrastive, None for 0 (off: exactly the paths without it, top_k stays what it
+    was to them).  On for 0 < penalty_alpha <= 1 together with 2 <= top_k <= 8, do_sample=False, num_beams == 1, one beam group, no guidance
+    and one returned sequence; everything else raises ValueError."""
+    a = penalty_alpha
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0 <= a <= 1:             # (NaN fails both comparisons)
+        raise ValueError(f"generate(): penalty_alpha must be a number in [0, 1] (0 = off), got {a!r}")
+    if a == 0:
+        return None
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 2 <= top_k <= F.ffi.CONTRASTIVE_K_MAX:
+        raise ValueError(f"generate(): contrastive search (penalty_alpha > 0) needs an integer top_k in [2, {F.ffi.CONTRASTIVE_K_MAX}], got {top_k!r}")
+    if do_sample:
+        raise ValueError("generate(): penalty_alpha cannot be combined with do_sample (contrastive search is deterministic)")
+    if num_beams > 1 or num_beam_groups > 1:
+        raise ValueError("generate(): penalty_alpha cannot be combined with beam search (num_beams > 1, num_beam_groups > 1)")
+    if guidance_scale != 1:
+        raise ValueError("generate(): penalty_alpha cannot be combined with guidance_scale")
+    if num_return_sequences > 1:
+        raise ValueError("generate(): penalty_alpha cannot be combined with num_return_sequences > 1 (contrastive search has one result)")
+    return Contrastive(int(top_k), float(a))
+
+
 def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
     """sum(token_logprobs) / float32(len ** length_penalty) per row, len = L0 + the generated tokens up to and including eos: beam search's
     normalisation (BeamState.len_norm) applied to greedy and sampled sequences."""
@@ -276,7 +300,7 @@ def sequence_scores(sequences, token_logprobs, L0, eos, length_penalty):
 
 
 def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_family, L0, max_length, ids_is_int64, procs_on, procs_given=(),
-          logprobs_on=False, constraints_on=False, vocab=0, table_entries=0, guidance_on=False, beam_sample_on=False):
+          logprobs_on=False, constraints_on=False, vocab=0, table_entries=0, guidance_on=False, beam_sample_on=False, contrastive_on=False):
     """Which path a generate() call takes: "static" (a _DecodeSession) or "dynamic" (dynamic_decode / beam_search), from plain values only.
     `static_decode` is generate()'s argument (None, True, False), `model_default` the model's attribute, `procs_given` the processor
     arguments' names for the TypeError on CPU tensors.  Greedy decoding takes the static path by default on the GPU; sampling and beam search
@@ -290,7 +314,9 @@ def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_fam
     `do_sample` here means TOKEN sampling (one token per row from its own distribution): together with num_beams > 1 it raises, as it always
     has.  Beam sampling (generate(num_beams > 1, do_sample=True)) is a beam search whose selection draws: generate() asks for it with
     do_sample=False and `beam_sample_on=True`, and it routes exactly like beam search - static only with static_decode=True, which on CPU
-    tensors raises what ffi.require_cuda raises (its kernel has no CPU form), otherwise the dynamic loop, which also runs on CPU tensors."""
+    tensors raises what ffi.require_cuda raises (its kernel has no CPU form), otherwise the dynamic loop, which also runs on CPU tensors.
+    Contrastive search (`contrastive_on`, with num_beams = 1 and do_sample=False) routes like beam search too: a _ContrastiveSession only
+    with static_decode=True, which needs GPU tensors; otherwise decoding.contrastive_search, which also runs on CPU tensors."""
     def need_gpu():                     # what ffi.require_cuda raises for a CPU tensor
         if not is_cuda:
             F.ffi.require_cuda(torch.empty(0))
@@ -301,7 +327,7 @@ def route(*, is_cuda, num_beams, do_sample, static_decode, model_default, lm_fam
         raise TypeError(f"generate(): unsupported generation arguments {list(procs_given)} on CPU tensors (the logits processors run on the GPU only)")
     if num_beams > 1 and do_sample:
         raise ValueError("beam search with sampling is not implemented")
-    on_request = num_beams > 1 or do_sample or beam_sample_on                 # static only when static_decode=True is passed
+    on_request = num_beams > 1 or do_sample or beam_sample_on or contrastive_on                 # static only when static_decode=True is passed
     if (on_request or logprobs_on or constraints_on or guidance_on) and static_decode:
         need_gpu()
     if static_decode is None:
@@ -404,6 +430,53 @@ def order_by_score(a, beam, token, V):
     a, flat = a.gather(-1, o), flat.gather(-1, o)
     o = a.argsort(dim=-1, descending=True, stable=True)
     return a.gather(-1, o), flat.gather(-1, o)
+
+
+def topk_logprobs_torch(logits, k):
+    """Rule T of contrastive search (include/flamingo_fusion.h) in torch, on tensors of any device: per row of `logits` (rows, V) the k
+    largest values, by value descending, then by index ascending, with logp = x - lse (lse = max + log(sum exp(x - max))); a -inf logit is
+    listed only when fewer than k finite ones exist and carries logp = -inf.  The math is float32, float64 for float64 logits.
+    Returns (tok (rows, k) int64, logp (rows, k))."""
+    dt = torch.float64 if logits.dtype == torch.float64 else torch.float32
+    x = logits.to(dt)
+    m = x.amax(-1, keepdim=True)
+    lse = m + (x - m).exp().sum(-1, keepdim=True).log()
+    val, tok = x.sort(dim=-1, descending=True, stable=True)                 # (a stable sort: the lower index on equal values)
+    val, tok = val[:, :k], tok[:, :k]
+    return tok, torch.where(val > float("-inf"), val - lse, torch.full_like(val, float("-inf")))
+
+
+def contrastive_select_torch(hidden, hist, mask, cand_tok, cand_logp, finished, alpha, eos=None, pad=0):
+    """Rules C2 - C6 of contrastive search (include/flamingo_fusion.h) in torch, on tensors of any device: `hidden` (b * k, dim) the
+    candidates' lm_head inputs, `hist` (b, n, dim) those of the n positions so far, `mask` (b, n) - 0 excludes a position -, `cand_tok` /
+    `cand_logp` (b, k), `finished` (b,) bool (not modified).  cos = <h_c, H_j> / (max(|h_c|, 1e-12) max(|H_j|, 1e-12)), pen = the maximum
+    over the live positions (0 without one), score = (1 - alpha) exp(logp) - alpha pen, -inf for a dead candidate (logp = -inf); c* = the
+    smallest c of maximal score.  The math is float32, float64 for float64 `hidden`.
+    Returns (next_tok (b,), logprob (b,), c* (b,), finished after the step (b,), score (b, k))."""
+    dt = torch.float64 if hidden.dtype == torch.float64 else torch.float32
+    b, k = cand_tok.shape
+    h = hidden.to(dt).reshape(b, k, -1)
+    H = hist.to(dt)
+    hn = h.square().sum(-1).sqrt().clamp(min=1e-12)                            # (b, k)
+    Hn = H.square().sum(-1).sqrt().clamp(min=1e-12)                            # (b, n)
+    cos = torch.einsum("bkd,bnd->bkn", h, H) / (hn[:, :, None] * Hn[:, None, :])
+    live = (mask != 0)[:, None, :].expand(b, k, -1)
+    if live.shape[-1] > 0:
+        pen = cos.masked_fill(~live, float("-inf")).amax(-1)
+        pen = torch.where(pen > float("-inf"), pen, torch.zeros_like(pen))
+    else:
+        pen = torch.zeros((b, k), dtype=dt, device=hidden.device)
+    lp = cand_logp.to(dt)
+    score = torch.where(lp > float("-inf"), (1.0 - alpha) * lp.exp() - alpha * pen, torch.full_like(lp, float("-inf")))
+    best = score.amax(-1, keepdim=True)
+    first = (score == best) & (best > float("-inf"))                          # every candidate dead: no True, and c* = k % k = 0
+    c = torch.where(first, torch.arange(k, device=score.device).expand(b, k), torch.full((b, k), k, device=score.device)).amin(-1) % k
+    tok = cand_tok.gather(1, c[:, None])[:, 0]
+    logprob = lp.gather(1, c[:, None])[:, 0]
+    nxt = torch.where(finished, torch.full_like(tok, pad), tok)
+    logprob = torch.where(finished, torch.zeros_like(logprob), logprob)
+    done = finished | (nxt == eos) if eos is not None else finished.clone()
+    return nxt, logprob, c, done, score
 
 
 def process_logits(logits, seqs, repetition_penalty, no_repeat_ngram_size, eos, min_len):
@@ -575,7 +648,8 @@ class _DecodeSession:
     If the capture raises (e.g. a host synchronisation inside the stock LM) the steps run eagerly.
     This class is what the strategies share - the caches and buffers, the step, capture and replay, the prompt step and the loop of run().
     How a token is chosen is the subclass's: _TokenSession (greedy, sampling) and _BeamSession supply _alloc, _begin, _history, _select,
-    _all_done and _result, and override neither _append nor run.
+    _all_done and _result, and override neither _append nor run.  _ContrastiveSession, whose selection needs the LM's output for the
+    candidates, also supplies _first and _step.
     `processors` (a Processors) puts functional.process_logits (one launch, csrc/ff_logits.hip) in front of the selection of every strategy:
     _append edits the step's logits in place against the strategy's token history (_history(), with `pos` as its length) and against
     `min_len`, a device scalar _begin sets outside any capture.  A session without processors issues none of this.
@@ -592,6 +666,8 @@ class _DecodeSession:
     and issues none of this."""
 
     nb = 1                                 # rows per sequence
+    first_in_step = False                  # the prompt step chooses the first token (True: the first decode step does, and one more step runs)
+    prompt_kwargs = {}                     # further arguments of the prompt step's forward
 
     def __init__(self, model, b, max_length, device, ids_dtype, am_dtype, eos, pad, graph, sampling=None, beams=None, processors=None, logprobs=False,
                  constraints=None, groups=None, guidance=False, truncation=None):
@@ -682,6 +758,9 @@ class _DecodeSession:
             F.constrain_logits(logits, self._history(), self.pos, self.gen_start, self.eos, trie=self.trie_bufs, bad_words=self.bw_bufs)
         self._select(logits)
 
+    def _first(self, out):                 # what the prompt step's output feeds
+        self._append(out.logits[:, -1])
+
     def _positions(self, L0=None):
         """How the LM family learns where a step's tokens sit without reading anything back to the host.  GPT-2 takes absolute cache
         positions.  OPT numbers the ATTENDED tokens (cumsum of the attention mask, padding skipped - modeling_opt's own rule), and derives
@@ -718,7 +797,7 @@ class _DecodeSession:
                 visual_features = torch.cat([visual_features, visual_features])
         self.cache.reset()
         out = self.model.flamingo(input_ids=lm_ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=(None, self.cache),
-                                  pixel_values=pixel_values, visual_features=visual_features, **self._positions(L0))
+                                  pixel_values=pixel_values, visual_features=visual_features, **self._positions(L0), **self.prompt_kwargs)
         fresh = out.past_key_values[0]
         if self.xattn_past is None:
             self.xattn_past = tuple((torch.empty_like(k, memory_format=torch.contiguous_format), torch.empty_like(v, memory_format=torch.contiguous_format))
@@ -731,8 +810,8 @@ class _DecodeSession:
         self.am_buf.zero_()
         self.am_buf[:, :L0] = am
         self.pos.fill_(L0)
-        self._append(out.logits[:, -1])
-        remaining = self.max_length - L0 - 1
+        self._first(out)
+        remaining = self.max_length - L0 - 1 + int(self.first_in_step)
         if self.graph_wanted and self.replay is None and not self.capture_failed and remaining > 1:
             self._step()                                                      # eager once: lazy initialisation, allocator pools
             remaining -= 1
@@ -915,8 +994,117 @@ class _BeamSession(_DecodeSession):
         return res.to(prompt_ids.device) if n_return is None else tuple(t.to(prompt_ids.device) for t in res)
 
 
+class _ContrastiveSession(_DecodeSession):
+    """Contrastive search (GPU only) for `b` sequences with `contrastive` (a Contrastive): rules T and C1 - C9 of include/flamingo_fusion.h.
+    Every LM-side buffer and the LM cache are b * k rows wide (row s * k + c = candidate c of sequence s; the prompt is repeated k times, the
+    visual features are encoded once per sequence and repeated, as in _BeamSession); `tok` holds the CANDIDATES, so a decode step runs the LM
+    on all of them (rule C1).  The session owns `hist` (b, max_length, dim), the lm_head inputs of the positions so far, in the model's dtype;
+    `mask` (b, max_length) - the prompt's attention mask, 1 from the prompt's end on, written by _begin outside any capture -; `seq_buf`
+    (b, max_length), the sequences, which is what the processors and constraints read; `next_logits` (b, V), the chosen rows' logits, which
+    they edit in place; the candidate buffers `cand_tok` / `cand_logp` (b, k); `alpha`, a device scalar run() writes outside any capture - a
+    later call with another penalty_alpha replays the same graph -; `finished`, `n_new` and, with `logprobs`, `lp_buf`.
+    The prompt step fills hist[:, :L0] from the rows s * k, runs the processors, the constraints and functional.topk_logprobs on those rows'
+    logits and writes tok <- candidates: it chooses NO token.  A decode step is: the LM on the b * k candidates; functional.contrastive_step
+    (one launch: the look-ahead ranking, the choice, the eos bookkeeping, hist[:, pos] <- the chosen vector); functional.beam_gather of the LM
+    cache with beam_idx - every row of a sequence takes the chosen row, live positions including the one just written -; the token appended to
+    seq_buf; index_select(logits, sel_row, out=next_logits); the processors and constraints in place against seq_buf; topk_logprobs;
+    tok <- candidates.  The first token is chosen by the first decode step, so a call that fills max_length runs max_length - L0 decode
+    steps, one more than the other sessions (first_in_step)."""
+
+    first_in_step = True
+    prompt_kwargs = {"output_last_hidden_state": True}
+
+    def __init__(self, model, b, *args, contrastive, **kw):
+        self.nb = contrastive.k
+        self.contrastive = contrastive
+        super().__init__(model, b, *args, **kw)
+
+    def _alloc(self):
+        dev, n, k = self.pos.device, self.n_seq, self.nb
+        self.finished = torch.zeros(n, dtype=torch.bool, device=dev)
+        self.n_new = torch.zeros((), dtype=torch.long, device=dev)            # tokens appended while not every sequence had finished
+        self.alpha = torch.zeros((1,), dtype=torch.float32, device=dev)
+        self.mask = torch.zeros((n, self.max_length), dtype=torch.bool, device=dev)
+        self.seq_buf = torch.full((n, self.max_length), self.fill, dtype=torch.long, device=dev)
+        self.cand_tok = torch.zeros((n, k), dtype=torch.long, device=dev)
+        self.cand_logp = torch.zeros((n, k), dtype=torch.float32, device=dev)
+        self.step_out = (torch.zeros((n,), dtype=torch.long, device=dev), torch.zeros((n,), dtype=torch.float32, device=dev),
+                         torch.zeros((n,), dtype=torch.long, device=dev), torch.zeros((n * k,), dtype=torch.long, device=dev))      # next_tok, logprob, sel_row, beam_idx
+        self.hist = self.next_logits = self.lm_tensors = None                 # allocated by the first prompt step (the model says dim, V and the dtypes)
+        if self.processors is not None:
+            self._alloc_min_len()
+        if self.logprobs:
+            self.lp_buf = torch.zeros((n, self.max_length), dtype=torch.float32, device=dev)
+
+    def _begin(self, ids, ml, am, pixel_values, visual_features, generator):
+        L0 = ids.shape[1]
+        if visual_features is None and pixel_values is not None:             # encoded once per sequence, repeated per candidate
+            visual_features, pixel_values = self.model.flamingo.encode_resample_visuals(pixel_values), None
+        self.finished.zero_()
+        self.n_new.zero_()
+        self.mask.fill_(True)
+        self.mask[:, :L0] = am != 0
+        self.seq_buf.fill_(self.fill)
+        self.seq_buf[:, :L0] = ids
+        if self.processors is not None:
+            self.min_len.fill_(self.processors.min_len(L0))
+        if self.logprobs:
+            self.lp_buf.zero_()
+        ids, ml, am = _repeat_leading(ids, self.nb), _repeat_leading(ml, self.nb), _repeat_leading(am, self.nb)
+        if visual_features is not None:
+            visual_features = _repeat_leading(visual_features, self.nb)
+        return ids, ml, am, pixel_values, visual_features
+
+    def _history(self):
+        return self.seq_buf
+
+    def _first(self, out):                 # the prompt step: H[:, :L0] and the first candidates, from the rows s * k
+        h, logits = out.hidden_states[-1][::self.nb], out.logits[::self.nb, -1]
+        if self.hist is None:
+            self.hist = torch.zeros((self.n_seq, self.max_length, h.shape[-1]), dtype=h.dtype, device=h.device)
+            self.next_logits = torch.empty((self.n_seq, logits.shape[-1]), dtype=logits.dtype, device=logits.device)
+            self.lm_tensors = [t for layer in self.cache.layers for t in (layer.keys, layer.values)]
+        self.hist[:, :h.shape[1]].copy_(h)
+        self.next_logits.copy_(logits)
+        self._append(self.next_logits)
+
+    def _select(self, logits):             # rule T on the processed logits of the chosen rows; the candidates are what the next step feeds
+        F.topk_logprobs(logits, self.nb, out=(self.cand_tok, self.cand_logp))
+        self.tok.copy_(self.cand_tok.view(-1, 1))
+
+    def _step(self):
+        self.am_buf.index_fill_(1, self.pos, 1)
+        o = self.model.flamingo(input_ids=self.tok, attention_mask=self.am_buf, use_cache=True, past_key_values=(self.xattn_past, self.cache),
+                                text_time=self.tt_step, output_last_hidden_state=True, **self._positions())
+        nxt, lp, sel_row, beam_idx = self.step_out
+        alive = ~self.finished.all()                                          # (before the launch updates `finished`, in stream order)
+        F.contrastive_step(o.hidden_states[-1][:, -1], self.hist, self.mask, self.cand_tok, self.cand_logp, self.finished, self.alpha, self.pos,
+                           eos=self.eos, pad=self.fill, out=self.step_out)
+        self.seq_buf.index_copy_(1, self.pos, nxt[:, None])
+        if self.logprobs:
+            self.lp_buf.index_copy_(1, self.pos, lp[:, None])
+        self.n_new.add_(alive.to(self.n_new.dtype))
+        self.pos.add_(1)
+        F.beam_gather(self.lm_tensors, beam_idx, self.pos, self.nb)          # positions < pos are live, the one just written included
+        torch.index_select(o.logits[:, -1], 0, sel_row, out=self.next_logits)
+        self._append(self.next_logits)
+
+    @torch.no_grad()
+    def run(self, *args, penalty_alpha, **kw):
+        self.alpha.fill_(penalty_alpha)                                       # outside any capture: the replayed step only reads it
+        return super().run(*args, **kw)
+
+    def _all_done(self):
+        return self.finished
+
+    def _result(self, L0, prompt_ids, length, n_return=None):
+        ids = self.seq_buf[:, :L0 + int(self.n_new)].clone() if self.eos is not None else self.seq_buf.clone()
+        ids = ids.to(prompt_ids.dtype)
+        return (ids, self.lp_buf[:, L0:ids.shape[1]].clone()) if self.logprobs else ids
+
+
 def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length, eos, pad, sampling=None, generator=None, beams=None, processors=None,
-                   logprobs=False, n_return=None, constraints=None, groups=None, guidance=None, truncation=None):
+                   logprobs=False, n_return=None, constraints=None, groups=None, guidance=None, truncation=None, contrastive=None):
     """Greedy, sampled (`sampling`) or beam-search (`beams`) decoding with FIXED shapes (see _DecodeSession).  Sessions - preallocated caches
     and buffers plus, on the GPU, the captured HIP graph of one decode step - are kept per (batch, max_length, keys per sequence, device,
     eos, pad, graph, sampling, beams, processors) and reused by later calls, so only the first caption batch of a shape pays for the
@@ -934,7 +1122,10 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
     key ends with the Truncation - the values are launch constants of the captured step, like the Groups.  A call without it builds the key it
     always built.
     `sampling` TOGETHER with `beams` selects a beam-sampling session (a _BeamSession whose selection draws): the key's own `sampling` and
-    `beams` elements tell it from both, nothing is appended."""
+    `beams` elements tell it from both, nothing is appended.
+    `contrastive` (a Contrastive) selects a _ContrastiveSession: its key ends with ("contrastive", k) - the k, which is the session's shape,
+    NOT penalty_alpha, a device scalar the captured step reads: a sweep over alpha replays one graph.  A call without it builds the key it
+    always built."""
     b = ids.shape[0]
     graph = ids.is_cuda and not model.training and model.decode_graph
     sessions = _DECODE_SESSIONS.setdefault(model, {})
@@ -949,6 +1140,8 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
         key += ("guidance",)
     if truncation is not None:
         key += (truncation,)
+    if contrastive is not None:
+        key += (("contrastive", contrastive.k),)
     sess = sessions.get(key)
     if sess is not None and sess.stale():
         sessions.pop(key)
@@ -956,12 +1149,13 @@ def _static_decode(model, ids, ml, am, pixel_values, visual_features, max_length
     if sess is None:
         if len(sessions) >= 4:                                                # a handful of shapes at most: each holds a KV cache and a graph
             sessions.pop(next(iter(sessions)))
-        cls = _TokenSession if beams is None else _BeamSession
+        cls = _ContrastiveSession if contrastive is not None else (_TokenSession if beams is None else _BeamSession)
         sess = sessions[key] = cls(model, b, max_length, ids.device, ids.dtype, am.dtype, eos, pad, graph, sampling=sampling, beams=beams, processors=processors, logprobs=logprobs,
                                    **({"constraints": constraints.caps()} if constraints is not None else {}), **({"groups": groups} if groups is not None else {}),
-                                   **({"guidance": True} if guidance is not None else {}), **({"truncation": truncation} if truncation is not None else {}))
+                                   **({"guidance": True} if guidance is not None else {}), **({"truncation": truncation} if truncation is not None else {}),
+                                   **({"contrastive": contrastive} if contrastive is not None else {}))
     return sess.run(ids, ml, am, pixel_values, visual_features, generator=generator, n_return=n_return, **({"constraints": constraints} if constraints is not None else {}),
-                    **({"guidance_scale": guidance} if guidance is not None else {}))
+                    **({"guidance_scale": guidance} if guidance is not None else {}), **({"penalty_alpha": contrastive.penalty_alpha} if contrastive is not None else {}))
 
 
 # ---- the dynamic path: growing caches, one forward per step (the only path on CPU tensors, and what the sessions are tested against) ----
@@ -1117,6 +1311,54 @@ def beam_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features,
     fill = pad if pad is not None else 0
     ids = torch.tensor([o + [fill] * (width - len(o)) for o in out], dtype=torch.long, device=dev)
     return ids if n_return is None else (ids, torch.tensor(out_scores, dtype=torch.float32, device=dev))
+
+
+def contrastive_search(step, reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, contrastive, eos, pad, processors=None,
+                       logprob_dtype=None, constraints=None, trace=None):
+    """Contrastive search (rules T, C1 - C7 of include/flamingo_fusion.h) over the cached decode path with growing caches; `step` is
+    FlamingoModel._contrastive_step - (last logits (rows, V) float, lm_head inputs (rows, positions, dim), past) -, `reorder_cache`
+    FlamingoModel._reorder_cache, `contrastive` a Contrastive.  The prompt runs once per sequence and gives H[:, :L0] and the first
+    candidates; every later step feeds the k candidates of every sequence (the caches expanded b -> b k by reorder_cache with a repeated
+    index), ranks them with contrastive_select_torch, appends the chosen token and its lm_head input, and selects the chosen rows back
+    (reorder_cache with sel_row).  Processors and constraints act on the chosen row's logits before the next candidates are listed; the eos
+    bookkeeping is dynamic_decode's.  It also runs on CPU tensors.  With `logprob_dtype` it returns (ids, token_logprobs): logp of the chosen
+    candidate, 0 for a row that had finished.  `trace` (a list) receives one dict per step: what the selection read and what it chose."""
+    b, L0 = ids.shape
+    k, alpha = contrastive.k, contrastive.penalty_alpha
+    fill = pad if pad is not None else 0
+    dev = ids.device
+    process = _dynamic_processor(processors, eos, L0, constraints)
+    finished = torch.zeros(b, dtype=torch.bool, device=dev)
+    lps = []
+    logits, hidden, past = step(ids, ml, am, None, pixel_values, visual_features)
+    hist, mask = hidden, am != 0                                          # (b, n, dim), (b, n)
+    x = process(logits if logprob_dtype is None else logits.to(logprob_dtype), ids)
+    cand_tok, cand_logp = topk_logprobs_torch(x, k)
+    expand = torch.arange(b, device=dev).repeat_interleave(k)
+    while ids.shape[1] < max_length:
+        ml = torch.cat([ml, torch.zeros_like(ml[:, :1])], dim=1)
+        am = torch.cat([am, torch.ones_like(am[:, :1])], dim=1)
+        logits, hidden, past = step(cand_tok.reshape(-1, 1).to(ids.dtype), _repeat_leading(ml, k), _repeat_leading(am, k), reorder_cache(past, expand), None, None)
+        h = hidden[:, -1]                                                 # (b k, dim)
+        nxt, lp, c, done, score = contrastive_select_torch(h, hist, mask, cand_tok, cand_logp, finished, alpha, eos, fill)
+        sel_row = torch.arange(b, device=dev) * k + c
+        if trace is not None:
+            trace.append(dict(x=x, hidden=h, hist=hist, mask=mask, cand_tok=cand_tok, cand_logp=cand_logp, finished=finished, next_tok=nxt, logprob=lp,
+                              sel_row=sel_row, score=score))
+        lps.append(lp)
+        finished = done
+        hist = torch.cat([hist, h.index_select(0, sel_row)[:, None]], dim=1)
+        mask = torch.cat([mask, torch.ones_like(mask[:, :1])], dim=1)
+        ids = torch.cat([ids, nxt[:, None].to(ids.dtype)], dim=1)
+        if ids.shape[1] >= max_length or (eos is not None and bool(finished.all())):
+            break
+        past = reorder_cache(past, sel_row)
+        nl = logits.index_select(0, sel_row)
+        x = process(nl if logprob_dtype is None else nl.to(logprob_dtype), ids)
+        cand_tok, cand_logp = topk_logprobs_torch(x, k)
+    if logprob_dtype is not None:
+        return ids, (torch.stack(lps, dim=1).to(logprob_dtype) if lps else torch.zeros((b, 0), dtype=logprob_dtype, device=dev))
+    return ids
 
 
 # ---- exact closed-set scoring: the candidate trie walked level by level (FlamingoModel.score_candidates) ----

@@ -97,6 +97,7 @@ class XattnDesc(C.Structure):
 BEAM_MAX = 8                   # FF_BEAM_MAX
 LOGITS_HIST_MAX = 4096         # FF_LOGITS_HIST_MAX
 CONSTRAIN_VOCAB_MAX = 262144   # FF_CONSTRAIN_VOCAB_MAX
+CONTRASTIVE_K_MAX = 8          # FF_CONTRASTIVE_K_MAX
 
 
 class BeamDesc(C.Structure):
@@ -104,6 +105,12 @@ class BeamDesc(C.Structure):
                [(n, C.c_int) for n in ("max_len", "eos", "pad", "early_stopping")] + \
                [(n, C.c_void_p) for n in ("score", "done", "n_hyp", "hyp_score", "hyp_len", "hyp_row", "hist_tok", "hist_parent", "hist_score",
                                           "next_tok", "beam_idx", "len_norm")]
+
+
+class ContrastiveDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("dtype", "b", "k", "dim")] + [("ld_hidden", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("max_len", "eos", "pad", "reserved")] + \
+               [(n, C.c_void_p) for n in ("hidden", "hist", "mask", "cand_tok", "cand_logp", "finished", "next_tok", "logprob", "sel_row", "beam_idx", "score")]
 
 
 _P, _SZ, _I = C.c_void_p, C.c_size_t, C.c_int
@@ -179,6 +186,8 @@ _SIGNATURES = {
     "ff_beam_sample_workspace_bytes": (_SZ, [_I, _I]),
     "ff_beam_sample_step": (_I, [C.POINTER(BeamDesc), C.c_float, _I, C.c_float, _P, _P, _P, _P, _SZ, _P]),
     "ff_beam_sample_noise": (_I, [_I, _I, _P, _P, _P, _P]),
+    "ff_topk_logprob": (_I, [_I, _I, _I, C.c_longlong, _P, _I, _P, _P, _P]),
+    "ff_contrastive_step": (_I, [C.POINTER(ContrastiveDesc), _P, _P, _P]),
     "ff_logits_process": (_I, [_I, _I, _I, C.c_longlong, _P, _P, C.c_longlong, C.c_longlong, _P, C.c_float, _I, _I, _P, _P]),
     "ff_token_logprob": (_I, [_I, _I, _I, C.c_longlong, _P, _P, _P, _P, _P, _P]),
     "ff_logprob_gather": (_I, [_I, _I, _I, C.c_longlong, _P, _P, _P, _I, _P, _P, _P]),

@@ -1286,6 +1286,75 @@ def beam_sample_noise(rows: int, vocab: int, seed: torch.Tensor, cur_len: torch.
     return out
 
 
+def topk_logprobs(logits: torch.Tensor, k: int, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best tokens of every row of `logits` (rows, V), float32 / bfloat16 on the GPU, with their log-probabilities: rule T of
+    contrastive search (include/flamingo_fusion.h) - the k largest values, by value descending, then by index ascending; logp = x - lse in
+    float32; a -inf logit is listed only when fewer than k finite ones exist, with logp = -inf.  ff_topk_logprob, one launch that reads each
+    row once; only the last dimension has to be contiguous (logits3d[:, -1] is read in place through its row stride).  1 <= k <= 8, V >= k.
+    Returns (tok (rows, k) int64, logp (rows, k) float32); with `out` = such a pair (contiguous) nothing is allocated, so the call can be
+    captured into a graph."""
+    ffi.require_cuda(logits, *(out or ()))
+    if logits.ndim != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"topk_logprobs: logits must be (rows, V) with a contiguous last dimension, got shape {tuple(logits.shape)} strides {logits.stride()}")
+    rows, V = logits.shape
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ffi.CONTRASTIVE_K_MAX or V < k:
+        raise ValueError(f"topk_logprobs: k must be an integer in [1, {ffi.CONTRASTIVE_K_MAX}] and at most V = {V}, got {k!r}")
+    if out is None:
+        out = (_new((rows, k), torch.long, logits.device), _new((rows, k), torch.float32, logits.device))
+    tok, logp = out
+    if tok.dtype != torch.long or logp.dtype != torch.float32 or tok.shape != (rows, k) or logp.shape != (rows, k) or not tok.is_contiguous() or not logp.is_contiguous():
+        raise ValueError(f"topk_logprobs: out must be (tok ({rows}, {k}) int64, logp ({rows}, {k}) float32), contiguous, got {tuple(tok.shape)} {tok.dtype}, {tuple(logp.shape)} {logp.dtype}")
+    ld = logits.stride(0) if rows > 1 else V
+    ffi.check(ffi.lib().ff_topk_logprob(ffi.dtype_code(logits.dtype), rows, V, ld, logits.data_ptr(), k, tok.data_ptr(), logp.data_ptr(),
+                                        ffi.stream_handle(logits.device)), "ff_topk_logprob")
+    return tok, logp
+
+
+def contrastive_step(hidden: torch.Tensor, hist: torch.Tensor, mask: torch.Tensor, cand_tok: torch.Tensor, cand_logp: torch.Tensor, finished: torch.Tensor,
+                     alpha: torch.Tensor, n_pos: torch.Tensor, eos: Optional[int] = None, pad: int = 0, out=None, score: Optional[torch.Tensor] = None):
+    """One contrastive-search selection, rules C2 - C7 of include/flamingo_fusion.h: ff_contrastive_step, one launch, one workgroup per
+    sequence.  `hidden` (b * k, dim), float32 / bfloat16 with a contiguous last dimension: the lm_head inputs of the k candidates of every
+    sequence (row s * k + c).  `hist` (b, max_len, dim), contiguous, the dtype of `hidden`: the lm_head inputs of the positions so far, read
+    below `n_pos` and WRITTEN at `n_pos` with the chosen candidate's vector.  `mask` (b, max_len) bool / uint8: 0 excludes a position from the
+    penalty.  `cand_tok` / `cand_logp` (b, k) int64 / float32: what topk_logprobs gave for the rows the candidates came from.  `finished`
+    (b,) bool / uint8, read and updated.  `alpha` (one float32) and `n_pos` (one int64) are DEVICE scalars the launch reads: a captured call
+    serves every value written there.  Returns `out` = (next_tok (b,) int64, logprob (b,) float32, sel_row (b,) int64 - the global row
+    s * k + c* -, beam_idx (b * k,) int64 - every row of a sequence points at its sel_row: the argument of beam_gather); with `out` given
+    nothing is allocated, so the call can be captured into a graph.  `score` (b, k) float32, optional: receives rule C4's values."""
+    ffi.require_cuda(hidden, hist, mask, cand_tok, cand_logp, finished, alpha, n_pos, score, *(out or ()))
+    if hidden.ndim != 2 or (hidden.shape[1] > 1 and hidden.stride(1) != 1):
+        raise ValueError(f"contrastive_step: hidden must be (b * k, dim) with a contiguous last dimension, got shape {tuple(hidden.shape)} strides {hidden.stride()}")
+    if cand_tok.ndim != 2 or cand_tok.dtype != torch.long or not cand_tok.is_contiguous():
+        raise ValueError(f"contrastive_step: cand_tok must be (b, k) contiguous int64, got {tuple(cand_tok.shape)} {cand_tok.dtype}")
+    b, k = cand_tok.shape
+    rows, dim = hidden.shape
+    if not 1 <= k <= ffi.CONTRASTIVE_K_MAX or rows != b * k:
+        raise ValueError(f"contrastive_step: k {k} must lie in [1, {ffi.CONTRASTIVE_K_MAX}] and hidden must have b * k = {b * k} rows, got {rows}")
+    if cand_logp.dtype != torch.float32 or cand_logp.shape != (b, k) or not cand_logp.is_contiguous():
+        raise ValueError(f"contrastive_step: cand_logp must be ({b}, {k}) contiguous float32, got {tuple(cand_logp.shape)} {cand_logp.dtype}")
+    if hist.ndim != 3 or hist.shape[0] != b or hist.shape[2] != dim or hist.dtype != hidden.dtype or not hist.is_contiguous():
+        raise ValueError(f"contrastive_step: hist must be ({b}, max_len, {dim}) contiguous {hidden.dtype}, got {tuple(hist.shape)} {hist.dtype}")
+    max_len = hist.shape[1]
+    for name, t, shape in (("mask", mask, (b, max_len)), ("finished", finished, (b,))):
+        if t.dtype not in (torch.bool, torch.uint8) or t.shape != shape or not t.is_contiguous():
+            raise ValueError(f"contrastive_step: {name} must be {shape} contiguous bool / uint8, got {tuple(t.shape)} {t.dtype}")
+    if alpha.dtype != torch.float32 or alpha.numel() != 1 or n_pos.dtype != torch.long or n_pos.numel() != 1:
+        raise ValueError(f"contrastive_step: alpha must be one float32 and n_pos one int64 value on the device, got {alpha.dtype} {tuple(alpha.shape)}, {n_pos.dtype} {tuple(n_pos.shape)}")
+    if out is None:
+        dev = hidden.device
+        out = (_new((b,), torch.long, dev), _new((b,), torch.float32, dev), _new((b,), torch.long, dev), _new((b * k,), torch.long, dev))
+    for name, t, dt, num in zip(("next_tok", "logprob", "sel_row", "beam_idx"), out, (torch.long, torch.float32, torch.long, torch.long), (b, b, b, b * k)):
+        if t.dtype != dt or t.shape != (num,) or not t.is_contiguous():
+            raise ValueError(f"contrastive_step: out {name} must be {num} contiguous {dt} values, got {tuple(t.shape)} {t.dtype}")
+    if score is not None and (score.dtype != torch.float32 or score.shape != (b, k) or not score.is_contiguous()):
+        raise ValueError(f"contrastive_step: score must be ({b}, {k}) contiguous float32, got {tuple(score.shape)} {score.dtype}")
+    d = ffi.ContrastiveDesc(ffi.dtype_code(hidden.dtype), b, k, dim, hidden.stride(0) if rows > 1 else dim, max_len, -1 if eos is None else int(eos), int(pad), 0,
+                            hidden.data_ptr(), hist.data_ptr(), mask.data_ptr(), cand_tok.data_ptr(), cand_logp.data_ptr(), finished.data_ptr(),
+                            *(t.data_ptr() for t in out), ffi.ptr(score))
+    ffi.check(ffi.lib().ff_contrastive_step(d, alpha.data_ptr(), n_pos.data_ptr(), ffi.stream_handle(hidden.device)), "ff_contrastive_step")
+    return out
+
+
 def beam_gather(tensors: Sequence[torch.Tensor], beam_idx: torch.Tensor, n_pos: torch.Tensor, nb: int) -> None:
     """t[row, :, p] <- t[beam_idx[row], :, p] IN PLACE for every tensor of `tensors` - all (b * nb, outer, len_max, inner), contiguous, one
     dtype of 2 or 4 bytes: the keys / values of a StaticCache - and every position p < n_pos (a one-element int64 device tensor); later

@@ -175,12 +175,14 @@ class FlamingoBaseModel(ABC, PreTrainedModel):
     def forward(self, input_ids=None, attention_mask=None, media_locations=None, pixel_values=None, visual_features=None,
                 head_mask=None, inputs_embeds=None, use_cache: bool = False, past_key_values=None, return_dict: bool = True,
                 labels=None, loss_reduction: str = "mean", text_time=None, label_smoothing: Optional[float] = None,
-                z_loss: Optional[float] = None, **kwargs) -> CausalLMOutputWithPast:
+                z_loss: Optional[float] = None, output_last_hidden_state: bool = False, **kwargs) -> CausalLMOutputWithPast:
         """label_smoothing (eps in [0, 1]) and z_loss (zeta >= 0) regularise the loss, per scored token
             lse - (1 - eps) x_t - eps mean(x) + zeta lse^2           (functional.shifted_cross_entropy)
         None takes the optional config keys `label_smoothing` / `z_loss` (0 when absent), so loops that call model(**batch) - HF Trainer,
         GraphedTrainStep, PiecewiseGraphedTrainStep - pick them up from the config.  They are launch constants: a captured step keeps the
-        values it was captured with.  The loss is the same in eval(): pass label_smoothing=0.0, z_loss=0.0 for the plain evaluation loss."""
+        values it was captured with.  The loss is the same in eval(): pass label_smoothing=0.0, z_loss=0.0 for the plain evaluation loss.
+        output_last_hidden_state=True returns the lm_head's input as `hidden_states` = (last_hidden_state,) - what contrastive search compares;
+        without it the output is what it always was."""
         assert return_dict, "can only use return_dict=True at the moment!"
         eps, zeta = F.check_loss_regularisers(getattr(self.config, "label_smoothing", 0.0) if label_smoothing is None else label_smoothing,
                                               getattr(self.config, "z_loss", 0.0) if z_loss is None else z_loss)
@@ -277,7 +279,7 @@ class FlamingoBaseModel(ABC, PreTrainedModel):
         return CausalLMOutputWithPast(
             loss=loss, logits=logits,
             past_key_values=(tuple(new_xattn_past), out.past_key_values) if use_cache else None,
-            hidden_states=getattr(out, "hidden_states", None), attentions=getattr(out, "attentions", None))
+            hidden_states=(out.last_hidden_state,) if output_last_hidden_state else getattr(out, "hidden_states", None), attentions=getattr(out, "attentions", None))
 
 
 class FlamingoGPT2(FlamingoBaseModel):
@@ -437,6 +439,12 @@ class FlamingoModel(PreTrainedModel):
                             pixel_values=pixel_values if past is None else None, visual_features=visual_features if past is None else None)
         return out.logits[:, -1], out.past_key_values
 
+    def _contrastive_step(self, step_ids, ml, am, past, pixel_values, visual_features):
+        """_decode_step for contrastive search: also the lm_head's input of every position fed, (rows, positions, dim) in the model's dtype."""
+        out = self.flamingo(input_ids=step_ids, attention_mask=am, media_locations=ml, use_cache=True, past_key_values=past, output_last_hidden_state=True,
+                            pixel_values=pixel_values if past is None else None, visual_features=visual_features if past is None else None)
+        return out.logits[:, -1].float(), out.hidden_states[-1], out.past_key_values
+
     _filter_logits = staticmethod(D.filter_logits)         # the torch restatements the dynamic loops use
     _process_logits = staticmethod(D.process_logits)
 
@@ -449,7 +457,7 @@ class FlamingoModel(PreTrainedModel):
                  min_length: int = 0, min_new_tokens: int = 0, return_dict_in_generate: bool = False, output_logprobs: bool = False,
                  num_return_sequences: int = 1, candidate_ids=None, bad_words_ids=None, num_beam_groups: int = 1,
                  diversity_penalty: float = 0.0, guidance_scale: float = 1.0, min_p: float = 0.0, typical_p: float = 1.0,
-                 epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0, **unsupported):
+                 epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0, penalty_alpha: float = 0.0, **unsupported):
         """Text generation with the cached cross-attention path: the first step runs CLIP + resampler and fills the xattn K/V and LM caches,
         every later step feeds one token (reference: HF `generate` through prepare_inputs_for_generation / _reorder_cache, :464-548).
         transformers >= 4.50 no longer gives PreTrainedModel a `generate`, so the decoding strategies the reference's callers use are
@@ -542,7 +550,27 @@ class FlamingoModel(PreTrainedModel):
         (decoding.beam_sample_select_torch), which also runs on CPU tensors.  As with token sampling the two paths draw DIFFERENT streams
         from one seed; each is reproducible per `generator`.  Known and accepted: with top_k < 2 * num_beams the first step has fewer
         finite candidates than it draws and the missing beams are dead.  num_beam_groups > 1, min_p / typical_p / epsilon_cutoff /
-        eta_cutoff and output_logprobs keep their ValueErrors under beam sampling."""
+        eta_cutoff and output_logprobs keep their ValueErrors under beam sampling.
+        Contrastive search (Su et al. 2022, "A Contrastive Framework for Neural Text Generation"; transformers' `penalty_alpha` with `top_k`)
+        is the deterministic answer to the repetitions of greedy and beam search: every step lists the `top_k` most probable next tokens,
+        feeds EACH of them to the LM, and chooses the one that maximises
+            (1 - penalty_alpha) * p(token) - penalty_alpha * max_j cos(h_token, h_j),
+        h the lm_head's input and j the positions so far (the prompt's left padding excluded): confident, and unlike what was said.  0 is off
+        (exactly the paths without it, call for call; `top_k` with greedy decoding stays ignored); it is on for 0 < penalty_alpha <= 1
+        together with 2 <= top_k <= 8, do_sample=False and num_beams == 1.  ValueError: a non-finite or negative value or one above 1; a
+        top_k outside that range while it is on; do_sample, num_beams > 1, num_beam_groups > 1, guidance_scale != 1, num_return_sequences > 1.
+        The exact rules are T and C1 - C9 of include/flamingo_fusion.h: probabilities come from the log-softmax of the logits after the
+        processors and constraints, ties go to the more probable candidate, a banned candidate (probability 0) never wins - in
+        transformers it can, on its penalty alone - and the norms are clamped at 1e-12 where transformers divides by zero.  It composes with
+        repetition_penalty, no_repeat_ngram_size, min_length / min_new_tokens, candidate_ids, bad_words_ids, eos / pad,
+        return_dict_in_generate and output_logprobs: token_logprobs is the chosen candidate's log-probability, the log-softmax of the
+        processed logits as for greedy decoding, and sequences_scores their length-normalised sum.  Routing is that of beam search: the
+        static session (decoding._ContrastiveSession: the LM runs on batch * top_k rows; the ranking, the choice and the eos bookkeeping are
+        one launch inside the replayed step, functional.contrastive_step, the candidates another, functional.topk_logprobs, and the LM
+        cache follows the chosen row through functional.beam_gather; penalty_alpha is a device scalar, so calls with other values reuse the
+        session and its graph, and top_k is part of the session key) only with static_decode=True, which needs GPU tensors; otherwise the
+        dynamic loop (decoding.contrastive_search), which also runs on CPU tensors.  Not offered: guidance, top_k above 8, per-row
+        penalty_alpha."""
         procs = D.check_generate_args(unsupported, use_cache, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, eos_token_id)
         n_ret = D.check_output_args(return_dict_in_generate, output_logprobs, num_return_sequences, num_beams, do_sample)
         groups = D.check_group_args(num_beam_groups, diversity_penalty, num_beams, do_sample)
@@ -550,6 +578,7 @@ class FlamingoModel(PreTrainedModel):
         guidance = D.check_guidance_args(guidance_scale)
         trunc = D.check_truncation_args(min_p, typical_p, epsilon_cutoff, eta_cutoff, do_sample, num_beams)
         tkw = {} if trunc is None else {"truncation": trunc}                 # nothing is passed on without them: the calls are what they were
+        contr = D.check_contrastive_args(penalty_alpha, top_k, do_sample, num_beams, num_beam_groups, guidance_scale, n_ret)
         ids = inputs if inputs is not None else input_ids
         assert ids is not None and media_locations is not None, "generate() needs input ids and media_locations"
         cons = D.check_constraint_args(candidate_ids, bad_words_ids, self.flamingo.lm.config.vocab_size, eos_token_id, procs, ids.shape[1], max_length)
@@ -565,7 +594,7 @@ class FlamingoModel(PreTrainedModel):
         path = D.route(is_cuda=ids.is_cuda, num_beams=num_beams, do_sample=do_sample and not beam_sample, static_decode=static_decode, model_default=self.static_decode, lm_family=self.flamingo.lm_family,
                        L0=ids.shape[1], max_length=max_length, ids_is_int64=ids.dtype == torch.long, procs_on=procs is not None, procs_given=procs.given() if procs is not None else (),
                        logprobs_on=bool(output_logprobs), **rkw, **({} if guidance is None else {"guidance_on": True}),
-                       **({"beam_sample_on": True} if beam_sample else {}))
+                       **({"beam_sample_on": True} if beam_sample else {}), **({} if contr is None else {"contrastive_on": True}))
         if n_ret > 1 and num_beams <= 1:                                     # sampling: every sequence n times, its visuals encoded once
             if visual_features is None and pixel_values is not None:
                 visual_features, pixel_values = self.flamingo.encode_resample_visuals(pixel_values), None
@@ -581,7 +610,14 @@ class FlamingoModel(PreTrainedModel):
             else:                                                            # the loops see a model whose logits are the guided scores
                 step, reorder = D.guided_step(step, guidance), D.guided_reorder(reorder)
         n_beams_out = n_ret if num_beams > 1 and (return_dict_in_generate or n_ret > 1) else None      # None: the search's single result, as ever
-        if path == "static":
+        if contr is not None and path == "static":
+            res = D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, processors=procs, logprobs=bool(output_logprobs),
+                                   contrastive=contr, **ckw)
+        elif contr is not None:
+            lp_dtype = (torch.float64 if next(self.parameters()).dtype == torch.float64 else torch.float32) if output_logprobs else None
+            res = D.contrastive_search(self._contrastive_step, self._reorder_cache, ids, ml, am, pixel_values, visual_features, max_length, contr, eos_token_id, pad,
+                                       processors=procs, logprob_dtype=lp_dtype, **ckw)
+        elif path == "static":
             res = D._static_decode(self, ids, ml, am, pixel_values, visual_features, max_length, eos_token_id, pad, generator=generator, processors=procs,
                                    sampling=D.Sampling(float(temperature), int(top_k), float(top_p)) if do_sample else None,
                                    beams=D.Beams(int(num_beams), bool(early_stopping), float(length_penalty)) if num_beams > 1 else None,
@@ -625,10 +661,11 @@ class FlamingoModel(PreTrainedModel):
         """Caption a batch of images; the prompt is replicated for every image (reference :550-605).  `kwargs` are generation
         arguments (do_sample, temperature, top_k, top_p, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length,
         min_new_tokens, num_return_sequences, output_logprobs, return_dict_in_generate, num_beam_groups, diversity_penalty, guidance_scale,
-        min_p, typical_p, epsilon_cutoff, eta_cutoff, ...) and go to
+        min_p, typical_p, epsilon_cutoff, eta_cutoff, penalty_alpha, ...) and go to
         generate(), which rejects unknown ones.  num_beams=4, num_beam_groups=4, diversity_penalty=1.0, num_return_sequences=4,
         return_scores=True gives the 4 best DIFFERENT captions of diverse beam search with the (penalised) scores they were ranked by.
         guidance_scale=1.5 weighs the image against the language model's prior (classifier-free guidance, see generate()).
+        penalty_alpha=0.6, top_k=4 is contrastive search: deterministic captions that do not repeat themselves (see generate()).
         `return_scores=True` returns (captions, scores), the scores floats from GenerateOutput.sequences_scores (beam search: the score the
         search ranked by; greedy and sampling: the length-normalised sum of the token log-probabilities).  With num_return_sequences = n > 1
         the captions (and the scores) are a list of one list of n per image.

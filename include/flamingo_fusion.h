@@ -61,7 +61,8 @@ int ff_version(void);          /* ABI version, bumped on any signature change (3
                                 * still 6, addition only: classifier-free guidance on the captured decode step, ff_guided_logits;
                                 * still 6, addition only: truncation samplers (min_p, typical_p, epsilon / eta cutoff), ff_sample_token_truncated;
                                 * still 6, addition only: exact closed-set scoring over a candidate trie, ff_logprob_gather;
-                                * still 6, additions only: beam sampling on the captured decode step, ff_beam_sample_step, ff_beam_sample_noise) */
+                                * still 6, additions only: beam sampling on the captured decode step, ff_beam_sample_step, ff_beam_sample_noise;
+                                * still 6, additions only: contrastive search on the captured decode step, ff_topk_logprob, ff_contrastive_step) */
 const char* ff_arch(void);     /* "gfx950" */
 const char* ff_last_error(void);
 
@@ -723,6 +724,66 @@ size_t ff_beam_sample_workspace_bytes(int b, int nb);
 int ff_beam_sample_step(const ff_beam_desc* d, float temperature, int top_k, float top_p, const long long* seed, const void* logits,
                         const long long* cur_len, void* workspace, size_t workspace_bytes, ff_stream_t stream);
 int ff_beam_sample_noise(int rows, int vocab, const long long* seed, const long long* cur_len, float* g, ff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Contrastive search (Su et al. 2022, "A Contrastive Framework for Neural Text Generation"; transformers' penalty_alpha with top_k) on the
+ * captured decode step (added under ABI 6): ff_topk_logprob lists a row's k best tokens with their log-probabilities, ff_contrastive_step
+ * ranks the k candidates of every sequence by model confidence minus their similarity to the context, chooses one and keeps the
+ * bookkeeping on the device.  Both are capturable: no allocation, no host synchronisation, no global atomics.
+ * Per sequence s, with n tokens so far (prompt included) and H[s, j] the lm_head input at position j < n:
+ *   T.  candidates: from the step's logits (after the processors and constraints) the k largest VALUES, ordered by value descending, then by
+ *       index ascending; they are compared as values, so the tokens are exact.  logp = x - lse in fp32, lse as in rules 1 - 2 of
+ *       ff_beam_step.  A -inf logit is listed only if fewer than k finite ones exist: a DEAD candidate, logp = -inf, its token unspecified but
+ *       in range;
+ *   C1. every candidate c is fed to the LM as the next token - k rows per sequence that share the sequence's cache -, which gives h_c (the
+ *       lm_head input) and the next logits.  (The caller's part.)
+ *   C2. cos_cj = <h_c, H_sj> / (max(|h_c|, 1e-12) * max(|H_sj|, 1e-12)), in fp32 in a fixed order, over the j < n with mask[s, j] != 0 (left
+ *       padding of the prompt is excluded, as in transformers);
+ *   C3. pen_c = max_j cos_cj; 0 if no live position exists;
+ *   C4. score_c = (1 - alpha) * exp(logp_c) - alpha * pen_c; a dead candidate scores -inf;
+ *   C5. c* = the smallest c of maximal score; 0 if every candidate is dead;
+ *   C6. a sequence that had finished gets pad and log-probability 0; otherwise the token is candidate c*'s, its log-probability logp_c*, and
+ *       finished |= token == eos;
+ *   C7. the state advances for every sequence, finished or not: H[s, n] <- h_c* (bit for bit), and the chosen row's cache and next logits
+ *       become the sequence's: sel_row[s] = s * k + c*, and beam_idx[s * k + i] = sel_row[s] for every i < k is the argument of ff_beam_gather;
+ *   C8. a row holding NaN or +-inf gives an unspecified choice, but every index written stays in range;
+ *   C9. fixed order throughout: equal inputs give equal bits, eager or replayed.
+ * Deliberate deviation from transformers: there a banned token (probability 0) can win on its penalty alone and a zero vector gives NaN;
+ * here dead candidates never win and the norms are clamped.
+ * ff_topk_logprob: logits are rows of `vocab` elements of `dtype` (bf16 or fp32), row r at element r * ld, ld >= vocab, element alignment
+ * only; tok [rows][k] int64 and logp [rows][k] fp32 are written; 1 <= k <= FF_CONTRASTIVE_K_MAX.  One launch, one workgroup per row.
+ * FF_ERR_SHAPE: a null pointer, rows <= 0, vocab <= 0, ld < vocab, k outside [1, FF_CONTRASTIVE_K_MAX], vocab < k.  FF_ERR_UNSUPPORTED: other dtypes.
+ * ff_contrastive_step: rules C2 - C7 in one launch, one workgroup per sequence (no workgroup waits for another).  hidden: [b * k][dim] of
+ * `dtype`, row r at element r * ld_hidden; hist: [b][max_len][dim] of `dtype`, contiguous, read at positions < *n_pos and written at
+ * *n_pos (nowhere if *n_pos is outside [0, max_len)); mask [b][max_len] uint8; cand_tok int64 / cand_logp fp32 [b][k] (what ff_topk_logprob
+ * wrote for the rows the candidates came from); finished [b] uint8, read and written; outputs next_tok [b] int64, logprob [b] fp32, sel_row
+ * [b] int64, beam_idx [b * k] int64, and - optional, may be NULL - score [b][k] fp32, the values of rule C4, for inspection.  eos = -1:
+ * none.  alpha and n_pos (= n) are DEVICE scalars: a captured call serves every value written there.  The workgroup keeps the k candidate
+ * vectors in LDS and reads H[s, :n] once.
+ * FF_ERR_SHAPE: a null pointer (score excepted), b, dim or max_len <= 0, k outside [1, FF_CONTRASTIVE_K_MAX], ld_hidden < dim.
+ * FF_ERR_UNSUPPORTED: other dtypes; k * dim * sizeof(element) > 131072 bytes (k = 8 serves dim <= 4096 in both dtypes).
+ * (ff_contrastive_desc is declared struct-then-typedef, like ff_beam_desc.)
+ * ------------------------------------------------------------------------------------------------------ */
+#define FF_CONTRASTIVE_K_MAX 8
+struct ff_contrastive_desc {
+    int dtype, b, k, dim;
+    long long ld_hidden;
+    int max_len, eos, pad, reserved;
+    const void* hidden;
+    void* hist;
+    const unsigned char* mask;
+    const long long* cand_tok;
+    const float* cand_logp;
+    unsigned char* finished;
+    long long* next_tok;
+    float* logprob;
+    long long* sel_row;
+    long long* beam_idx;
+    float* score;
+};
+typedef struct ff_contrastive_desc ff_contrastive_desc;
+int ff_topk_logprob(int dtype, int rows, int vocab, long long ld, const void* logits, int k, long long* tok, float* logp, ff_stream_t stream);
+int ff_contrastive_step(const ff_contrastive_desc* d, const float* alpha, const long long* n_pos, ff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Logits processors on the captured decode step (added under ABI 6): repetition penalty, no-repeat n-gram ban and minimum length, applied
