@@ -1051,10 +1051,17 @@ extern "C" int ff_xattn_saved_view(const ff_xattn_desc* d, int what, size_t* off
     XaSaved S;
     const uintptr_t base = 4096;
     xa_saved_layout(s, (void*)base, 0, S);
-    const size_t M = (size_t)s.b * s.L, stat = M * 4, act = M * s.d * s.es;
+    const size_t M = (size_t)s.b * s.L, stat = M * 4, act = M * s.d * s.es, head = M * s.inner * s.es, hid = M * s.ffi * s.es;
     const void* p = nullptr;
     size_t n = 0;
     switch (what) {
+        case FF_XA_SAVED_QS: p = S.Qs; n = head; break;
+        case FF_XA_SAVED_LSE: p = S.lse; n = (size_t)s.b * s.H * s.L * 4; break;
+        case FF_XA_SAVED_O: p = S.O; n = head; break;
+        case FF_XA_SAVED_ATTN_OUT: p = S.attn_out; n = act; break;
+        case FF_XA_SAVED_HPRE: p = S.Hpre; n = hid; break;
+        case FF_XA_SAVED_AACT: p = S.Aact; n = hid; break;
+        case FF_XA_SAVED_FFW_OUT: p = S.ffw_out; n = act; break;
         case FF_XA_SAVED_MEAN_A: p = S.mean_a; n = stat; break;
         case FF_XA_SAVED_RSTD_A: p = S.rstd_a; n = stat; break;
         case FF_XA_SAVED_YN: p = S.yn; n = act; break;
@@ -1093,6 +1100,28 @@ extern "C" size_t ff_xattn_wgrad_stash_bytes(const ff_xattn_desc* d) {
     if (ff::xa_check(d) != FF_OK) return 0;
     ff::XaStash T;
     return ff::xa_stash_layout(ff::XaDims(*d), nullptr, 0, T);
+}
+// the operands the data pass leaves for the grouped weight gradients, answered from xa_stash_layout itself (as ff_xattn_saved_view)
+extern "C" int ff_xattn_wgrad_stash_view(const ff_xattn_desc* d, int what, size_t* offset, size_t* bytes) {
+    using namespace ff;
+    FF_TRY(xa_check(d));
+    FF_CHECK(offset && bytes, FF_ERR_SHAPE, "ff_xattn_wgrad_stash_view: null argument");
+    const XaDims s(*d);
+    XaStash T;
+    const uintptr_t base = 4096;
+    xa_stash_layout(s, (void*)base, 0, T);
+    const size_t M = (size_t)s.b * s.L;
+    const void* p = nullptr;
+    size_t n = 0;
+    switch (what) {
+        case FF_XA_STASH_DY1: p = T.dy1; n = M * s.d * s.es; break;
+        case FF_XA_STASH_DH: p = T.dH; n = M * s.ffi * s.es; break;
+        case FF_XA_STASH_DQS: p = T.dQs; n = M * s.inner * s.es; break;
+        default: FF_CHECK(false, FF_ERR_SHAPE, "ff_xattn_wgrad_stash_view: what = %d", what);
+    }
+    *offset = (size_t)((uintptr_t)p - base);
+    *bytes = n;
+    return FF_OK;
 }
 extern "C" size_t ff_xattn_wgrad_workspace_bytes(const ff_xattn_desc* d) {
     if (ff::xa_check(d) != FF_OK) return 0;

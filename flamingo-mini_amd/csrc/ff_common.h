@@ -148,14 +148,18 @@ template <typename T> FF_DEV T fetch_args(const T& a) {
 }
 
 // ---- activations (flamingo_mini/utils.py:26-30) ------------------------------------------
+// Phi(h) as erfc(-h / sqrt 2) / 2, not (1 + erf(h / sqrt 2)) / 2: for h < -3 the sum cancels and leaves erff's absolute error (6e-8) on a
+// result of 1e-3 and less - the fp32 GELU of the block's feed-forward was up to 31 x its element bound in that tail (measured,
+// tests/test_hip_xattn_bounds.py); erfcf keeps the tail's relative accuracy.
+FF_DEV float gelu_cdf(float h) { return 0.5f * erfcf(-0.70710678118654752440f * h); }
 FF_DEV float act_fwd(float h, int act) {
-    if (act == FF_ACT_GELU) return 0.5f * h * (1.f + erff(h * 0.70710678118654752440f));
+    if (act == FF_ACT_GELU) return h * gelu_cdf(h);
     float r = fmaxf(h, 0.f);
     return act == FF_ACT_SQRELU ? r * r : r;
 }
 FF_DEV float act_grad(float h, int act) {  // d act / d h
     if (act == FF_ACT_GELU) {
-        float cdf = 0.5f * (1.f + erff(h * 0.70710678118654752440f));
+        float cdf = gelu_cdf(h);
         float pdf = 0.39894228040143267794f * __expf(-0.5f * h * h);
         return cdf + h * pdf;
     }

@@ -25,6 +25,9 @@ ACTS = {"gelu": ACT_GELU, "sqrelu": ACT_SQRELU, "relu": ACT_RELU}
 ATTN_DENSE, ATTN_MEDIA = 0, 1
 RESAMPLER_GLOBAL_PARAMS, RESAMPLER_LAYER_PARAMS, XATTN_PARAMS = 4, 12, 11
 XA_SAVED = {"mean_a": 0, "rstd_a": 1, "yn": 2, "y1": 3, "mean_f": 4, "rstd_f": 5, "xn_f": 6}      # FF_XA_SAVED_*: selectors of ff_xattn_saved_view
+XA_SAVED_STAGES = {"Qs": 7, "lse": 8, "O": 9, "attn_out": 10, "Hpre": 11, "Aact": 12, "ffw_out": 13}      # ... the other stages' results
+XA_SAVED_ORDER = ("mean_a", "rstd_a", "yn", "Qs", "lse", "O", "attn_out", "y1", "mean_f", "rstd_f", "xn_f", "Hpre", "Aact", "ffw_out")   # in memory
+XA_STASH = {"dy1": 0, "dH": 1, "dQs": 2}          # FF_XA_STASH_*: selectors of ff_xattn_wgrad_stash_view, in layout order
 WGRAD_GROUP_MAX = 12          # capacity of one ff_xattn_wgrad_grouped call (FF_WGRAD_GROUP_MAX); functional._WgradQueue.group = how many it batches
 
 
@@ -198,6 +201,7 @@ _SIGNATURES = {
     "ff_kv_project_fwd": (_I, [C.POINTER(KvProjDesc), _P, _P, _P, _P, _SZ, _P]),
     "ff_kv_project_bwd": (_I, [C.POINTER(KvProjDesc), _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "ff_xattn_wgrad_stash_bytes": (_SZ, [C.POINTER(XattnDesc)]),
+    "ff_xattn_wgrad_stash_view": (_I, [C.POINTER(XattnDesc), _I, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "ff_xattn_wgrad_workspace_bytes": (_SZ, [C.POINTER(XattnDesc)]),
     "ff_xattn_block_bwd_kv_data": (_I, [C.POINTER(XattnDesc), _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _SZ, _P]),
     "ff_xattn_wgrad_grouped": (_I, [C.POINTER(XattnDesc), _I, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),

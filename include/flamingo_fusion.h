@@ -321,9 +321,15 @@ size_t ff_xattn_kv_offset(const ff_xattn_desc* d);
 /* Where ff_xattn_block_fwd leaves the LayerNorm by-products that the backward reads, inside `saved` (host only; for tests and tools).
  * mean_a / rstd_a: fp32 (batch * n_tokens) statistics of attn.norm; yn = attn.norm(y); y1 = y + tanh(alpha_attn) * to_out(...);
  * mean_f / rstd_f: statistics of ffw.0 over y1; xn_f = ffw.0(y1).  yn, y1 and xn_f are (batch * n_tokens, dim) in the descriptor's dtype.
+ * The other stages' results, selectors 7..13 (additions; the numbering above is unchanged): Qs = scale * to_q(yn) and O, the attention's
+ * output, (batch * n_tokens, heads * dim_head); lse, fp32 (batch, heads, n_tokens), 1e30 for a row that sees no key; attn_out = to_out(O),
+ * (batch * n_tokens, dim); Hpre = ffw.1(xn_f) and Aact = act(Hpre), (batch * n_tokens, ff_mult * dim); ffw_out = ffw.3(Aact), (batch *
+ * n_tokens, dim).  In memory the regions follow each other as mean_a, rstd_a, yn, Qs, lse, O, attn_out, y1, mean_f, rstd_f, xn_f, Hpre,
+ * Aact, ffw_out.
  * Returns FF_OK and the region's byte offset and size, or FF_ERR_SHAPE for a bad descriptor, selector or pointer. */
 enum { FF_XA_SAVED_MEAN_A = 0, FF_XA_SAVED_RSTD_A = 1, FF_XA_SAVED_YN = 2, FF_XA_SAVED_Y1 = 3, FF_XA_SAVED_MEAN_F = 4, FF_XA_SAVED_RSTD_F = 5,
-       FF_XA_SAVED_XN_F = 6 };
+       FF_XA_SAVED_XN_F = 6, FF_XA_SAVED_QS = 7, FF_XA_SAVED_LSE = 8, FF_XA_SAVED_O = 9, FF_XA_SAVED_ATTN_OUT = 10, FF_XA_SAVED_HPRE = 11,
+       FF_XA_SAVED_AACT = 12, FF_XA_SAVED_FFW_OUT = 13 };
 int ff_xattn_saved_view(const ff_xattn_desc* d, int what, size_t* offset, size_t* bytes);
 int ff_xattn_block_fwd(const ff_xattn_desc* d, const void* y, const void* visual_features, const int* text_time,
                        const void* const* params, const void* cached_k, const void* cached_v, void* y_out,
@@ -376,6 +382,11 @@ int ff_xattn_block_bwd_kv(const ff_xattn_desc* d, const void* y, const void* k, 
  * ------------------------------------------------------------------------------------------------------ */
 #define FF_WGRAD_GROUP_MAX 12
 size_t ff_xattn_wgrad_stash_bytes(const ff_xattn_desc* d);
+/* Where ff_xattn_block_bwd_kv_data leaves the three operands inside `stash` (host only; for tests and tools, as ff_xattn_saved_view):
+ * d y1 (batch * n_tokens, dim), d H (batch * n_tokens, ff_mult * dim), the gradient of Hpre, and d Qs (batch * n_tokens, heads * dim_head),
+ * in this order and in the descriptor's dtype. */
+enum { FF_XA_STASH_DY1 = 0, FF_XA_STASH_DH = 1, FF_XA_STASH_DQS = 2 };
+int ff_xattn_wgrad_stash_view(const ff_xattn_desc* d, int what, size_t* offset, size_t* bytes);
 size_t ff_xattn_wgrad_workspace_bytes(const ff_xattn_desc* d);
 int ff_xattn_block_bwd_kv_data(const ff_xattn_desc* d, const void* y, const void* k, const void* v, const int* text_time,
                                const void* const* params, const void* dy_out, const void* saved, size_t saved_bytes, void* const* grads,

@@ -175,14 +175,16 @@ def _bhnd(t):
     return (t.detach().double().cpu().numpy() if torch.is_tensor(t) else np.asarray(t, np.float64)).transpose(0, 2, 1, 3)
 
 
-def attention_ref(q, k, v, do=None, tt=None, n_visual=0):
+def attention_ref(q, k, v, do=None, tt=None, n_visual=0, e_do=None):
     """Everything util.attn_bound_ok needs, in float64 from the tensors as stored ((b, n, h, d); tt (b, n_q) or None = dense), with the
     allowed key set of each row from oracle.attention_masks.  A dict of float64 numpy arrays:
       lse (b, h, n_q), o (b, n_q, h, d) and, with dO, dq, dk, dv; per output x: t_x (the terms one float32 rounding is proportional to),
       pu_x (what the bf16 rounding of P / dS scales), ut_x (dq, dk: what the rounding of the stored O scales through D), fl_x (what a
       probability below 2^-126, lost by the device's exp, scales); kinds (b, n_q): 0 zero row, 1 softmax row, 2 uniform row; p (b, h, n_q,
       n_kv) and s, for the case table's own tests.  A zero row: p = 0, o = 0, lse = 1e30 (the kernel's sentinel), no gradient; a uniform
-      row: all scores 0 over all keys, no gradient to the scores."""
+      row: all scores 0 over all keys, no gradient to the scores.
+      With e_do (the fused block kernels, which form dO themselves and never store it: tests/xattn_cases.py) also e_dv, e_dq, e_dk, the
+      fixed terms util.attn_bound_ok adds when asked (extra=True)."""
     Q, K, V = _bhnd(q), _bhnd(k), _bhnd(v)
     b, h, n_q, dh = Q.shape
     n_kv = K.shape[2]
@@ -226,6 +228,10 @@ def attention_ref(q, k, v, do=None, tt=None, n_visual=0):
                fl_dq=back(fl @ np.abs(K)),
                dk=back(T(ds) @ Q), t_dk=back(T(g) @ np.abs(Q)), pu_dk=back(T(np.abs(ds)) @ np.abs(Q)), ut_dk=back(T(Dabs * ps) @ np.abs(Q)),
                fl_dk=back(T(fl) @ np.abs(Q)))
+    if e_do is not None:      # dO is itself a result with the element-wise error bound e_do (b, n_q, h, d): what that adds, to first order
+        E = _bhnd(e_do)
+        hh = np.where(soft, E @ np.abs(VT) + (E * np.abs(o)).sum(-1, keepdims=True), 0.0)      # h_ij = sum_d e_id (|v_jd| + |o_id|): dp_ij - D_i
+        out.update(e_dv=back(T(p) @ E), e_dq=back((ps * hh) @ np.abs(K)), e_dk=back(T(ps * hh) @ np.abs(Q)))
     return out
 
 
@@ -266,17 +272,22 @@ def _ranges(case_tt, n_q, n_kv, n_visual, mutate):
     lo, hi, sm, un = row_ranges(case_tt, n_q, n_kv, n_visual)
     if mutate == "range-shift":                     # the image's keys taken one key late
         lo, hi = np.where(sm == 1, lo + 1, lo), np.where(sm == 1, hi + 1, hi)
+    if mutate == "drop-last-key":                   # the last key of the last image (the ragged end of the key tile) is never seen
+        hi = np.where((sm == 1) & (hi == n_kv), hi - 1, hi)
+    if mutate == "uniform-as-image":                # a text_time past the last image is taken for the first image
+        lo, hi, sm, un = np.where(un == 1, 0, lo), np.where(un == 1, n_visual, hi), np.where(un == 1, 1, sm), 0 * un
     return lo, hi, sm, un
 
 
-def attn_fwd_f32(q, k, v, tt=None, n_visual=0, mutate=None, at=(0, 0, 0), tile=0):
+def attn_fwd_f32(q, k, v, tt=None, n_visual=0, mutate=None, at=(0, 0, 0), tile=0, bm=TILE, keep_f32=False):
     """attn_fwd_kernel + attn_fwd_loop: per workgroup of 64 queries the key tiles [blo, bhi) of block_range, per tile S^T = K Q^T, the
     masked scores at -1e30, the group maximum, alpha = exp(m - m_new), p = exp(s - m_new) (0 where masked), each lane's partial lsum
     (its 16 of the tile's 64 keys) rescaled and summed over the four lanes at the end, acc * alpha + P V with P rounded to bf16 in bf16,
     o = acc * (1 / lsum) rounded to storage, lse = m + log(lsum), 1e30 where lsum = 0.  Returns (o (b, n_q, h, d) in q's dtype, lse
     (b, h, n_q) float32).  `mutate` with at = (sample, head, query) and `tile` (index of a 64-key tile): skip-tile (that row does not see
     that tile), no-rescale (acc is not multiplied by alpha), lse-log2 (that row's lse + log 2), range-shift (every image's range one key
-    late), zero-1e-30 (the first zero row of sample `at[0]` holds 1e-30)."""
+    late), zero-1e-30 (the first zero row of sample `at[0]` holds 1e-30), drop-last-key, uniform-as-image (_ranges).  `bm`: queries per
+    workgroup (the fused kernels of csrc/ff_xattn_fused.hip run 32 or 64); keep_f32: o is returned as accumulated, not rounded to storage."""
     dtype, f = q.dtype, np.float32
     Q, K, V = _f32(q), _f32(k), _f32(v)
     b, h, n_q, dh = Q.shape
@@ -285,8 +296,8 @@ def attn_fwd_f32(q, k, v, tt=None, n_visual=0, mutate=None, at=(0, 0, 0), tile=0
     o, lse = np.zeros_like(Q), np.zeros((b, h, n_q), np.float32)
     with np.errstate(all="ignore"):
         for s in range(b):
-            for q0 in range(0, n_q, TILE):
-                rows = slice(q0, min(q0 + TILE, n_q))
+            for q0 in range(0, n_q, bm):
+                rows = slice(q0, min(q0 + bm, n_q))
                 l, u, uni = lo[s, rows, None], hi[s, rows, None], un[s, rows, None] == 1
                 blo, bhi = _block_range(l, u)
                 R = l.shape[0]
@@ -296,7 +307,7 @@ def attn_fwd_f32(q, k, v, tt=None, n_visual=0, mutate=None, at=(0, 0, 0), tile=0
                     z = Q[s, :, rows] @ kt.transpose(0, 2, 1)
                     key = k0 + np.arange(TILE)[None, :]
                     z = np.where((key >= l) & (key < u), np.where(uni, f(0), z), NEG_BIG).astype(f)
-                    if mutate == "skip-tile" and s == at[0] and k0 == tile * TILE and q0 <= at[2] < q0 + TILE:
+                    if mutate == "skip-tile" and s == at[0] and k0 == tile * TILE and q0 <= at[2] < q0 + bm:
                         z[at[1], at[2] - q0] = NEG_BIG
                     m_new = np.maximum(m, z.max(-1))
                     alpha = _exp(m - m_new)
@@ -315,22 +326,23 @@ def attn_fwd_f32(q, k, v, tt=None, n_visual=0, mutate=None, at=(0, 0, 0), tile=0
         lse[at] += np.float32(np.log(2.0))
     if mutate == "zero-1e-30":
         o[at[0], :, int(np.nonzero((hi - lo)[at[0]] == 0)[0][0])] = np.float32(1e-30)
-    return _store(o, dtype), torch.from_numpy(lse)
+    return _store(o, F32 if keep_f32 else dtype), torch.from_numpy(lse)
 
 
-def attn_bwd_f32(q, k, v, o, do, lse, tt=None, n_visual=0, mutate=None, at=(0, 0, 0), tile=0):
+def attn_bwd_f32(q, k, v, o, do, lse, tt=None, n_visual=0, mutate=None, at=(0, 0, 0), tile=0, bm=TILE, D=None):
     """attn_bwd_dq_kernel and attn_bwd_dkv_kernel: D = rowsum(dO . O) from the STORED o; p = exp(s - L) with the stored lse (0 outside the
     row's range); dS = p (dP - D), 0 for zero and uniform rows; dQ += dS K over the key tiles of block_range (zero and uniform rows have an
     empty range there); per 64 keys, over all 64-query tiles, dV += P^T dO and dK += dS^T Q, P and dS rounded to bf16 in bf16.  Returns
     (dq, dk, dv) in q's dtype.  `mutate`: D-zero (D of query `at` is 0), dk-miss-qtile (dK skips query tile `tile`), uniform-dq (uniform
-    rows are treated as softmax rows by the dQ kernel), range-shift."""
+    rows are treated as softmax rows by the dQ kernel), range-shift, drop-last-key, uniform-as-image.  `bm`: queries per workgroup of the
+    dQ pass; D (b, h, n_q) float32: taken in place of rowsum(dO . O)."""
     dtype, f = q.dtype, np.float32
     Q, K, V, Om, dO = _f32(q), _f32(k), _f32(v), _f32(o), _f32(do)
     L = lse.detach().float().cpu().numpy()
     b, h, n_q, dh = Q.shape
     n_kv = K.shape[2]
     lo, hi, sm, un = _ranges(tt, n_q, n_kv, n_visual, mutate)
-    D = (dO * Om).sum(-1, dtype=f)
+    D = (dO * Om).sum(-1, dtype=f) if D is None else np.ascontiguousarray(D, f)
     if mutate == "D-zero":
         D[at] = 0
     dq, dk, dv = np.zeros_like(Q), np.zeros_like(K), np.zeros_like(V)
@@ -338,8 +350,8 @@ def attn_bwd_f32(q, k, v, o, do, lse, tt=None, n_visual=0, mutate=None, at=(0, 0
         for s in range(b):
             keep = (sm[s] == 1) | ((un[s] == 1) if mutate == "uniform-dq" else False)
             lq, uq = np.where(keep, lo[s], 0), np.where(keep, hi[s], 0)
-            for q0 in range(0, n_q, TILE):
-                rows = slice(q0, min(q0 + TILE, n_q))
+            for q0 in range(0, n_q, bm):
+                rows = slice(q0, min(q0 + bm, n_q))
                 l, u = lq[rows, None], uq[rows, None]
                 blo, bhi = _block_range(l, u)
                 acc = np.zeros((h, l.shape[0], dh), f)

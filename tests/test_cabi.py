@@ -154,8 +154,47 @@ def test_workspace_queries_and_error_codes_without_a_device():
     assert [n for _, n in views] == [rows * 4, rows * 4, rows * 1280 * 2, rows * 1280 * 2, rows * 4, rows * 4, rows * 1280 * 2]
     assert views[0][0] >= kv_bytes and all(o % 16 == 0 for o, _ in views)
     assert all(a[0] + a[1] <= b[0] for a, b in zip(views, views[1:])) and views[-1][0] + views[-1][1] <= lib.ff_xattn_saved_bytes(x)
-    assert lib.ff_xattn_saved_view(x, 7, C.byref(off), C.byref(nb)) == -1 and b"what" in lib.ff_last_error()
+    # ... and with the other stages' results (selectors 7..13): all fourteen regions, in the order they have in memory
+    codes = {**ffi.XA_SAVED, **ffi.XA_SAVED_STAGES}
+    assert sorted(codes.values()) == list(range(14)) and sorted(ffi.XA_SAVED_ORDER) == sorted(codes)
+    sizes = dict(mean_a=rows * 4, rstd_a=rows * 4, yn=rows * 1280 * 2, Qs=rows * 512 * 2, lse=32 * 8 * 32 * 4, O=rows * 512 * 2, attn_out=rows * 1280 * 2,
+                 y1=rows * 1280 * 2, mean_f=rows * 4, rstd_f=rows * 4, xn_f=rows * 1280 * 2, Hpre=rows * 5120 * 2, Aact=rows * 5120 * 2,
+                 ffw_out=rows * 1280 * 2)
+    every = []
+    for name in ffi.XA_SAVED_ORDER:
+        assert lib.ff_xattn_saved_view(x, codes[name], C.byref(off), C.byref(nb)) == 0
+        assert nb.value == sizes[name], (name, nb.value)
+        every.append((off.value, nb.value))
+    assert every[0][0] >= kv_bytes and all(o % 16 == 0 for o, _ in every)
+    assert all(a[0] + a[1] <= b[0] for a, b in zip(every, every[1:])) and every[-1][0] + every[-1][1] <= lib.ff_xattn_saved_bytes(x)
+    for xd in (ffi.XattnDesc(ffi.DTYPE_F32, 3, 7, 96, 32, 5, 8, 2, 16, 2, ffi.ACT_GELU, 7, 0),                    # fp32, odd row count
+               ffi.XattnDesc(ffi.DTYPE_BF16, 5, 1, 256, 32, 2, 32, 8, 64, 2, ffi.ACT_GELU, 24, 23, ffi.Strides(64 * 1024, 1024, 64), ffi.Strides(64 * 1024, 1024, 64))):
+        ext = xd.cached_k.sr != 0                # K / V from outside: `saved` holds no K / V region
+        r, es = xd.batch * xd.n_tokens, 4 if xd.dtype == ffi.DTYPE_F32 else 2
+        inner = xd.heads * xd.dim_head
+        want = dict(mean_a=r * 4, rstd_a=r * 4, yn=r * xd.dim * es, Qs=r * inner * es, lse=r * xd.heads * 4, O=r * inner * es, attn_out=r * xd.dim * es,
+                    y1=r * xd.dim * es, mean_f=r * 4, rstd_f=r * 4, xn_f=r * xd.dim * es, Hpre=r * 2 * xd.dim * es, Aact=r * 2 * xd.dim * es,
+                    ffw_out=r * xd.dim * es)
+        got = []
+        for name in ffi.XA_SAVED_ORDER:
+            assert lib.ff_xattn_saved_view(xd, codes[name], C.byref(off), C.byref(nb)) == 0
+            assert nb.value == want[name], (name, nb.value)
+            got.append((off.value, nb.value))
+        assert got[0][0] >= (0 if ext else xd.batch * xd.n_media * xd.n_visual * 2 * inner * es)
+        assert all(a[0] + a[1] <= b[0] for a, b in zip(got, got[1:])) and got[-1][0] + got[-1][1] <= lib.ff_xattn_saved_bytes(xd)
+    assert lib.ff_xattn_saved_view(x, 14, C.byref(off), C.byref(nb)) == -1 and b"what" in lib.ff_last_error()
+    assert lib.ff_xattn_saved_view(x, -1, C.byref(off), C.byref(nb)) == -1 and b"what" in lib.ff_last_error()
     assert lib.ff_xattn_saved_view(x, 0, None, C.byref(nb)) == -1
+    # ff_xattn_wgrad_stash_view: d y1, d H, d Qs inside the stash, apart and in layout order
+    stash = []
+    for name, code in ffi.XA_STASH.items():
+        assert lib.ff_xattn_wgrad_stash_view(x, code, C.byref(off), C.byref(nb)) == 0
+        stash.append((off.value, nb.value))
+    assert list(ffi.XA_STASH) == ["dy1", "dH", "dQs"] and [n for _, n in stash] == [rows * 1280 * 2, rows * 5120 * 2, rows * 512 * 2]
+    assert stash[0][0] == 0 and all(o % 16 == 0 for o, _ in stash)
+    assert all(a[0] + a[1] <= b[0] for a, b in zip(stash, stash[1:])) and stash[-1][0] + stash[-1][1] <= lib.ff_xattn_wgrad_stash_bytes(x)
+    assert lib.ff_xattn_wgrad_stash_view(x, 3, C.byref(off), C.byref(nb)) == -1 and b"what" in lib.ff_last_error()
+    assert lib.ff_xattn_wgrad_stash_view(x, 0, C.byref(off), None) == -1
     assert lib.ff_xattn_block_fwd(x, None, None, None, None, None, None, None, None, 0, None, 0, None) == -1     # null arguments
     g = ffi.GemmDesc(ffi.DTYPE_BF16, 1024, 1280, 5120, 0, 0, ffi.rowmap(5120), ffi.rowmap(5120), ffi.rowmap(1280), 1.0, -1, -1, 0)
     assert lib.ff_gemm_workspace_bytes(g) > 0                                                                      # long K, few tiles -> split-K
